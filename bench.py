@@ -2,9 +2,18 @@
 """Headline benchmark: env steps/sec of XarmPDPickAndPlace-v0 (BASELINE.json `metric`).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E] [--workload pnp|reach|handover|stack|handover2]
-                  [--scaling weak|strong] [--repeats R] [--episode-phase desync|lockstep] [--aged-preroll P]
-                  [--no-aged] [--no-lockstep] [--no-lazy] [--no-strong] [--no-extras] [--no-cpu-baseline] [--allow-variant-lib]
+                  [--scaling weak|strong] [--repeats R] [--episode-phase desync|lockstep] [--dump-outputs DIR] [--allow-variant-lib]
+                  [--full [--aged-preroll P] [--no-aged] [--no-lockstep] [--no-lazy] [--no-strong] [--no-extras] [--no-cpu-baseline]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run (no --full) does only what `value` needs: set up, W warm-up steps, ONE window of exactly K timed steps
+(`--repeats` defaults to 1), the outputs of the last timed step if --dump-outputs is given, the JSON line.  `--full` adds
+everything else below: three windows by default, the extra legs and the CPU baseline.
+`--dump-outputs DIR` writes what the caller of env.step received from the last timed step (observation, achieved_goal,
+desired_goal, reward, done and the info arrays; rank 0's shard) as DIR/<name>.npy in float32 (float64 for 32/64-bit
+integers); above 64 MB in all, a fixed seeded sample of env rows is written instead, its indices in DIR/sample_rows.npy.
+Inputs (env seed, action ring, episode phases) are fixed, so two builds run with the same arguments can be compared
+array for array.
 
 A "step" is one env step of EVERY environment of the job (one xarm_step call per rank), including
 the automatic resets of finished episodes.  `--scaling weak` (default, what `value` uses): each rank owns
@@ -12,7 +21,7 @@ the automatic resets of finished episodes.  `--scaling weak` (default, what `val
 ids rank*E .. (rank+1)*E-1; `--scaling strong`: the same number of environments in TOTAL, split over the ranks
 (gym_xarm_amd.distributed.shard_range).  No data-path collective either way.  Inputs are
 synthetic: a ring of 64 pre-generated uniform[-1,1] action tensors resident in HBM, so the timed region contains no
-RNG and no host->device traffic.  The timed window of K steps is repeated `--repeats` times back to back (default 3);
+RNG and no host->device traffic.  The timed window of K steps is repeated `--repeats` times back to back (default 1, 3 with --full);
 `value` is the MEDIAN window (max over ranks per window), the others are listed.  `--episode-phase desync` spreads
 the per-env step counters uniformly over the episode length before the warm-up, so that time-limit resets arrive at
 their steady-state rate (E / max_episode_steps per step) instead of all E at once every 50th step; `lockstep` keeps the
@@ -22,7 +31,7 @@ Rank 0 prints ONE JSON line.  `library` in it is xarm_version() and the path of 
 (a development build with fewer solver sweeps) or a library named by XARM_HIP_LIB makes bench.py exit non-zero unless
 --allow-variant-lib says the run is a development measurement.
 
-Besides `value` (the K timed steps right after the W warm-up steps) the line carries, each measured by the same
+With --full, besides `value` (the K timed steps right after the W warm-up steps) the line carries, each measured by the same
 three-window protocol and never feeding `value`:
   aged_state      the same handle after an untimed pre-roll of --aged-preroll (default 1 000) further steps: random actions
                   knock the objects about, reset wavefronts then carry finger-contact rows through their ticks - the rate a
@@ -30,7 +39,8 @@ three-window protocol and never feeding `value`:
   strong_scaling  only when world > 1 under weak scaling: the configured env count (65 536) as the TOTAL, split over the
                   ranks by shard_range - the other reading of "65 536 parallel envs at 1/2/4/8 GPUs" (skip: --no-strong);
   lockstep_phase  episodes in lockstep from reset() (skip: --no-lockstep); lazy_reset: the opt-in lazy auto-reset (--no-lazy).
---no-extras skips all four (what the profiling scripts use).
+--no-extras skips all four (what the profiling scripts use); `cpu_baseline` (world 1; skip: --no-cpu-baseline) is the
+CPU oracle on the host cores.
 
 `--workload` selects one of the other BASELINE.json configs for the same measurement (same JSON schema, its own
 metric name): reach = config 2 (XarmReach-v0, 4 096 envs), stack = config 4 (XarmPDStackTower-v0, 8 192 envs per
@@ -119,15 +129,17 @@ def cpu_baseline(workload="pnp"):
 
 def timed_window(env, ring, first, steps, world, dev, dist, D, torch, sync):
     """time exactly `steps` calls of env.step between two barriers + synchronize; returns max-over-ranks seconds,
-    episodes finished, and the HIP-event averages of the step kernel and of the reset kernels (ms per call)"""
+    episodes finished, the HIP-event averages of the step kernel and of the reset kernels (ms per call), the launch count
+    and what the last call returned (the env's own buffers: read them before the next step)"""
     env.timing_enable(True)
     if world > 1:
         dist.barrier()
     sync()
     t0 = time.perf_counter()
     n_done = torch.zeros((), device=dev)
+    last = None
     for i in range(steps):
-        obs, rew, done, info = env.step(ring[(first + i) % 64])
+        last = obs, rew, done, info = env.step(ring[(first + i) % 64])
         n_done += done.sum()
     sync()
     if world > 1:
@@ -139,7 +151,45 @@ def timed_window(env, ring, first, steps, world, dev, dist, D, torch, sync):
     kstep_ms = D.max_over_ranks(kstep_ms_total / max(launches, 1), device=dev)
     reset_ms = D.max_over_ranks(reset_ms_total / max(launches, 1), device=dev)
     resets = D.sum_over_ranks(float(n_done.item()), device=dev)
-    return dt, resets, kstep_ms, reset_ms, int(launches)
+    return dt, resets, kstep_ms, reset_ms, int(launches), last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(last, out_dir):
+    """--dump-outputs: the arrays the caller of env.step received from the last timed step (obs dict, reward, done, info),
+    as out_dir/<name>.npy; float32, or float64 for 32/64-bit integers (exact).  Arrays over the envs are cut to a fixed,
+    seeded sample of rows (out_dir/sample_rows.npy) when the whole set would exceed DUMP_LIMIT_BYTES."""
+    import numpy as np
+    import torch
+    obs, rew, done, info = last
+    flat = {}
+
+    def add(name, x):
+        if isinstance(x, dict):
+            for k, v in x.items():
+                add("%s_%s" % (name, k) if name else k, v)
+        elif isinstance(x, torch.Tensor):
+            flat["".join(c if c.isalnum() or c in "-_" else "_" for c in name)] = x.detach().cpu().numpy()
+
+    add("", obs)
+    add("reward", rew)
+    add("done", done)
+    add("info", info)
+    for k, a in flat.items():
+        wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize >= 4)
+        flat[k] = a.astype(np.float64 if wide else np.float32)
+    n_rows = max((a.shape[0] for a in flat.values() if a.ndim), default=0)
+    total = sum(a.nbytes for a in flat.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES and n_rows > 0:
+        keep = max(1, n_rows * DUMP_LIMIT_BYTES // (total + 8 * n_rows) - 1)      # (+ 8 B per row: sample_rows itself)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+        flat = {k: (a[rows] if a.ndim and a.shape[0] == n_rows else a) for k, a in flat.items()}
+        flat["sample_rows"] = rows.astype(np.float64)
+    for k, a in flat.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def main():
@@ -150,8 +200,10 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=None)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="pnp")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=None, help="timed windows of --steps steps (default 1, 3 with --full)")
     ap.add_argument("--episode-phase", choices=["auto", "desync", "lockstep"], default="auto")
+    ap.add_argument("--full", action="store_true", help="also the extra legs and the CPU baseline (each with its --no-* switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-lazy", action="store_true", help="skip the extra measurement of the opt-in lazy auto-reset mode")
     ap.add_argument("--no-lockstep", action="store_true", help="skip the lockstep-phase leg")
@@ -161,8 +213,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip every leg that does not feed `value`")
     ap.add_argument("--allow-variant-lib", action="store_true", help="development measurement: accept a TIMING VARIANT build / XARM_HIP_LIB")
     args = ap.parse_args()
-    if args.no_extras:
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.no_extras or not args.full:
         args.no_lazy = args.no_lockstep = args.no_aged = args.no_strong = True
+    if not args.full:
+        args.no_cpu_baseline = True
 
     import torch
     import torch.distributed as dist
@@ -255,7 +311,9 @@ def main():
         return ws, ws[order[len(order) // 2]]
 
     ring_of = {id(env): ring}
-    windows, (dt, resets, kstep_ms, reset_ms, launches) = measure(env, args.warmup)
+    windows, (dt, resets, kstep_ms, reset_ms, launches, _) = measure(env, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(windows[-1][5], args.dump_outputs)          # the last timed step, before any other leg steps the handle
     if pipe["fast_pipeline"] and hasattr(env, "debug_counts"):
         # (outside the timed windows: the read synchronises) how many envs the fast kernel handed to the cooperative kernel(s) in the last call
         pipe = dict(pipe, handed_off_last_call=int(env.debug_counts()[1]))
@@ -272,7 +330,7 @@ def main():
         for i in range(args.aged_preroll):
             env.step(ring[i % 64])
         sync()
-        aw, (adt, aresets, akstep, areset, _) = measure(env, args.aged_preroll)
+        aw, (adt, aresets, akstep, areset, _, _) = measure(env, args.aged_preroll)
         aged = {"value": total_envs * args.steps / adt, "unit": "env steps/s", "preroll_steps": args.aged_preroll + args.warmup + args.steps * len(windows),
                 "ms_per_step": adt / args.steps * 1e3, "step_kernel_ms": akstep, "reset_kernels_ms": areset,
                 "resets_per_step": aresets / args.steps,
@@ -292,7 +350,7 @@ def main():
         for i in range(args.warmup):
             senv.step(sring[i % 64])
         sync()
-        sw, (sdt, sres, skstep, sreset, _) = measure(senv, args.warmup)
+        sw, (sdt, sres, skstep, sreset, _, _) = measure(senv, args.warmup)
         s_lim = senv.kernel_limits() if hasattr(senv, "kernel_limits") else (0, 0)
         strong = {"value": n_cfg * args.steps / sdt, "unit": "env steps/s", "total_envs": n_cfg, "envs_per_gpu": shi - slo,
                   "shard_range_rank0": [int(slo), int(shi)], "ms_per_step": sdt / args.steps * 1e3,

@@ -94,7 +94,7 @@ def test_bench_rank_plumbing_two_ranks_gloo(tmp_path, scaling):
                XARM_BENCH_STUB_LOG=log, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "tests"), ROOT, os.environ.get("PYTHONPATH", "")]))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "3",
-           "--envs-per-gpu", "101", "--scaling", scaling, "--repeats", "2", "--no-cpu-baseline", "--aged-preroll", "25"]
+           "--envs-per-gpu", "101", "--scaling", scaling, "--repeats", "2", "--full", "--no-cpu-baseline", "--aged-preroll", "25"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.split("\n") if l.startswith("{")]

@@ -85,31 +85,27 @@ def test_oracle_reach_behaviour(oracle):
 
 
 def test_reach_model_matches_urdf(oracle):
-    import xml.etree.ElementTree as ET
-    urdf = "/root/reference/gym_xarm/envs/urdf/xarm7.urdf"
-    if not os.path.exists(urdf):
-        pytest.skip("reference not present")
+    """against the reference's xarm7.urdf, as tools/gen_golden.py read it into tests/golden/model_reference.json"""
+    import json
     js = oracle.load_model_json(oracle.REACH_JSON)
-    root = ET.parse(urdf).getroot()
-    links = {l.get("name"): l for l in root.findall("link")}
-    joints = {j.find("child").get("link"): j for j in root.findall("joint")}
+    urdf = json.load(open(os.path.join(ROOT, "tests", "golden", "model_reference.json")))["xarm7_urdf"]
+    joints, inertials = urdf["joints"], urdf["inertials"]
     names = [l["name"] for l in js["links"]]
     for l in js["links"]:
         j = joints[l["name"]]
-        assert j.get("type") == l["joint"]
-        assert j.find("parent").get("link") == ("link_base" if l["parent"] < 0 else names[l["parent"]])
-        np.testing.assert_allclose([float(x) for x in j.find("origin").get("xyz").split()], l["origin_xyz"], atol=0)
+        assert j["type"] == l["joint"]
+        assert j["parent"] == ("link_base" if l["parent"] < 0 else names[l["parent"]])
+        np.testing.assert_allclose(j["origin_xyz"], l["origin_xyz"], atol=0)
         if l["joint"] != "fixed":
-            np.testing.assert_allclose([float(x) for x in j.find("axis").get("xyz").split()], l["axis"], atol=0)
-            assert float(j.find("limit").get("lower")) == l["lower"] and float(j.find("limit").get("upper")) == l["upper"]
-        inert = links[l["name"]].find("inertial")
+            np.testing.assert_allclose(j["axis"], l["axis"], atol=0)
+            assert j["lower"] == l["lower"] and j["upper"] == l["upper"]
+        inert = inertials[l["name"]]
         if inert is None:
             assert l["mass"] == 1.0
             continue
-        assert float(inert.find("mass").get("value")) == l["mass"]
-        np.testing.assert_allclose([float(x) for x in inert.find("origin").get("xyz").split()], l["com"], atol=0)
-        I = inert.find("inertia")
-        np.testing.assert_allclose([float(I.get(k)) for k in ("ixx", "ixy", "ixz", "iyy", "iyz", "izz")], l["inertia"], atol=0)
+        assert inert["mass"] == l["mass"]
+        np.testing.assert_allclose(inert["com"], l["com"], atol=0)
+        np.testing.assert_allclose(inert["inertia"], l["inertia"], atol=0)
     assert names.index("left_outer_knuckle") + 1 == 10 and len(names) + 1 == 17    # gripper_driver_index, num_joints (:21-22)
 
 

@@ -4,6 +4,7 @@ stand-alone executables that replay a reset + a few steps of PickAndPlace and Re
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -91,8 +92,11 @@ int main(void) { unsigned int o[4]; xo_philox(1, 2, 3, 4, 5, o); printf("ok %u %
 
 
 def _have_sanitizers():
-    return subprocess.run("echo 'int main(){return 0;}' | g++ -x c++ - -fsanitize=address,undefined -o /tmp/_san_probe && /tmp/_san_probe",
-                          shell=True, capture_output=True).returncode == 0
+    # the probe goes to a private directory: a fixed name under the shared temp dir may belong to another user
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "san_probe")
+        return subprocess.run(["g++", "-x", "c++", "-", "-fsanitize=address,undefined", "-o", exe], input=b"int main(){return 0;}",
+                              capture_output=True).returncode == 0 and subprocess.run([exe], capture_output=True).returncode == 0
 
 
 @pytest.mark.skipif(not _have_sanitizers(), reason="libasan/libubsan not available")

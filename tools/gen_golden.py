@@ -285,8 +285,86 @@ def stack_tower():
     print("wrote stack_reward_reference.npz")
 
 
+def _urdf_table(path):
+    """joints (keyed by child link) and inertials of a URDF, as plain numbers: what tests/test_model.py and tests/test_reach.py
+    hold the model tables against"""
+    import xml.etree.ElementTree as ET
+
+    def floats(e, attr):
+        return None if e is None else [float(x) for x in e.get(attr).split()]
+    root = ET.parse(path).getroot()
+    joints = {}
+    for j in root.findall("joint"):
+        org, lim, dyn = j.find("origin"), j.find("limit"), j.find("dynamics")
+        joints[j.find("child").get("link")] = {
+            "type": j.get("type"), "parent": j.find("parent").get("link"), "origin_xyz": floats(org, "xyz"), "origin_rpy": floats(org, "rpy"),
+            "axis": floats(j.find("axis"), "xyz"), "lower": None if lim is None else float(lim.get("lower")),
+            "upper": None if lim is None else float(lim.get("upper")), "damping": None if dyn is None else float(dyn.get("damping"))}
+    inertials = {}
+    for l in root.findall("link"):
+        i = l.find("inertial")
+        inertials[l.get("name")] = None if i is None else {
+            "mass": float(i.find("mass").get("value")), "com": floats(i.find("origin"), "xyz"),
+            "inertia": [float(i.find("inertia").get(k)) for k in ("ixx", "ixy", "ixz", "iyy", "iyz", "izz")]}
+    return {"joints": joints, "inertials": inertials}
+
+
+def _pnp_scene_constants(path):
+    """the scene constants of XarmPickAndPlace that gym_xarm_amd/model/xarm7_pd.json restates, read from the env file"""
+    import re
+    src = open(path).read()
+
+    def grab(pattern):
+        m = re.search(pattern, src)
+        assert m, pattern
+        return m
+
+    def box(name, sep=" "):
+        m = grab(r"self\.%s = spaces\.Box\(low=np\.array\(\[([^\]]+)\]\),%shigh=np\.array\(\[([^\]]+)\]\)" % (name, sep))
+        return [float(x) for x in m.group(1).split(",")], [float(x) for x in m.group(2).split(",")]
+    num, den = grab(r"self\.timeStep=([\d.]+)/([\d.]+)").groups()
+    lego = float(grab(r"self\.lego_length = ([\d.]+)").group(1))
+    half = grab(r"halfExtents = \[self\.lego_length/2, ([\d.]+), ([\d.]+)\]").groups()
+    gear = grab(r"gearRatio=(-?[\d.]+), erp=([\d.]+), maxForce=([\d.]+)").groups()
+    gripper = grab(r"self\.gripper_space = spaces\.Box\(low=([\d.]+), high=([\d.]+)").groups()
+    out = {"time_step": float(num) / float(den), "n_substeps": int(grab(r"self\.n_substeps = (\d+)").group(1)),
+           "distance_threshold": float(grab(r"self\.distance_threshold=([\d.]+)").group(1)),
+           "max_vel": float(grab(r"self\.max_vel = ([\d.]+)").group(1)),
+           "max_gripper_vel": float(grab(r"self\.max_gripper_vel = ([\d.]+)").group(1)),
+           "max_episode_steps": int(grab(r"self\._max_episode_steps = (\d+)").group(1)),
+           "gripper_low": float(gripper[0]), "gripper_high": float(gripper[1]),
+           "start_gripper_pos": [float(x) for x in grab(r"self\.startGripperPos = \[([^\]]+)\]").group(1).split(",")],
+           "obj_half": [lego / 2, float(half[0]), float(half[1])],
+           "obj_mass": float(grab(r"baseMass = ([\d.]+)").group(1)),
+           "finger_motor_force": float(grab(r"POSITION_CONTROL, new_gripper_pos, force=([\d.]+)").group(1)),
+           "gear_ratio": float(gear[0]), "gear_erp": float(gear[1]), "gear_max_force": float(gear[2]),
+           "finger_lateral_friction_grasp": float(grab(r"lateralFriction = (\d+)").group(1))}
+    out["pos_low"], out["pos_high"] = box("pos_space")
+    out["goal_low"], out["goal_high"] = box("goal_space", "")
+    out["obj_low"], out["obj_high"] = box("obj_space")
+    return out
+
+
+def model_reference():
+    """tests/golden/model_reference.json: the numbers of the reference's two arm URDFs and of its PickAndPlace scene that the
+    model tables restate, so that the tests compare against the reference without reading it"""
+    import json
+    envs = os.path.dirname(REF)
+    out = {"xarm7_pd_urdf": _urdf_table(os.path.join(envs, "urdf", "xarm7_pd.urdf")),
+           "xarm7_urdf": _urdf_table(os.path.join(envs, "urdf", "xarm7.urdf")),
+           "pick_and_place": _pnp_scene_constants(REF)}
+    with open(os.path.join(OUT, "model_reference.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote model_reference.json")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["model"]:
+        model_reference()
+        sys.exit(0)
     main()
     reach()
     handover()
     stack_tower()
+    model_reference()

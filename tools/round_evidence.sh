@@ -11,15 +11,17 @@ python -m pytest tests -m gpu -x -q > gpurun_out/gpu_suite_$TAG.log 2>&1 || { ta
 tail -3 gpurun_out/gpu_suite_$TAG.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/smoke_$TAG.log 2>&1; tail -1 gpurun_out/smoke_$TAG.log
 L=gpurun_out/${TAG}_bench_lines.jsonl
+ERR=${L%_lines.jsonl}.err
 : > $L
-python bench.py >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --envs-per-gpu 16384 --no-cpu-baseline --no-lazy --no-lockstep >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --envs-per-gpu 4096 --no-cpu-baseline --no-lazy --no-lockstep >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --workload reach >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --workload handover >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --workload stack >> $L 2>> gpurun_out/${TAG}_bench.err
-python bench.py --workload handover2 >> $L 2>> gpurun_out/${TAG}_bench.err
+# --full: the lines quoted in DESIGN.md 6 carry the extra legs (aged_state, lockstep_phase, lazy_reset) and the CPU baseline
+python bench.py --full >> $L 2>> $ERR
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline >> $L 2>> $ERR
+python bench.py --full --envs-per-gpu 16384 --no-cpu-baseline --no-lazy --no-lockstep >> $L 2>> $ERR
+python bench.py --full --envs-per-gpu 4096 --no-cpu-baseline --no-lazy --no-lockstep >> $L 2>> $ERR
+python bench.py --full --workload reach >> $L 2>> $ERR
+python bench.py --full --workload handover >> $L 2>> $ERR
+python bench.py --full --workload stack >> $L 2>> $ERR
+python bench.py --full --workload handover2 >> $L 2>> $ERR
 python - $L <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
