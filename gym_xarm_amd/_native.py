@@ -18,7 +18,9 @@ RESET_COOP_LIMIT_DEFAULT = STEP_COOP_LIMIT_DEFAULT = 8192   # include/xarm_hip.h
 
 EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step", "xarm_compute_reward",
            "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
-           "xarm_version"]
+           "xarm_version", "xarm_default_camera", "xarm_render"]
+RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
+RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
 
 
 class XarmConfig(C.Structure):
@@ -32,6 +34,13 @@ class XarmConfig(C.Structure):
 class XarmDims(C.Structure):
     _fields_ = [("obs_dim", C.c_int32), ("goal_dim", C.c_int32), ("act_dim", C.c_int32),
                 ("state_dim", C.c_int32), ("max_episode_steps", C.c_int32), ("n_substeps", C.c_int32)]
+
+
+class XarmCamera(C.Structure):
+    """include/xarm_hip.h xarm_camera (52 bytes)"""
+    _fields_ = [("target", C.c_float * 3), ("distance", C.c_float), ("yaw_deg", C.c_float), ("pitch_deg", C.c_float),
+                ("roll_deg", C.c_float), ("fov_deg", C.c_float), ("near_z", C.c_float), ("far_z", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32)]
 
 
 class XarmNativeError(RuntimeError):
@@ -73,6 +82,8 @@ def load(path=None):
     L.xarm_stage_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.xarm_debug_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     L.xarm_class_keys.argtypes = [vp, vp, vp]
+    L.xarm_default_camera.argtypes = [vp, C.POINTER(XarmCamera)]
+    L.xarm_render.argtypes = [vp, C.POINTER(XarmCamera), vp, C.c_int32, vp, vp, vp, vp]
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

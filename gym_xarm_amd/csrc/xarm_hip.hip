@@ -22,6 +22,7 @@
 #include <string.h>
 #include <new>
 #include "xarm_dev.h"
+#include "xarm_render_core.h"
 
 using namespace xd;
 
@@ -751,6 +752,29 @@ int xarm_pipeline_info(const xarm_handle *h, int32_t *fast_pipeline, int32_t *re
 #else
     *solver_iterations = xm::NUM_ITERATIONS;
 #endif
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------- rendering (xarm_k_render.hip)
+int xarm_default_camera(const xarm_handle *h, xarm_camera *out) {
+    if (!h || !out) return XARM_E_INVALID;
+    return xrc_render::rc_default_camera(h->cfg.env_kind, *out) == 0 ? XARM_OK : XARM_E_INVALID;
+}
+
+int xarm_render(xarm_handle *h, const xarm_camera *cam, const int32_t *env_ids_dev, int32_t n, uint32_t *rgba_dev, float *depth_dev,
+                uint8_t *seg_dev, void *stream) {
+    if (!h) return XARM_E_INVALID;
+    if (!cam) return fail(h, XARM_E_INVALID, "%s", "xarm_render: cam is NULL");
+    if (!rgba_dev) return fail(h, XARM_E_INVALID, "%s", "xarm_render: rgba_dev is NULL");
+    if (n < 1 || (int64_t)n > h->kp.num_envs) return fail(h, XARM_E_INVALID, "%s", "xarm_render: need 1 <= n <= num_envs");
+    xrc_render::RScene sc;
+    if (xrc_render::rc_scene_of(h->cfg.env_kind, h->cfg.num_obj, h->kp.hcfg.use_stand, sc) != 0)
+        return fail(h, XARM_E_INVALID, "%s", "xarm_render: unknown env kind");
+    xrc_render::RCam rc;
+    if (const char *why = xrc_render::rc_make_camera(*cam, rc)) return fail(h, XARM_E_INVALID, "xarm_render: %s", why);
+    DEVGUARD(h);
+    const int le = xrc_render::launch_render(h->kp.state, h->kp.stride, h->kp.num_envs, sc, rc, env_ids_dev, n, rgba_dev, depth_dev, seg_dev, stream);
+    if (le != 0) return fail(h, XARM_E_HIP, "xarm_render: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

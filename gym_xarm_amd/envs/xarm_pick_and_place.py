@@ -47,8 +47,10 @@ class XarmPickAndPlace:
     def seed(self, seed=None):
         return self._vec.seed(seed)
 
-    def render(self, mode="rgb_array", **kw):
-        return self._vec.render(mode)
+    def render(self, mode="rgb_array", width=None, height=None):
+        """env 0's image, a NumPy uint8 (H, W, 4) RGBA array (the reference's render(mode='rgb_array')); width / height default
+        to the env kind's camera (VecEnv.default_camera)"""
+        return self._vec.render(mode, width=width, height=height)[0].cpu().numpy()
 
     def close(self):
         self._vec.close()

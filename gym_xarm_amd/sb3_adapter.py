@@ -117,10 +117,15 @@ class SB3VecEnv:
         return [False] * len(self._indices(indices))
 
     def get_images(self):
-        raise NotImplementedError("rendering is outside the HIP hot path (SURVEY.md 2 #20)")
+        """RGB frames (H, W, 3) uint8 of the first min(E, 16) envs (one render call, the default camera)"""
+        n = min(self.num_envs, 16)
+        return list(_np(self.venv.render("rgb_array", env_ids=list(range(n)))[..., :3]))
 
-    def render(self, mode="human"):
-        raise NotImplementedError("rendering is outside the HIP hot path (SURVEY.md 2 #20)")
+    def render(self, mode="rgb_array"):
+        """env 0's RGB frame (H, W, 3) uint8; only 'rgb_array' (no window)"""
+        if mode != "rgb_array":
+            raise NotImplementedError("render mode %r: only 'rgb_array' (a window is outside the HIP hot path)" % (mode,))
+        return _np(self.venv.render("rgb_array")[0, ..., :3])
 
     @property
     def unwrapped(self):
@@ -237,6 +242,9 @@ class XarmHandoverNoGoal:
 
     def seed(self, seed=None):
         return self._env.seed(seed)
+
+    def render(self, mode="rgb_array", width=None, height=None):
+        return self._env.render(mode, width=width, height=height)
 
     def close(self):
         self._env.close()

@@ -258,8 +258,65 @@ class XarmPickAndPlaceVecEnv:
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False] * self.num_envs
 
-    def render(self, mode="rgb_array", **kw):
-        raise NotImplementedError("rendering is outside the HIP hot path (SURVEY.md 2 #20)")
+    # ------------------------------------------------------------------ rendering (include/xarm_hip.h xarm_render)
+    def default_camera(self):
+        """the env kind's default camera as a dict of include/xarm_hip.h xarm_camera fields"""
+        c = _native.XarmCamera()
+        _native.check(self._L, self._h, self._L.xarm_default_camera(self._h, C.byref(c)), "xarm_default_camera")
+        return {k: (list(getattr(c, k)) if k == "target" else getattr(c, k)) for k, _ in _native.XarmCamera._fields_}
+
+    def _camera(self, camera, width, height):
+        d = self.default_camera()
+        for k, v in (camera or {}).items():
+            if k not in d:
+                raise KeyError("unknown camera field %r (xarm_camera: %s)" % (k, ", ".join(d)))
+            d[k] = v
+        if width is not None:
+            d["width"] = int(width)
+        if height is not None:
+            d["height"] = int(height)
+        c = _native.XarmCamera()
+        for k, v in d.items():
+            if k == "target":
+                c.target[:] = [float(x) for x in v]
+            else:
+                setattr(c, k, v)
+        return c
+
+    def render_into(self, cam, ids, rgba, depth=None, seg=None):
+        """xarm_render into caller-owned buffers on the current stream (no allocation, no host sync: graph-capturable).
+        cam: an _native.XarmCamera; ids: int32 device tensor or None (= envs 0 .. rgba.shape[0]-1); rgba int32/uint8 device
+        memory of n * H * W dwords"""
+        n = rgba.shape[0]
+        rc = self._L.xarm_render(self._h, C.byref(cam), _ptr(ids), int(n), _ptr(rgba), _ptr(depth), _ptr(seg), self._stream())
+        _native.check(self._L, self._h, rc, "xarm_render")
+
+    def render(self, mode="rgb_array", width=None, height=None, env_ids=None, camera=None, depth=False, segmentation=False):
+        """Images of the envs env_ids (default [0]) as the last step / reset on the current stream left them: a device
+        torch.uint8 [n, H, W, 4] RGBA tensor (the reference's getCameraImage layout), or with depth / segmentation a dict
+        {'rgba', 'depth' (float32 [n, H, W], view-axis metres, far for the background), 'seg' (uint8 [n, H, W])}.
+        camera: dict of xarm_camera fields overriding default_camera(); width / height override its size.  With auto-reset
+        a finished env shows its new episode; with auto_reset='lazy' its terminal frame until its next step."""
+        if mode != "rgb_array":
+            raise NotImplementedError("render mode %r: only 'rgb_array' (a window is outside the HIP hot path)" % (mode,))
+        cam = self._camera(camera, width, height)
+        ids = torch.as_tensor([0] if env_ids is None else env_ids, dtype=torch.int32)
+        if ids.dim() != 1 or ids.numel() < 1:
+            raise ValueError("env_ids must be a non-empty 1-D sequence")
+        ids = ids.to(self.device)
+        n, H, W = ids.numel(), max(cam.height, 0), max(cam.width, 0)   # xarm_render refuses an empty image
+        rgba = torch.empty(n, H, W, 4, device=self.device, dtype=torch.uint8)
+        dep = torch.empty(n, H, W, device=self.device, dtype=torch.float32) if depth else None
+        seg = torch.empty(n, H, W, device=self.device, dtype=torch.uint8) if segmentation else None
+        self.render_into(cam, ids, rgba, dep, seg)
+        if not (depth or segmentation):
+            return rgba
+        out = {"rgba": rgba}
+        if depth:
+            out["depth"] = dep
+        if segmentation:
+            out["seg"] = seg
+        return out
 
     def timing_enable(self, on=True):
         _native.check(self._L, self._h, self._L.xarm_timing_enable(self._h, int(on)), "xarm_timing_enable")

@@ -213,6 +213,31 @@ int xarm_debug_counts(xarm_handle *h, int32_t *finished, int32_t *handed_off, vo
  * this call fails with XARM_E_INVALID).  Introspection only - nothing in the reference corresponds to it. */
 int xarm_class_keys(xarm_handle *h, uint8_t *keys_dev, void *stream);
 
+/* ---- batched on-device rendering (gym_xarm_amd/csrc/xarm_render_core.h, xarm_k_render.hip).
+ * Camera: PyBullet's computeViewMatrixFromYawPitchRoll (upAxisIndex 2) + computeProjectionMatrixFOV (vertical fov, aspect
+ * width / height) restated in closed form; one ray through each pixel centre, row 0 = the top of the image.  The scene is
+ * drawn from primitives (render_scene.json), not the reference's meshes: pixel parity with PyBullet is UNPINNED. */
+#define XARM_RENDER_SHADOWS 1      /* xarm_camera.flags: one shadow ray per lit pixel */
+#define XARM_RENDER_MAX_DIM 2048   /* width, height <= this */
+typedef struct xarm_camera {
+    float target[3], distance, yaw_deg, pitch_deg, roll_deg, fov_deg, near_z, far_z;
+    int32_t width, height, flags;          /* XARM_RENDER_SHADOWS */
+} xarm_camera;                             /* 52 bytes */
+/* the env kind's default camera: PickAndPlace and Handover the reference's render() cameras, Reach / StackTower build-defined */
+int xarm_default_camera(const xarm_handle *h, xarm_camera *out);
+/* render the n envs env_ids_dev[0 .. n) (int32 device array; NULL = envs 0 .. n-1) into rgba_dev (uint32 [n, height, width],
+ * bytes R G B A, alpha 255), and, when not NULL, depth_dev (float32 [n, height, width]: view-axis eye-space distance in
+ * metres, far_z for the background - NOT PyBullet's nonlinear z-buffer) and seg_dev (uint8 [n, height, width]: 0 background,
+ * 1 table / ground / stand, 2 / 3 arm 0 links / gripper, 4 / 5 arm 1 links / gripper, 8 + k object k, 16 + k goal marker k).
+ * Stream-ordered, never synchronises the host, reads the state the last xarm_step / xarm_reset on the stream left and writes
+ * none of it; one kernel launch, no workspace (safe inside graph capture).  With auto_reset an env that finished in the last
+ * step shows its NEW episode; with XARM_AUTO_RESET_LAZY it shows its terminal frame until its next xarm_step.  An env id
+ * outside [0, num_envs) renders an all-zero image (rgba 0, depth 0) with segmentation 255.  XARM_E_INVALID: cam or rgba_dev
+ * NULL, width / height outside [1, XARM_RENDER_MAX_DIM], n < 1 or n > num_envs, fov_deg outside (0, 180), not
+ * 0 < near_z < far_z, distance <= 0, unknown flags. */
+int xarm_render(xarm_handle *h, const xarm_camera *cam, const int32_t *env_ids_dev /* NULL = 0..n-1 */, int32_t n,
+                uint32_t *rgba_dev, float *depth_dev /* may be NULL */, uint8_t *seg_dev /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
