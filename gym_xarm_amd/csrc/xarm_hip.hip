@@ -1,6 +1,12 @@
 // xarm_hip.hip - the C ABI (include/xarm_hip.h) of the batched Xarm environments: handles, kernel selection, launches.
 // The gfx950 kernels live in xarm_k_*.hip, one translation unit per kernel family (prototypes: xarm_dev.h).
 //
+// What an environment kind is stands in ONE place, its KindOps entry (KIND_PNP .. KIND_REARRANGE below): dimensions, lanes per
+// env, default limits and the init / reset / step / reward launches.  xarm_create validates the config, picks the entry and
+// resolves the limits; every other entry point reads a field of h->ops or calls through it.  The caller's buffers travel as a
+// StepIO and become kernel arguments in launch_step alone; the fast-step pipelines of PickAndPlace and Handover share one
+// fork / join skeleton (pipelined_step); the slots of the device counter block are the CNT_* constants.
+//
 // PickAndPlace launches (xarm_k_pnp.hip, xarm_k_pnp_coop.hip; cores: xarm_core.h, xarm_coop_core.h):
 //   k_step        one thread per environment, one 64-lane wavefront per workgroup.  The fused step keeps an env's whole
 //                 working set on chip for all 15 substeps x 50 solver sweeps: ~450 VGPRs of per-env state / solver blocks
@@ -26,39 +32,38 @@
 
 using namespace xd;
 
+struct KindOps;
 
 // ------------------------------------------------------------------------------------- C ABI
 struct xarm_handle {
     xarm_config cfg;
+    const KindOps *ops;  // the env kind's table entry, picked once by xarm_create
     KParams kp;
-    int *done_list;   // [E]
-    int *counters;    // [3 + 2 * NCLS], zeroed by ONE memset at the start of every step call (no host-side state: a captured
-                      // step can be replayed): done_count = +0, eject_count = +1 (2), class_hist = +3
-    int *done_count;  // [1] episodes that ended in this call (list A)
+    int *done_list;   // [E] episodes that ended in this call (list A)
+    int *counters;    // [CNT_INTS], slots CNT_*: the leading step_counter_ints() zeroed by ONE memset at the start of every step
+                      // call (no host-side state: a captured step can be replayed)
     int *mask_count;  // [1]
-    int coop_step_limit; // PickAndPlace: batches of at most this many envs step on k_step_coop
+    int coop_step_limit; // PickAndPlace, Reach, Handover (one stick): batches of at most this many envs step on the cooperative kernel
     int fast_pipeline;   // PickAndPlace, larger batches: k_step_fast + hand-off of the envs with finger-pad rows (1) or k_step (0)
-    int *eject_list;     // [E] envs handed off by k_step_fast
-    int *eject_count;    // [2]: hand-off count, count of episodes that ended in the hand-off kernels
+    int *eject_list;     // [stages][E] envs handed off by the fast kernel, one list per stage
     // the two reset launches of a pipelined step (xarm_step): episodes that ended in k_step_fast are reset on `side`
     // while the hand-off still runs on the caller's stream, the few that end in the hand-off after it
     int *done_list_b;    // [E] episodes that ended in the hand-off kernels
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
-    int reset_overlap;
-    // staged Handover step (xarm_step): the fast lane-pair kernel runs the step's 15 ticks in ho_stages launches; the envs a stage
-    // hands off re-run only the ticks from that stage's first one on the cooperative rows, on a side stream beside the next stage
+    int reset_overlap;   // PickAndPlace pipeline with auto-reset only (xarm_create)
+    // staged step (pipelined_step): the fast kernel runs the step's 15 ticks in ho_stages launches; the envs a stage hands off
+    // re-run only the ticks from that stage's first one on the cooperative rows, on a side stream beside the next stage
     static constexpr int MAX_ST = XARM_HO_MAX_STAGES;
-    int ho_stages;        // 1 = one fast launch, one hand-off (round 4's first pipeline)
+    int ho_stages;        // 1 = one fast launch, one hand-off
     int ho_tick[MAX_ST + 1]; // stage c runs the ticks [ho_tick[c], ho_tick[c + 1])
     float *ho_qt;         // [18][stride] joint targets of the step the first stage opened
     uint8_t *ho_flag;     // [stride] handed off in an earlier stage of this call
     hipStream_t st_side[MAX_ST];
     hipEvent_t st_fork[MAX_ST], st_join[MAX_ST];
     int ho_force_coupled; // test hook (XARM_HO_FORCE_COUPLED=1): every substep of the cooperative Handover step through the coupled sweep
-    // StackTower: class-homogeneous wavefronts (xarm_stack_core.h class_layout); null when XARM_ST_CLASS_ORDER=0
+    // StackTower / Rearrange: class-homogeneous wavefronts (xarm_stack_core.h class_layout); null when XARM_*_CLASS_ORDER=0
     uint8_t *class_key;  // [E] row-set class of each env's last substep
-    int *class_hist;     // [2 * NCLS] histogram, then the per-class arrival counters
     int *class_order;    // [E] slot -> env
     char err[512];
     // timing
@@ -70,6 +75,17 @@ struct xarm_handle {
     int64_t ev_launches;
     bool ev_created;
 };
+
+// The device counter block.  The class histogram (2 * ncls ints: histogram, then the per-class arrival counters) and the
+// hand-off counts of the stages >= 1 SHARE the region from CNT_REGION on: no kind has both a class order and a pipeline.
+enum { CNT_DONE = 0,      // episodes that ended in this call (list A)
+       CNT_EJECT = 1,     // envs handed off by the first fast stage
+       CNT_DONE_B = 2,    // episodes that ended in the hand-off kernels (list B)
+       CNT_REGION = 3 };
+static constexpr int cnt_stage(int c) { return c == 0 ? (int)CNT_EJECT : CNT_REGION + c; }   // hand-off count of stage c
+constexpr int CNT_STAGE_INTS = cnt_stage(xarm_handle::MAX_ST) + 1;   // what a staged step clears and xarm_debug_counts reads
+constexpr int CNT_INTS = CNT_REGION + 2 * xra::NCLS;                 // the allocation
+static_assert(xra::NCLS >= xs::NCLS && CNT_STAGE_INTS <= CNT_INTS, "one counter block serves both class orders and the stage counters");
 
 static char g_err[512] = "";
 
@@ -84,61 +100,266 @@ static int fail(xarm_handle *h, int code, const char *fmt, const char *detail) {
         if (_e != hipSuccess) return fail(h, XARM_E_HIP, #call ": %s", hipGetErrorString(_e)); \
     } while (0)
 
+// ------------------------------------------------------------------------------------- launches
+// the eight caller buffers of xarm_step; expanded into kernel arguments in launch_step only (the kernels keep their
+// __restrict__ pointer parameters)
+struct StepIO {
+    const float *actions;
+    float *obs, *ag, *dg, *reward;
+    uint8_t *done, *success;
+    float *terminal_obs;
+};
+// every step kernel: (KParams, the eight buffers, then what the family adds - done list and count, hand-off list, stage ...)
+template <typename... KA, typename... A>
+static void launch_step(void (*k)(KParams, const float *, float *, float *, float *, float *, uint8_t *, uint8_t *, float *, KA...), unsigned grid,
+                        hipStream_t st, const xarm_handle *h, const StepIO &io, A... tail) {
+    k<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, io.actions, io.obs, io.ag, io.dg, io.reward, io.done, io.success, io.terminal_obs, tail...);
+}
+// the Handover kernels are templates over the scene; the cooperative ones also over the test hook FORCE_COUPLED
+#define HO_KERNEL(h, K) ((h)->kp.hcfg.use_stand ? K<xh::HandoverStandScene> : K<xh::HandoverScene>)
+#define HO_COOP_KERNEL(h, K) \
+    ((h)->kp.hcfg.use_stand ? K<xh::HandoverStandScene, false> : ((h)->ho_force_coupled ? K<xh::HandoverScene, true> : K<xh::HandoverScene, false>))
+
+struct KindOps {
+    xarm_dims_t dims;
+    int steps_field;         // state row of the episode's step counter
+    int lanes;               // lanes per env: the grid of a whole-batch launch is lanes * stride / WG
+    int reset_coop_default, step_coop_default;   // cooperative reset / step kernels: default limits (0: the kind has none)
+    int stages_default;      // fast-step pipeline: default stage count and the variable that overrides it (null: no pipeline)
+    const char *stages_env;
+    int unstaged_ticks;      // what xarm_stage_info reports as the one stage of an unstaged step (0: nothing)
+    int ncls;                // class order: classes and the variable that switches it off (0, null: none)
+    const char *class_env;
+    void (*init)(xarm_handle *h);
+    // reset of the envs in list[0 .. *count) (null: all)
+    void (*reset)(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st);
+    int (*step)(xarm_handle *h, const StepIO &io, hipStream_t st);
+    void (*reward)(xarm_handle *h, const float *ag, const float *g, int64_t n, float *out, hipStream_t st);
+    int fixed_reward_type;   // the reward type that cannot be relabelled and xarm_compute_reward's message for it (null: none)
+    const char *fixed_reward_msg;
+};
+
+static int *slot(const xarm_handle *h, int s) { return h->counters + s; }
+static unsigned env_grid(const xarm_handle *h) { return (unsigned)(h->ops->lanes * h->kp.stride / WG); }
+static bool small_batch(const xarm_handle *h) { return h->kp.num_envs <= (int64_t)h->coop_step_limit; }   // steps on the cooperative kernel
+static int64_t capped(const xarm_handle *h, int limit) { return h->kp.num_envs < (int64_t)limit ? h->kp.num_envs : (int64_t)limit; }
+// grid of a cooperative PickAndPlace / Reach launch over at most `cap` envs: four envs per wavefront
+static unsigned coop_grid(int64_t cap) { return (unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS); }
 // grid of a cooperative Handover launch over at most `cap` envs: two envs per wavefront, grid stride beyond 2 048 workgroups
 static unsigned ho_coop_grid(int64_t cap) {
     const int64_t g = (cap + xhc::ROW_ENVS - 1) / xhc::ROW_ENVS;
     return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
-// XarmHandover.step of the envs list[0 .. *count) (null: all) on the cooperative rows, from tick stage.tick0 on
-static void launch_ho_coop_step(xarm_handle *h, unsigned g_, const float *actions_dev, float *obs_dev, float *ag_dev, float *dg_dev, float *reward_dev,
-                                uint8_t *done_dev, uint8_t *success_dev, float *terminal_obs_dev, int *done_list, int *done_count,
-                                const int *list, const int *count, HoStage stage, hipStream_t st) {
-    if (h->kp.hcfg.use_stand) k_ho_step_coop_list<xh::HandoverStandScene, false><<<dim3(g_), dim3(WG), 0, st>>>(
-        h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, done_list, done_count, list, count, stage);
-    else if (h->ho_force_coupled) k_ho_step_coop_list<xh::HandoverScene, true><<<dim3(g_), dim3(WG), 0, st>>>(
-        h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, done_list, done_count, list, count, stage);
-    else k_ho_step_coop_list<xh::HandoverScene, false><<<dim3(g_), dim3(WG), 0, st>>>(
-        h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, done_list, done_count, list, count, stage);
+
+template <auto K> static void init_with(xarm_handle *h) { K<<<dim3(env_grid(h)), dim3(WG)>>>(h->kp); }
+
+using ResetKernel = void (*)(KParams, const int *, const int *, float *, float *, float *);
+// the cooperative kernel takes counts up to kp.coop_limit, the one-env-per-lane (Handover: lane-pair) kernel the rest; both
+// are launched, the one out of its range exits at once (the count lives on the device)
+static void split_reset(xarm_handle *h, ResetKernel coop, unsigned (*cgrid)(int64_t), ResetKernel lane, const int *list, const int *count,
+                        float *obs, float *ag, float *dg, hipStream_t st) {
+    const int64_t cap = capped(h, h->kp.coop_limit);
+    if (cap > 0) coop<<<dim3(cgrid(cap)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
+    if (h->kp.num_envs > cap) lane<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
 }
-// Handover reset of the envs in list[0 .. *count) (null: all): the cooperative rows take counts up to kp.coop_limit, the lane-pair
-// kernel the rest; both are launched, the one out of its range exits at once (the count lives on the device)
-static void launch_ho_reset(xarm_handle *h, unsigned grid2, const int *list, const int *count, float *obs_dev, float *ag_dev, float *dg_dev,
-                            hipStream_t st) {
-    if (h->cfg.num_obj == 2) {
-        if (h->kp.hcfg.use_stand) k_ho2_reset<xh::HandoverStandScene><<<dim3(grid2), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-        else k_ho2_reset<xh::HandoverScene><<<dim3(grid2), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-        return;
-    }
-    const int64_t cap = h->kp.num_envs < (int64_t)h->kp.coop_limit ? h->kp.num_envs : (int64_t)h->kp.coop_limit;
-    if (cap > 0) {
-        if (h->kp.hcfg.use_stand) k_ho_reset_coop<xh::HandoverStandScene, false><<<dim3(ho_coop_grid(cap)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-        else if (h->ho_force_coupled) k_ho_reset_coop<xh::HandoverScene, true><<<dim3(ho_coop_grid(cap)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-        else k_ho_reset_coop<xh::HandoverScene, false><<<dim3(ho_coop_grid(cap)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-    }
-    if (h->kp.num_envs > cap) {
-        if (h->kp.hcfg.use_stand) k_ho_reset<xh::HandoverStandScene><<<dim3(grid2), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-        else k_ho_reset<xh::HandoverScene><<<dim3(grid2), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-    }
+static void pnp_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
+    split_reset(h, k_reset_coop, coop_grid, k_reset, list, count, obs, ag, dg, st);
+}
+static void reach_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
+    split_reset(h, k_reach_reset_coop, coop_grid, k_reach_reset, list, count, obs, ag, dg, st);
+}
+static void ho_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
+    split_reset(h, HO_COOP_KERNEL(h, k_ho_reset_coop), ho_coop_grid, HO_KERNEL(h, k_ho_reset), list, count, obs, ag, dg, st);
+}
+static void ho2_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
+    HO_KERNEL(h, k_ho2_reset)<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
+}
+template <auto K>   // StackTower, Rearrange: the reset also writes the env's class key
+static void keyed_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
+    K<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg, h->class_key);
 }
 
-static void launch_reach_reset(xarm_handle *h, const int *list, const int *count, float *obs_dev, float *ag_dev, float *dg_dev, hipStream_t st) {
-    const int64_t cap = h->kp.num_envs < (int64_t)h->kp.coop_limit ? h->kp.num_envs : (int64_t)h->kp.coop_limit;
-    if (cap > 0)
-        k_reach_reset_coop<<<dim3((unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-    if (h->kp.num_envs > cap)
-        k_reach_reset<<<dim3((unsigned)(h->kp.stride / WG)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
+template <auto K> static void typed_reward(xarm_handle *h, const float *ag, const float *g, int64_t n, float *out, hipStream_t st) {
+    K<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->cfg.reward_type, ag, g, n, out);
+}
+template <auto K> static void sparse_reward(xarm_handle *h, const float *ag, const float *g, int64_t n, float *out, hipStream_t st) {
+    K<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(ag, g, n, out);
 }
 
-// PickAndPlace reset of the envs in list[0 .. *count) (null: all): the cooperative kernel takes counts up to
-// kp.coop_limit, the one-env-per-lane kernel the rest; both are launched, the one out of its range exits at once.
-static void launch_pnp_reset(xarm_handle *h, const int *list, const int *count, float *obs_dev, float *ag_dev, float *dg_dev,
-                             hipStream_t st) {
-    const int64_t cap = h->kp.num_envs < (int64_t)h->kp.coop_limit ? h->kp.num_envs : (int64_t)h->kp.coop_limit;
-    if (cap > 0)
-        k_reset_coop<<<dim3((unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
-    if (h->kp.num_envs > cap)
-        k_reset<<<dim3((unsigned)(h->kp.stride / WG)), dim3(WG), 0, st>>>(h->kp, list, count, obs_dev, ag_dev, dg_dev);
+// The fast-step pipeline of PickAndPlace and Handover: every env on the pad-free fast step; the ones with an active finger-pad
+// row are handed off, untouched, to the cooperative kernel (lists of at most eject_coop_cap envs) or to the one-env-per-lane
+// kernel (longer lists) - both launched, the one out of its range exits at once (the count lives on the device).
+// STAGED (ho_stages > 1): the fast kernel runs the 15 ticks in ho_stages launches.  An env whose pads come alive in stage c keeps
+// the state it had before that stage and re-runs the ticks from the stage's first one in the hand-off kernels - on a side stream,
+// beside the next fast stage (16 384 Handover envs are 512 of the 1 024 SIMDs); only the last stage's hand-off, a third of a step
+// long, is on the critical path: Handover's fast 0.73 + hand-off 0.69 ms became 0.77 + 0.27.
+//   fast        launches fast stage c on the caller's stream
+//   handoff     launches the hand-off of stage c on hs
+//   after_fast  hook, after the last fast stage and before its hand-off (null: none)
+static int pipelined_step(xarm_handle *h, const StepIO &io, hipStream_t st,
+                          void (*fast)(xarm_handle *, const StepIO &, int *elist, int *ecnt, HoStage, hipStream_t),
+                          void (*handoff)(xarm_handle *, const StepIO &, int *elist, int *ecnt, HoStage rest, hipStream_t hs),
+                          int (*after_fast)(xarm_handle *, const StepIO &, hipStream_t)) {
+    static_assert(xm::HO_N_TICKS == xm::PNP_N_SUBSTEPS, "one stage table for both");
+    const int nst = h->ho_stages;
+    for (int c = 0; c < nst; c++) {
+        const HoStage sg{h->ho_tick[c], h->ho_tick[c + 1], h->ho_qt, h->ho_flag};
+        int *elist = h->eject_list + (int64_t)c * h->kp.stride, *ecnt = slot(h, cnt_stage(c));
+        fast(h, io, elist, ecnt, sg, st);
+        hipStream_t hs = st;
+        if (c + 1 < nst) {
+            hs = h->st_side[c];
+            HIPCHK(h, hipEventRecord(h->st_fork[c], st));
+            HIPCHK(h, hipStreamWaitEvent(hs, h->st_fork[c], 0));
+        } else if (after_fast) {
+            const int rc = after_fast(h, io, st);
+            if (rc != XARM_OK) return rc;
+        }
+        // one done list for every kernel of the call (atomic appends), the reset after the last hand-off
+        const HoStage rest{sg.tick0, xm::HO_N_TICKS, h->ho_qt, h->ho_flag};
+        handoff(h, io, elist, ecnt, rest, hs);
+        if (c + 1 < nst) HIPCHK(h, hipEventRecord(h->st_join[c], hs));
+    }
+    for (int c = 0; c + 1 < nst; c++) HIPCHK(h, hipStreamWaitEvent(st, h->st_join[c], 0));
+    return XARM_OK;
 }
+
+// PickAndPlace.  The unstaged pipeline (XARM_PNP_STAGES=1) is the one-stage case with kernels of its own.
+static void pnp_fast(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage sg, hipStream_t st) {
+    if (h->ho_stages > 1) launch_step(k_step_fast_stage, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, sg);
+    else launch_step(k_step_fast, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt);
+}
+// With the reset overlap the episodes that end in the hand-off go to a list of their own (done_list_b): the reset of the ~98 %
+// that ended on the fast path need not wait for it.  Without the side stream (XARM_RESET_OVERLAP=0): one list, one reset after
+// the hand-off.
+static void pnp_handoff(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
+    int *list_b = h->reset_overlap ? h->done_list_b : h->done_list, *cnt_b = slot(h, h->reset_overlap ? CNT_DONE_B : CNT_DONE);
+    const int64_t cap = capped(h, h->kp.eject_coop_cap);
+    const unsigned cgrid = coop_grid(cap) < 1024u ? coop_grid(cap) : 1024u;
+    if (h->ho_stages > 1) {
+        launch_step(k_step_coop_list_stage, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt, rest);
+        if (h->kp.num_envs > cap) launch_step(k_step_from_stage, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt, rest);
+    } else {
+        launch_step(k_step_coop_list, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt);
+        if (h->kp.num_envs > cap) launch_step(k_step, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt);
+    }
+}
+// a reset is six sequential ticks of latency on a few hundred wavefronts (2.9 ms), the hand-off 0.55 ms on a few hundred
+// others: started after the last fast stage on the side stream, the first reset overlaps the hand-off.  The call still waits
+// for the second one - a few dozen envs, but the ones with a finger contact, whose reset carries the pad rows through the
+// homing ticks (worth 0.16 ms per call at 16 384 envs, nothing at 65 536)
+static int pnp_overlapped_reset(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    if (!h->reset_overlap) return XARM_OK;
+    HIPCHK(h, hipEventRecord(h->ev_fork, st));
+    HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
+    pnp_reset(h, h->done_list, slot(h, CNT_DONE), io.obs, io.ag, io.dg, h->side);
+    HIPCHK(h, hipEventRecord(h->ev_join, h->side));
+    return XARM_OK;
+}
+static int pnp_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    if (small_batch(h)) launch_step(k_step_coop, coop_grid(h->kp.num_envs), st, h, io, h->done_list, slot(h, CNT_DONE));
+    else if (h->fast_pipeline) return pipelined_step(h, io, st, pnp_fast, pnp_handoff, pnp_overlapped_reset);
+    else launch_step(k_step, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), nullptr, nullptr);
+    return XARM_OK;
+}
+
+static int reach_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    if (small_batch(h)) launch_step(k_reach_step_coop, coop_grid(h->kp.num_envs), st, h, io, h->done_list, slot(h, CNT_DONE));
+    else launch_step(k_reach_step, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE));
+    return XARM_OK;
+}
+
+// Handover with one stick.  Its reset is not overlapped: six single-substep ticks, 0.28 ms whether it runs beside the hand-off
+// or after it, and the two launches slow each other down when they overlap - 1.78 against 1.76 ms per call
+static void ho_fast(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage sg, hipStream_t st) {
+    launch_step(HO_KERNEL(h, k_ho_step_fast), env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, sg);
+}
+static void ho_handoff(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
+    const int64_t cap = capped(h, h->kp.eject_coop_cap);
+    launch_step(HO_COOP_KERNEL(h, k_ho_step_coop_list), ho_coop_grid(cap), hs, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, rest);
+    if (h->kp.num_envs > cap) launch_step(HO_KERNEL(h, k_ho_step), env_grid(h), hs, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, rest);
+}
+static int ho_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    const HoStage whole{0, xm::HO_N_TICKS, nullptr, nullptr};   // an unstaged step
+    // small batch: every env on the cooperative rows, one launch (list == null: all envs; finished episodes -> done_list)
+    if (small_batch(h)) launch_step(HO_COOP_KERNEL(h, k_ho_step_coop_list), ho_coop_grid(h->kp.num_envs), st, h, io, h->done_list, slot(h, CNT_DONE),
+                                    nullptr, nullptr, whole);
+    else if (h->fast_pipeline) return pipelined_step(h, io, st, ho_fast, ho_handoff, nullptr);
+    else launch_step(HO_KERNEL(h, k_ho_step), env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), nullptr, nullptr, whole);
+    return XARM_OK;
+}
+static int ho2_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    launch_step(HO_KERNEL(h, k_ho2_step), env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE));
+    return XARM_OK;
+}
+
+// StackTower, Rearrange: with the class order, a histogram of the envs' class keys and their placement into class-homogeneous
+// wavefronts (class_order) come before the step
+template <auto HIST, auto PLACE, auto STEP>
+static int class_ordered_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
+    if (h->class_key) {
+        const unsigned cg = (unsigned)((h->kp.num_envs + 255) / 256);
+        int *hist = slot(h, CNT_REGION);
+        HIST<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, hist);
+        PLACE<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, hist, hist + h->ops->ncls, h->class_order, WG / 2);
+    }
+    launch_step(STEP, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), h->class_order, h->class_key);
+    return XARM_OK;
+}
+
+static const char NO_RELABEL_CONTACT[] = "xarm_compute_reward: reward_type 'dense' depends on the contact state and cannot be relabelled";
+static const char NO_RELABEL_DIFF[] = "xarm_compute_reward: reward_type 'dense_diff' is stateful (d_old) and cannot be relabelled";
+static const char NO_RELABEL_GRASP[] = "xarm_compute_reward: reward_type 'dense' depends on the grasp flags and gripper positions and cannot be relabelled";
+
+//  dims: obs, goal, act, state, max_episode_steps, n_substeps | steps field, lanes | reset, step limit defaults | stages | ticks | classes
+//  init, reset, step, reward | reward type that cannot be relabelled
+static const KindOps KIND_PNP = {
+    {xk::OBS_DIM, xk::GOAL_DIM, xk::ACT_DIM, xk::STATE_DIM, xm::PNP_MAX_EPISODE_STEPS, xm::PNP_N_SUBSTEPS}, xk::S_STEPS, 1,
+    XARM_RESET_COOP_LIMIT_DEFAULT, XARM_STEP_COOP_LIMIT_DEFAULT, XARM_PNP_STAGES_DEFAULT, "XARM_PNP_STAGES", xm::PNP_N_SUBSTEPS, 0, nullptr,
+    init_with<k_init>, pnp_reset, pnp_step, typed_reward<k_compute_reward>, XARM_REWARD_DENSE, NO_RELABEL_CONTACT};
+static const KindOps KIND_REACH = {
+    {xr::OBS_DIM, xk::GOAL_DIM, xk::ACT_DIM, xr::STATE_DIM, xmr::MAX_EPISODE_STEPS, xmr::N_SUBSTEPS}, xr::R_STEPS, 1,
+    XARM_RESET_COOP_LIMIT_DEFAULT, XARM_STEP_COOP_LIMIT_DEFAULT, 0, nullptr, 0, 0, nullptr,
+    init_with<k_reach_init>, reach_reset, reach_step, typed_reward<k_reach_compute_reward>, XARM_REACH_REWARD_DENSE_DIFF, NO_RELABEL_DIFF};
+static const KindOps KIND_HANDOVER1 = {
+    {xh::OBS_DIM, xk::GOAL_DIM, xh::ACT_DIM, xh::STATE_DIM, xm::HO_MAX_EPISODE_STEPS, xm::HO_N_TICKS}, xh::H_STEPS, 2,
+    XARM_HO_RESET_COOP_LIMIT_DEFAULT, XARM_HO_STEP_COOP_LIMIT_DEFAULT, XARM_HO_STAGES_DEFAULT, "XARM_HO_STAGES", xm::HO_N_TICKS, 0, nullptr,
+    init_with<k_ho_init>, ho_reset, ho_step, sparse_reward<k_ho_compute_reward>, XARM_REWARD_DENSE, NO_RELABEL_GRASP};
+static const KindOps KIND_HANDOVER2 = {
+    {xh2::OBS_DIM, xh2::GOAL_DIM, xh::ACT_DIM, xh2::STATE_DIM, xm::HO_MAX_EPISODE_STEPS, xm::HO_N_TICKS}, xh2::G_STEPS, 2,
+    0, 0, 0, nullptr, xm::HO_N_TICKS, 0, nullptr,
+    init_with<k_ho2_init>, ho2_reset, ho2_step, sparse_reward<k_ho2_compute_reward>, XARM_REWARD_DENSE, NO_RELABEL_GRASP};
+static const KindOps KIND_STACK = {
+    {xs::OBS_DIM, xs::GOAL_DIM, xs::ACT_DIM, xs::STATE_DIM, xm::ST_MAX_EPISODE_STEPS, xm::ST_N_SUBSTEPS}, xs::K_STEPS, 2,
+    0, 0, 0, nullptr, 0, xs::NCLS, "XARM_ST_CLASS_ORDER",
+    init_with<k_st_init>, keyed_reset<k_st_reset>, class_ordered_step<k_class_hist, k_class_place, k_st_step>, typed_reward<k_st_compute_reward>, -1, nullptr};
+static const KindOps KIND_REARRANGE = {
+    {xra::OBS_DIM, xra::GOAL_DIM, xra::ACT_DIM, xra::STATE_DIM, xm::RA_MAX_EPISODE_STEPS, xm::ST_N_SUBSTEPS}, xra::K_STEPS, 2,
+    0, 0, 0, nullptr, 0, xra::NCLS, "XARM_RA_CLASS_ORDER",
+    init_with<k_ra_init>, keyed_reset<k_ra_reset>, class_ordered_step<k_ra_class_hist, k_ra_class_place, k_ra_step>, typed_reward<k_ra_compute_reward>, -1, nullptr};
+
+// how many ints of the counter block a step call of this handle clears
+static int step_counter_ints(const xarm_handle *h) {
+    if (h->class_key) return CNT_REGION + 2 * h->ops->ncls;
+    if (!h->fast_pipeline) return CNT_DONE + 1;
+    return h->ho_stages > 1 ? CNT_STAGE_INTS : (int)CNT_REGION;
+}
+
+// integer value of an environment variable that is set and not empty
+static bool env_int(const char *name, int *value) {
+    const char *ev = getenv(name);
+    if (!ev || !*ev) return false;
+    *value = atoi(ev);
+    return true;
+}
+// a cooperative-kernel limit: an explicit xarm_config value wins (< 0 = never = 0); the environment variable replaces the
+// DEFAULT only, and a non-positive value of it means 0
+static int resolve_limit(int cfg_value, int dflt, const char *env_name) {
+    int v;
+    if (cfg_value != 0) return cfg_value > 0 ? cfg_value : 0;
+    return env_int(env_name, &v) ? (v > 0 ? v : 0) : dflt;
+}
+static int clamp_stages(int n) { return n < 1 ? 1 : (n > xarm_handle::MAX_ST ? xarm_handle::MAX_ST : n); }
 
 // The handle's kernels, events and buffers live on cfg.device.  Every entry point makes that device current for its
 // own duration and restores the caller's (torch's) current device on return, so a handle can be created and used
@@ -180,9 +401,17 @@ const char *xarm_last_error(const xarm_handle *h) { return h ? h->err : g_err; }
 
 int xarm_create(const xarm_config *cfg, xarm_handle **out) {
     if (!cfg || !out) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: null argument");
+    const KindOps *ops;
+    switch (cfg->env_kind) {
+    case XARM_ENV_PICK_AND_PLACE: ops = &KIND_PNP; break;
+    case XARM_ENV_REACH: ops = &KIND_REACH; break;
+    case XARM_ENV_HANDOVER: ops = cfg->num_obj == 2 ? &KIND_HANDOVER2 : &KIND_HANDOVER1; break;
+    case XARM_ENV_STACK_TOWER: ops = &KIND_STACK; break;
+    case XARM_ENV_REARRANGE: ops = &KIND_REARRANGE; break;
+    default: return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: unsupported env_kind");
+    }
     const bool reach = cfg->env_kind == XARM_ENV_REACH, handover = cfg->env_kind == XARM_ENV_HANDOVER, stack = cfg->env_kind == XARM_ENV_STACK_TOWER;
     const bool rearrange = cfg->env_kind == XARM_ENV_REARRANGE;
-    if (cfg->env_kind != XARM_ENV_PICK_AND_PLACE && !reach && !handover && !stack && !rearrange) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: unsupported env_kind");
     if (stack && cfg->num_obj != 3) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: XarmStackTower has num_obj == 3 (xarm_stack_tower.py:19)");
     if (stack && cfg->reward_type > 1) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: XarmStackTower reward_type is 0 (sparse) or 1 (-d)");
     if (rearrange && cfg->num_obj != 4) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: XarmRearrange has num_obj == 4 (xarm_rearrange.py:20)");
@@ -210,6 +439,7 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
     if (!h) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_create: out of host memory");
     memset(h, 0, sizeof *h);
     h->cfg = *cfg;
+    h->ops = ops;
     const int64_t E = cfg->num_envs, stride = (E + WG - 1) / WG * WG;
     h->kp.stride = stride;
     h->kp.num_envs = E;
@@ -220,78 +450,44 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
     h->kp.cfg.goal_shape = cfg->goal_shape;
     h->kp.cfg.reward_type = cfg->reward_type;
     h->kp.auto_reset = cfg->auto_reset;
-    // cooperative reset kernel (PickAndPlace): default cross-over measured on MI355X; 0 disables it
-    h->kp.coop_limit = 0;
-    if (cfg->env_kind == XARM_ENV_PICK_AND_PLACE || cfg->env_kind == XARM_ENV_REACH) {
-        h->kp.coop_limit = cfg->reset_coop_limit > 0 ? cfg->reset_coop_limit : (cfg->reset_coop_limit < 0 ? 0 : XARM_RESET_COOP_LIMIT_DEFAULT);
-        // the environment variable replaces the DEFAULT only: an explicit xarm_config value (incl. "< 0 = never") wins
-        const char *ev = getenv("XARM_RESET_COOP_LIMIT");
-        if (ev && *ev && cfg->reset_coop_limit == 0) h->kp.coop_limit = atoi(ev) > 0 ? atoi(ev) : 0;
-    }
-    // cooperative step kernel: pays while the one-env-per-lane launch would leave SIMDs empty (measured cross-over,
-    // DESIGN.md 5); XARM_STEP_COOP_LIMIT overrides, 0 disables
-    h->coop_step_limit = (cfg->env_kind != XARM_ENV_PICK_AND_PLACE && cfg->env_kind != XARM_ENV_REACH) || cfg->step_coop_limit < 0 ? 0 :
-                         (cfg->step_coop_limit > 0 ? cfg->step_coop_limit : XARM_STEP_COOP_LIMIT_DEFAULT);
-    {
-        const char *ev = getenv("XARM_STEP_COOP_LIMIT");
-        if (ev && *ev && cfg->step_coop_limit == 0 && (cfg->env_kind == XARM_ENV_PICK_AND_PLACE || cfg->env_kind == XARM_ENV_REACH))
-            h->coop_step_limit = atoi(ev) > 0 ? atoi(ev) : 0;
-    }
-    const bool handover2 = handover && cfg->num_obj == 2;
-    const bool handover1 = handover && !handover2;
+    int v;
+    // cooperative reset kernel: default cross-over measured on MI355X (Handover with one stick, two rows per env,
+    // against the lane-pair reset: DESIGN.md 10b); 0 disables it
+    h->kp.coop_limit = ops->reset_coop_default ? resolve_limit(cfg->reset_coop_limit, ops->reset_coop_default, "XARM_RESET_COOP_LIMIT") : 0;
+    // cooperative step kernel: pays while the one-env-per-lane launch would leave SIMDs empty (measured cross-over).
     // Handover (one stick): small batches step on the cooperative rows altogether - 2 048 envs are one round of 1 024 wavefronts
     // and one kernel of ~0.6 ms, where the fast lane-pair kernel (0.72 ms whatever the batch, a latency) plus the hand-off take 1.4
-    if (handover1 && cfg->step_coop_limit >= 0) {
-        h->coop_step_limit = cfg->step_coop_limit > 0 ? cfg->step_coop_limit : XARM_HO_STEP_COOP_LIMIT_DEFAULT;
-        const char *ev = getenv("XARM_STEP_COOP_LIMIT");
-        if (ev && *ev && cfg->step_coop_limit == 0) h->coop_step_limit = atoi(ev) > 0 ? atoi(ev) : 0;
-    }
-    // cooperative reset of Handover (one stick): two rows per env, measured cross-over against the lane-pair reset
-    if (handover1) {
-        h->kp.coop_limit = cfg->reset_coop_limit > 0 ? cfg->reset_coop_limit : (cfg->reset_coop_limit < 0 ? 0 : XARM_HO_RESET_COOP_LIMIT_DEFAULT);
-        const char *ev = getenv("XARM_RESET_COOP_LIMIT");
-        if (ev && *ev && cfg->reset_coop_limit == 0) h->kp.coop_limit = atoi(ev) > 0 ? atoi(ev) : 0;
-    }
+    h->coop_step_limit = ops->step_coop_default ? resolve_limit(cfg->step_coop_limit, ops->step_coop_default, "XARM_STEP_COOP_LIMIT") : 0;
     // fast-step pipeline (PickAndPlace batches above the cooperative limit, Handover with one stick): on unless the caller
     // pinned the one-env-per-lane family (step_coop_limit < 0: gym_xarm_amd.distributed.reproducible_limits('lane')) or
     // XARM_STEP_PIPELINE=0 asks for the plain k_step / k_ho_step
-    h->fast_pipeline = ((cfg->env_kind == XARM_ENV_PICK_AND_PLACE || handover1) && cfg->step_coop_limit >= 0 && cfg->auto_reset != XARM_AUTO_RESET_LAZY) ? 1 : 0;
-    {
-        const char *ev = getenv("XARM_STEP_PIPELINE");
-        if (ev && *ev) h->fast_pipeline = h->fast_pipeline && atoi(ev) != 0;
-        ev = getenv("XARM_HO_FORCE_COUPLED");
-        h->ho_force_coupled = ev && *ev && atoi(ev) != 0;
-        // staged Handover step: XARM_HO_STAGES=1 is the unstaged pipeline (one fast launch, one hand-off)
-        h->ho_stages = handover1 && h->fast_pipeline ? XARM_HO_STAGES_DEFAULT : 1;
-        ev = getenv("XARM_HO_STAGES");
-        if (ev && *ev && handover1 && h->fast_pipeline) h->ho_stages = atoi(ev) < 1 ? 1 : (atoi(ev) > xarm_handle::MAX_ST ? xarm_handle::MAX_ST : atoi(ev));
-        // PickAndPlace: the same staging of the 15 substeps (XARM_PNP_STAGES; 1 = unstaged)
-        const bool pnp_pipe = cfg->env_kind == XARM_ENV_PICK_AND_PLACE && h->fast_pipeline;
-        if (pnp_pipe) h->ho_stages = XARM_PNP_STAGES_DEFAULT;
-        ev = getenv("XARM_PNP_STAGES");
-        if (ev && *ev && pnp_pipe) h->ho_stages = atoi(ev) < 1 ? 1 : (atoi(ev) > xarm_handle::MAX_ST ? xarm_handle::MAX_ST : atoi(ev));
-        static_assert(xm::HO_N_TICKS == xm::PNP_N_SUBSTEPS, "one stage table for both");
-        for (int c = 0; c <= h->ho_stages; c++) h->ho_tick[c] = c * xm::HO_N_TICKS / h->ho_stages;
-        // measurement hook: XARM_HO_STAGE_TICKS="3,9" = the interior stage boundaries (increasing, inside 1 .. 14)
-        ev = getenv("XARM_HO_STAGE_TICKS");
-        if (ev && *ev && h->ho_stages > 1) {
-            int c = 1, prev = 0;
-            const char *q = ev;
-            while (*q && c < h->ho_stages) {
-                const int v = atoi(q);
-                if (v <= prev || v >= xm::HO_N_TICKS) break;
-                h->ho_tick[c++] = prev = v;
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
-            if (c != h->ho_stages) for (int k = 0; k <= h->ho_stages; k++) h->ho_tick[k] = k * xm::HO_N_TICKS / h->ho_stages;   // malformed: the default
+    h->fast_pipeline = (ops->stages_env && cfg->step_coop_limit >= 0 && cfg->auto_reset != XARM_AUTO_RESET_LAZY) ? 1 : 0;
+    if (env_int("XARM_STEP_PIPELINE", &v)) h->fast_pipeline = h->fast_pipeline && v != 0;
+    h->ho_force_coupled = env_int("XARM_HO_FORCE_COUPLED", &v) && v != 0;
+    // staged step: XARM_HO_STAGES=1 / XARM_PNP_STAGES=1 is the unstaged pipeline (one fast launch, one hand-off)
+    h->ho_stages = 1;
+    if (h->fast_pipeline) h->ho_stages = clamp_stages(env_int(ops->stages_env, &v) ? v : ops->stages_default);
+    for (int c = 0; c <= h->ho_stages; c++) h->ho_tick[c] = c * xm::HO_N_TICKS / h->ho_stages;
+    // measurement hook: XARM_HO_STAGE_TICKS="3,9" = the interior stage boundaries (increasing, inside 1 .. 14)
+    const char *ev = getenv("XARM_HO_STAGE_TICKS");
+    if (ev && *ev && h->ho_stages > 1) {
+        int c = 1, prev = 0;
+        const char *q = ev;
+        while (*q && c < h->ho_stages) {
+            const int t = atoi(q);
+            if (t <= prev || t >= xm::HO_N_TICKS) break;
+            h->ho_tick[c++] = prev = t;
+            while (*q && *q != ',') q++;
+            if (*q == ',') q++;
         }
+        if (c != h->ho_stages) for (int k = 0; k <= h->ho_stages; k++) h->ho_tick[k] = k * xm::HO_N_TICKS / h->ho_stages;   // malformed: the default
     }
+    const bool handover1 = ops == &KIND_HANDOVER1;
     h->kp.eject_coop_cap = handover1 ? XARM_HO_EJECT_COOP_CAP : XARM_EJECT_COOP_CAP;
     // step_coop_limit == 1 is the pin of reproducible_limits('fast'): every hand-off list steps on the cooperative kernel (it
     // walks the list with a grid stride), so that which kernel steps an env is a function of the handle's config alone
     if (cfg->step_coop_limit == 1) h->kp.eject_coop_cap = 0x7fffffff;
-    h->kp.state_dim = reach ? xr::STATE_DIM : (handover2 ? xh2::STATE_DIM : (handover ? xh::STATE_DIM : (stack ? xs::STATE_DIM : (rearrange ? xra::STATE_DIM : xk::STATE_DIM))));
+    h->kp.state_dim = ops->dims.state_dim;
     h->kp.hcfg.seed = cfg->seed;
     h->kp.hcfg.env_id_offset = cfg->env_id_offset;
     h->kp.hcfg.same_side_rate = cfg->same_side_rate;
@@ -303,17 +499,13 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
     h->kp.rcfg.reward_type = cfg->reward_type;
     hipError_t e1 = hipMalloc(&h->kp.state, sizeof(float) * h->kp.state_dim * stride);
     hipError_t e2 = hipMalloc(&h->done_list, sizeof(int) * stride);
-    static_assert(xra::NCLS >= xs::NCLS, "one counter block serves both class orders");
-    hipError_t e3 = hipMalloc(&h->counters, sizeof(int) * (3 + 2 * xra::NCLS));   // (Handover: +3 + c = hand-off count of stage c >= 1)
-    h->done_count = h->counters; h->eject_count = h->counters + 1; h->class_hist = h->counters + 3;
+    hipError_t e3 = hipMalloc(&h->counters, sizeof(int) * CNT_INTS);
     hipError_t e4 = hipMalloc(&h->mask_count, sizeof(int));
     if (e4 == hipSuccess && h->fast_pipeline) {
         e4 = hipMalloc(&h->eject_list, sizeof(int) * stride * h->ho_stages);   // one list per stage
         if (e4 == hipSuccess) e4 = hipMalloc(&h->done_list_b, sizeof(int) * stride);
-        const char *ev = getenv("XARM_RESET_OVERLAP");
-        // (PickAndPlace only: Handover's reset is six single-substep ticks, 0.28 ms whether it runs beside the hand-off or after
-        // it, and the two launches slow each other down when they overlap - 1.78 against 1.76 ms per call)
-        if (e4 == hipSuccess && cfg->auto_reset && !handover1 && !(ev && *ev && atoi(ev) == 0)) {
+        // the reset overlap is PickAndPlace's (Handover: see ho_fast)
+        if (e4 == hipSuccess && cfg->auto_reset && !handover1 && !(env_int("XARM_RESET_OVERLAP", &v) && v == 0)) {
             e4 = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
             if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
             if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming);
@@ -325,22 +517,18 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
         if (e4 == hipSuccess) e4 = hipMalloc(&h->ho_flag, stride);
         if (e4 == hipSuccess) e4 = hipMemset(h->ho_flag, 0, stride);
         for (int c = 0; c + 1 < h->ho_stages && e4 == hipSuccess; c++) {
-            const char *pv = getenv("XARM_HO_SIDE_PRIO");
             int lo = 0, hi = 0;
             hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = the LEAST urgent (numerically greatest)
-            if (pv && *pv && atoi(pv) != 0) e4 = hipStreamCreateWithPriority(&h->st_side[c], hipStreamNonBlocking, lo);
+            if (env_int("XARM_HO_SIDE_PRIO", &v) && v != 0) e4 = hipStreamCreateWithPriority(&h->st_side[c], hipStreamNonBlocking, lo);
             else e4 = hipStreamCreateWithFlags(&h->st_side[c], hipStreamNonBlocking);
             if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&h->st_fork[c], hipEventDisableTiming);
             if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&h->st_join[c], hipEventDisableTiming);
         }
     }
-    if (e4 == hipSuccess && (stack || rearrange)) {
-        const char *ev = getenv(stack ? "XARM_ST_CLASS_ORDER" : "XARM_RA_CLASS_ORDER");
-        if (!(ev && *ev && atoi(ev) == 0)) {
-            e4 = hipMalloc(&h->class_key, stride);
-            if (e4 == hipSuccess) e4 = hipMalloc(&h->class_order, sizeof(int) * stride);
-            if (e4 == hipSuccess) e4 = hipMemset(h->class_key, 0, stride);
-        }
+    if (e4 == hipSuccess && ops->class_env && !(env_int(ops->class_env, &v) && v == 0)) {
+        e4 = hipMalloc(&h->class_key, stride);
+        if (e4 == hipSuccess) e4 = hipMalloc(&h->class_order, sizeof(int) * stride);
+        if (e4 == hipSuccess) e4 = hipMemset(h->class_key, 0, stride);
     }
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
         fail(nullptr, XARM_E_HIP, "xarm_create: hipMalloc failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : (e3 != hipSuccess ? e3 : e4))));
@@ -348,14 +536,9 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
         return XARM_E_HIP;
     }
     hipMemset(h->kp.state, 0, sizeof(float) * h->kp.state_dim * stride);
-    hipMemset(h->counters, 0, sizeof(int) * (3 + 2 * xra::NCLS));
+    hipMemset(h->counters, 0, sizeof(int) * CNT_INTS);
     hipMemset(h->mask_count, 0, sizeof(int));
-    if (reach) k_reach_init<<<dim3((unsigned)(stride / WG)), dim3(WG)>>>(h->kp);
-    else if (handover2) k_ho2_init<<<dim3((unsigned)(2 * stride / WG)), dim3(WG)>>>(h->kp);
-    else if (handover) k_ho_init<<<dim3((unsigned)(2 * stride / WG)), dim3(WG)>>>(h->kp);
-    else if (stack) k_st_init<<<dim3((unsigned)(2 * stride / WG)), dim3(WG)>>>(h->kp);
-    else if (rearrange) k_ra_init<<<dim3((unsigned)(2 * stride / WG)), dim3(WG)>>>(h->kp);
-    else k_init<<<dim3((unsigned)(stride / WG)), dim3(WG)>>>(h->kp);
+    ops->init(h);
     hipError_t e5 = hipDeviceSynchronize();
     if (e5 != hipSuccess) {
         fail(nullptr, XARM_E_HIP, "xarm_create: k_init: %s", hipGetErrorString(e5));
@@ -396,20 +579,7 @@ int xarm_destroy(xarm_handle *h) {
 
 int xarm_dims(const xarm_handle *h, xarm_dims_t *out) {
     if (!out) return XARM_E_INVALID;
-    const bool reach = h && h->cfg.env_kind == XARM_ENV_REACH, handover = h && h->cfg.env_kind == XARM_ENV_HANDOVER;
-    const bool stack = h && h->cfg.env_kind == XARM_ENV_STACK_TOWER;
-    const bool handover2 = handover && h->cfg.num_obj == 2;
-    if (h && h->cfg.env_kind == XARM_ENV_REARRANGE) {
-        out->obs_dim = xra::OBS_DIM; out->goal_dim = xra::GOAL_DIM; out->act_dim = xra::ACT_DIM; out->state_dim = xra::STATE_DIM;
-        out->max_episode_steps = xm::RA_MAX_EPISODE_STEPS; out->n_substeps = xm::ST_N_SUBSTEPS;
-        return XARM_OK;
-    }
-    out->obs_dim = reach ? xr::OBS_DIM : (handover2 ? xh2::OBS_DIM : (handover ? xh::OBS_DIM : (stack ? xs::OBS_DIM : xk::OBS_DIM)));
-    out->goal_dim = stack ? xs::GOAL_DIM : (handover2 ? xh2::GOAL_DIM : xk::GOAL_DIM);
-    out->act_dim = handover ? xh::ACT_DIM : (stack ? xs::ACT_DIM : xk::ACT_DIM);
-    out->state_dim = reach ? xr::STATE_DIM : (handover2 ? xh2::STATE_DIM : (handover ? xh::STATE_DIM : (stack ? xs::STATE_DIM : xk::STATE_DIM)));
-    out->max_episode_steps = reach ? xmr::MAX_EPISODE_STEPS : (handover ? xm::HO_MAX_EPISODE_STEPS : (stack ? xm::ST_MAX_EPISODE_STEPS : xm::PNP_MAX_EPISODE_STEPS));
-    out->n_substeps = reach ? xmr::N_SUBSTEPS : (handover ? xm::HO_N_TICKS : (stack ? xm::ST_N_SUBSTEPS : xm::PNP_N_SUBSTEPS));
+    *out = (h ? h->ops : &KIND_PNP)->dims;
     return XARM_OK;
 }
 
@@ -418,22 +588,11 @@ int xarm_reset(xarm_handle *h, const uint8_t *mask_dev, float *obs_dev, float *a
     DEVGUARD(h);
     if (obs_dev && (!ag_dev || !dg_dev)) return fail(h, XARM_E_INVALID, "%s", "xarm_reset: goal buffers required with obs");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(h->kp.stride / WG);
     if (mask_dev) {
         HIPCHK(h, hipMemsetAsync(h->mask_count, 0, sizeof(int), st));
         k_compact_mask<<<dim3((unsigned)((h->kp.num_envs + 255) / 256)), dim3(256), 0, st>>>(mask_dev, h->kp.num_envs, h->done_list, h->mask_count);
-        if (h->cfg.env_kind == XARM_ENV_REACH) launch_reach_reset(h, h->done_list, h->mask_count, obs_dev, ag_dev, dg_dev, st);
-        else if (h->cfg.env_kind == XARM_ENV_HANDOVER) launch_ho_reset(h, 2 * grid, h->done_list, h->mask_count, obs_dev, ag_dev, dg_dev, st);
-        else if (h->cfg.env_kind == XARM_ENV_STACK_TOWER) k_st_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, h->done_list, h->mask_count, obs_dev, ag_dev, dg_dev, h->class_key);
-        else if (h->cfg.env_kind == XARM_ENV_REARRANGE) k_ra_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, h->done_list, h->mask_count, obs_dev, ag_dev, dg_dev, h->class_key);
-        else launch_pnp_reset(h, h->done_list, h->mask_count, obs_dev, ag_dev, dg_dev, st);
-    } else {
-        if (h->cfg.env_kind == XARM_ENV_REACH) launch_reach_reset(h, nullptr, nullptr, obs_dev, ag_dev, dg_dev, st);
-        else if (h->cfg.env_kind == XARM_ENV_HANDOVER) launch_ho_reset(h, 2 * grid, nullptr, nullptr, obs_dev, ag_dev, dg_dev, st);
-        else if (h->cfg.env_kind == XARM_ENV_STACK_TOWER) k_st_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, nullptr, nullptr, obs_dev, ag_dev, dg_dev, h->class_key);
-        else if (h->cfg.env_kind == XARM_ENV_REARRANGE) k_ra_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, nullptr, nullptr, obs_dev, ag_dev, dg_dev, h->class_key);
-        else launch_pnp_reset(h, nullptr, nullptr, obs_dev, ag_dev, dg_dev, st);
     }
+    h->ops->reset(h, mask_dev ? h->done_list : nullptr, mask_dev ? h->mask_count : nullptr, obs_dev, ag_dev, dg_dev, st);
     HIPCHK(h, hipGetLastError());
     return XARM_OK;
 }
@@ -445,184 +604,27 @@ int xarm_step(xarm_handle *h, const float *actions_dev, float *obs_dev, float *a
     if (!actions_dev || !obs_dev || !ag_dev || !dg_dev || !reward_dev || !done_dev || !success_dev)
         return fail(h, XARM_E_INVALID, "%s", "xarm_step: null buffer");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(h->kp.stride / WG);
-    int *cnt = h->done_count;
+    const StepIO io{actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev};
     const bool timed = h->timing && h->ev_created;
-    bool pipelined = false;
-    const bool overlap = h->reset_overlap && h->kp.auto_reset;
     if (timed && h->ev_n == xarm_handle::NEV) timing_flush(h);
     if (timed) HIPCHK(h, hipEventRecord(h->ev0[h->ev_n], st));
-    const bool reach = h->cfg.env_kind == XARM_ENV_REACH, handover = h->cfg.env_kind == XARM_ENV_HANDOVER;
-    const bool stack = h->cfg.env_kind == XARM_ENV_STACK_TOWER, rearrange = h->cfg.env_kind == XARM_ENV_REARRANGE;
-    const HoStage whole{0, xm::HO_N_TICKS, nullptr, nullptr};   // Handover: an unstaged step
-    if (h->kp.auto_reset == XARM_AUTO_RESET_LAZY) {
-        k_step_lazy<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev);
+    if (h->kp.auto_reset == XARM_AUTO_RESET_LAZY) {     // PickAndPlace only (xarm_create); no terminal_obs, no counters
+        k_step_lazy<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, io.actions, io.obs, io.ag, io.dg, io.reward, io.done, io.success);
         if (timed) { HIPCHK(h, hipEventRecord(h->ev1[h->ev_n], st)); HIPCHK(h, hipEventRecord(h->ev2[h->ev_n], st)); h->ev_n++; }
         HIPCHK(h, hipGetLastError());
         return XARM_OK;
     }
     // the call's device-side counters (ended episodes, hand-offs, class histogram): zeroed here, in stream order - the
     // handle keeps no host-side per-step state, so a captured step call replays correctly
-    HIPCHK(h, hipMemsetAsync(h->counters, 0, sizeof(int) * ((rearrange && h->class_key) ? 3 + 2 * xra::NCLS : ((stack && h->class_key) ? 3 + 2 * xs::NCLS :
-                                                         (h->fast_pipeline ? (h->ho_stages > 1 ? 4 + xarm_handle::MAX_ST : 3) : 1))), st));
-    if (rearrange) {
-        if (h->class_key) {
-            const unsigned cg = (unsigned)((h->kp.num_envs + 255) / 256);
-            k_ra_class_hist<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, h->class_hist);
-            k_ra_class_place<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, h->class_hist, h->class_hist + xra::NCLS, h->class_order, WG / 2);
-        }
-        k_ra_step<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                       terminal_obs_dev, h->done_list, cnt, h->class_order, h->class_key);
-    }
-    else if (stack) {
-        if (h->class_key) {
-            const unsigned cg = (unsigned)((h->kp.num_envs + 255) / 256);
-            k_class_hist<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, h->class_hist);
-            k_class_place<<<dim3(cg), dim3(256), 0, st>>>(h->class_key, h->kp.num_envs, h->class_hist, h->class_hist + xs::NCLS, h->class_order, WG / 2);
-        }
-        k_st_step<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                       terminal_obs_dev, h->done_list, cnt, h->class_order, h->class_key);
-    }
-    else if (handover && h->cfg.num_obj == 2) {
-        if (h->kp.hcfg.use_stand) k_ho2_step<xh::HandoverStandScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                        terminal_obs_dev, h->done_list, cnt);
-        else k_ho2_step<xh::HandoverScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                        terminal_obs_dev, h->done_list, cnt);
-    }
-    else if (handover && h->cfg.num_obj == 1 && h->kp.num_envs <= (int64_t)h->coop_step_limit) {
-        // small batch: every env on the cooperative rows, one launch (list == null: all envs; finished episodes -> done_list)
-        launch_ho_coop_step(h, ho_coop_grid(h->kp.num_envs), actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev,
-                            h->done_list, cnt, nullptr, nullptr, whole, st);
-    }
-    else if (handover && h->fast_pipeline) {
-        // as for PickAndPlace below: every env on the pad-free fast lane-pair step, the ones with an active finger-pad row
-        // handed off, untouched, to the cooperative rows (lists of at most eject_coop_cap envs) or to k_ho_step (longer).
-        // STAGED: the fast kernel runs the 15 ticks in ho_stages launches.  An env whose pads come alive in stage c keeps the
-        // state it had before that stage and re-runs the ticks from the stage's first one on the cooperative rows - on a side
-        // stream, beside the next fast stage (16 384 envs are 512 of the 1 024 SIMDs); only the last stage's hand-off, a third
-        // of a step long, is on the critical path: fast 0.73 + hand-off 0.69 ms became 0.77 + 0.27.
-        pipelined = true;
-        const bool stand = h->kp.hcfg.use_stand != 0;
-        const int nst = h->ho_stages;
-        const int64_t cap = h->kp.num_envs < (int64_t)h->kp.eject_coop_cap ? h->kp.num_envs : (int64_t)h->kp.eject_coop_cap;
-        for (int c = 0; c < nst; c++) {
-            const HoStage sg{h->ho_tick[c], h->ho_tick[c + 1], h->ho_qt, h->ho_flag};
-            int *elist = h->eject_list + (int64_t)c * h->kp.stride, *ecnt = c == 0 ? h->eject_count : h->counters + 3 + c;
-            if (stand) k_ho_step_fast<xh::HandoverStandScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                                                 terminal_obs_dev, h->done_list, cnt, elist, ecnt, sg);
-            else k_ho_step_fast<xh::HandoverScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                                      terminal_obs_dev, h->done_list, cnt, elist, ecnt, sg);
-            hipStream_t hs = st;
-            if (c + 1 < nst) {
-                hs = h->st_side[c];
-                HIPCHK(h, hipEventRecord(h->st_fork[c], st));
-                HIPCHK(h, hipStreamWaitEvent(hs, h->st_fork[c], 0));
-            }
-            // one done list for every kernel of the call (atomic appends), one reset launch after the last hand-off
-            const HoStage rest{sg.tick0, xm::HO_N_TICKS, h->ho_qt, h->ho_flag};
-            launch_ho_coop_step(h, ho_coop_grid(cap), actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev,
-                                h->done_list, cnt, elist, ecnt, rest, hs);
-            if (h->kp.num_envs > cap) {
-                if (stand) k_ho_step<xh::HandoverStandScene><<<dim3(2 * grid), dim3(WG), 0, hs>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                                                terminal_obs_dev, h->done_list, cnt, elist, ecnt, rest);
-                else k_ho_step<xh::HandoverScene><<<dim3(2 * grid), dim3(WG), 0, hs>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                                     terminal_obs_dev, h->done_list, cnt, elist, ecnt, rest);
-            }
-            if (c + 1 < nst) HIPCHK(h, hipEventRecord(h->st_join[c], hs));
-        }
-        for (int c = 0; c + 1 < nst; c++) HIPCHK(h, hipStreamWaitEvent(st, h->st_join[c], 0));
-    }
-    else if (handover && h->kp.hcfg.use_stand)
-        k_ho_step<xh::HandoverStandScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev,
-                                                                           success_dev, terminal_obs_dev, h->done_list, cnt, nullptr, nullptr, whole);
-    else if (handover)
-        k_ho_step<xh::HandoverScene><<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev,
-                                                                      success_dev, terminal_obs_dev, h->done_list, cnt, nullptr, nullptr, whole);
-    else if (reach && h->kp.num_envs <= (int64_t)h->coop_step_limit)
-        k_reach_step_coop<<<dim3((unsigned)((h->kp.num_envs + COOP_ENVS - 1) / COOP_ENVS)), dim3(WG), 0, st>>>(
-            h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, h->done_list, cnt);
-    else if (reach)
-        k_reach_step<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                      terminal_obs_dev, h->done_list, cnt);
-    else if (h->kp.num_envs <= (int64_t)h->coop_step_limit)
-        k_step_coop<<<dim3((unsigned)((h->kp.num_envs + COOP_ENVS - 1) / COOP_ENVS)), dim3(WG), 0, st>>>(
-            h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, h->done_list, cnt);
-    else if (h->fast_pipeline && h->ho_stages > 1) {
-        // STAGED PickAndPlace step (XARM_PNP_STAGES): as the staged Handover step above - fast stages on the caller's stream, each
-        // stage's hand-off on a side stream beside the next stage, the last one's on the caller's stream; with the reset overlap the
-        // episodes that ended on the fast path are reset on `side` after the last fast stage, those that ended in a hand-off after all of them
-        pipelined = true;
-        const int nst = h->ho_stages;
-        const int64_t cap = h->kp.num_envs < (int64_t)h->kp.eject_coop_cap ? h->kp.num_envs : (int64_t)h->kp.eject_coop_cap;
-        const unsigned cgrid = (unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS) < 1024u ? (unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS) : 1024u;
-        int *list_b = overlap ? h->done_list_b : h->done_list, *cnt_b = overlap ? h->eject_count + 1 : cnt;
-        for (int c = 0; c < nst; c++) {
-            const HoStage sg{h->ho_tick[c], h->ho_tick[c + 1], h->ho_qt, h->ho_flag};
-            int *elist = h->eject_list + (int64_t)c * h->kp.stride, *ecnt = c == 0 ? h->eject_count : h->counters + 3 + c;
-            k_step_fast_stage<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                               terminal_obs_dev, h->done_list, cnt, elist, ecnt, sg);
-            hipStream_t hs = st;
-            if (c + 1 < nst) {
-                hs = h->st_side[c];
-                HIPCHK(h, hipEventRecord(h->st_fork[c], st));
-                HIPCHK(h, hipStreamWaitEvent(hs, h->st_fork[c], 0));
-            } else if (overlap) {
-                HIPCHK(h, hipEventRecord(h->ev_fork, st));
-                HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-                launch_pnp_reset(h, h->done_list, cnt, obs_dev, ag_dev, dg_dev, h->side);
-                HIPCHK(h, hipEventRecord(h->ev_join, h->side));
-            }
-            const HoStage rest{sg.tick0, xm::PNP_N_SUBSTEPS, h->ho_qt, h->ho_flag};
-            k_step_coop_list_stage<<<dim3(cgrid), dim3(WG), 0, hs>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                     terminal_obs_dev, list_b, cnt_b, elist, ecnt, rest);
-            if (h->kp.num_envs > cap)
-                k_step_from_stage<<<dim3(grid), dim3(WG), 0, hs>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                                   terminal_obs_dev, list_b, cnt_b, elist, ecnt, rest);
-            if (c + 1 < nst) HIPCHK(h, hipEventRecord(h->st_join[c], hs));
-        }
-        for (int c = 0; c + 1 < nst; c++) HIPCHK(h, hipStreamWaitEvent(st, h->st_join[c], 0));
-    }
-    else if (h->fast_pipeline) {
-        // every env on the pad-free fast step; the ones with an active finger-pad row are handed off, untouched, to the
-        // cooperative kernel (lists of at most eject_coop_cap envs) or to k_step (longer lists) - both launched, the one
-        // out of its range exits at once (the count lives on the device).  Episodes that end in the hand-off go to a
-        // list of their own (done_list_b): the reset of the ~98 % that ended in k_step_fast need not wait for it.
-        pipelined = true;
-        k_step_fast<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                     terminal_obs_dev, h->done_list, cnt, h->eject_list, h->eject_count);
-        if (overlap) {
-            // a reset is six sequential ticks of latency on a few hundred wavefronts (2.9 ms), the hand-off 0.55 ms on a
-            // few hundred others: started now on the side stream, the first reset overlaps the hand-off.  The call still
-            // waits for the second one - a few dozen envs, but the ones with a finger contact, whose reset carries the pad
-            // rows through the homing ticks (worth 0.16 ms per call at 16 384 envs, nothing at 65 536)
-            HIPCHK(h, hipEventRecord(h->ev_fork, st));
-            HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            launch_pnp_reset(h, h->done_list, cnt, obs_dev, ag_dev, dg_dev, h->side);
-            HIPCHK(h, hipEventRecord(h->ev_join, h->side));
-        }
-        const int64_t cap = h->kp.num_envs < (int64_t)h->kp.eject_coop_cap ? h->kp.num_envs : (int64_t)h->kp.eject_coop_cap;
-        const unsigned cgrid = (unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS) < 1024u ? (unsigned)((cap + COOP_ENVS - 1) / COOP_ENVS) : 1024u;
-        // without the side stream (XARM_RESET_OVERLAP=0): one list, one reset after the hand-off
-        int *list_b = overlap ? h->done_list_b : h->done_list, *cnt_b = overlap ? h->eject_count + 1 : cnt;
-        k_step_coop_list<<<dim3(cgrid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                           terminal_obs_dev, list_b, cnt_b, h->eject_list, h->eject_count);
-        if (h->kp.num_envs > cap)
-            k_step<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                    terminal_obs_dev, list_b, cnt_b, h->eject_list, h->eject_count);
-    } else
-        k_step<<<dim3(grid), dim3(WG), 0, st>>>(h->kp, actions_dev, obs_dev, ag_dev, dg_dev, reward_dev, done_dev, success_dev,
-                                                terminal_obs_dev, h->done_list, cnt, nullptr, nullptr);
+    HIPCHK(h, hipMemsetAsync(h->counters, 0, sizeof(int) * step_counter_ints(h), st));
+    const int rc = h->ops->step(h, io, st);
+    if (rc != XARM_OK) return rc;
     if (timed) HIPCHK(h, hipEventRecord(h->ev1[h->ev_n], st));
-    if (h->kp.auto_reset && pipelined && overlap) {     // PickAndPlace only (Handover keeps one list, xarm_create)
-        launch_pnp_reset(h, h->done_list_b, h->eject_count + 1, obs_dev, ag_dev, dg_dev, st);
+    if (h->reset_overlap && !small_batch(h)) {     // the PickAndPlace pipeline reset list A on `side` (pnp_overlapped_reset)
+        pnp_reset(h, h->done_list_b, slot(h, CNT_DONE_B), obs_dev, ag_dev, dg_dev, st);
         HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
-    } else if (h->kp.auto_reset) {
-        if (reach) launch_reach_reset(h, h->done_list, cnt, obs_dev, ag_dev, dg_dev, st);
-        else if (handover) launch_ho_reset(h, 2 * grid, h->done_list, cnt, obs_dev, ag_dev, dg_dev, st);
-        else if (stack) k_st_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, h->done_list, cnt, obs_dev, ag_dev, dg_dev, h->class_key);
-        else if (rearrange) k_ra_reset<<<dim3(2 * grid), dim3(WG), 0, st>>>(h->kp, h->done_list, cnt, obs_dev, ag_dev, dg_dev, h->class_key);
-        else launch_pnp_reset(h, h->done_list, cnt, obs_dev, ag_dev, dg_dev, st);
-    }
+    } else if (h->kp.auto_reset)
+        h->ops->reset(h, h->done_list, slot(h, CNT_DONE), obs_dev, ag_dev, dg_dev, st);
     if (timed) { HIPCHK(h, hipEventRecord(h->ev2[h->ev_n], st)); h->ev_n++; }
     HIPCHK(h, hipGetLastError());
     return XARM_OK;
@@ -632,39 +634,9 @@ int xarm_compute_reward(xarm_handle *h, const float *ag_dev, const float *g_dev,
     if (!h) return XARM_E_INVALID;
     DEVGUARD(h);
     if (n < 0 || (n > 0 && (!ag_dev || !g_dev || !out_dev))) return fail(h, XARM_E_INVALID, "%s", "xarm_compute_reward: bad argument");
-    if (h->cfg.env_kind == XARM_ENV_STACK_TOWER) {
-        if (n == 0) return XARM_OK;
-        k_st_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->cfg.reward_type, ag_dev, g_dev, n, out_dev);
-        HIPCHK(h, hipGetLastError());
-        return XARM_OK;
-    }
-    if (h->cfg.env_kind == XARM_ENV_REARRANGE) {
-        if (n == 0) return XARM_OK;
-        k_ra_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->cfg.reward_type, ag_dev, g_dev, n, out_dev);
-        HIPCHK(h, hipGetLastError());
-        return XARM_OK;
-    }
-    if (h->cfg.env_kind == XARM_ENV_HANDOVER) {
-        if (h->cfg.reward_type == XARM_REWARD_DENSE)
-            return fail(h, XARM_E_INVALID, "%s", "xarm_compute_reward: reward_type 'dense' depends on the grasp flags and gripper positions and cannot be relabelled");
-        if (n == 0) return XARM_OK;
-        if (h->cfg.num_obj == 2) k_ho2_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(ag_dev, g_dev, n, out_dev);
-        else k_ho_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(ag_dev, g_dev, n, out_dev);
-        HIPCHK(h, hipGetLastError());
-        return XARM_OK;
-    }
-    if (h->cfg.env_kind == XARM_ENV_REACH) {
-        if (h->cfg.reward_type == XARM_REACH_REWARD_DENSE_DIFF)
-            return fail(h, XARM_E_INVALID, "%s", "xarm_compute_reward: reward_type 'dense_diff' is stateful (d_old) and cannot be relabelled");
-        if (n == 0) return XARM_OK;
-        k_reach_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->cfg.reward_type, ag_dev, g_dev, n, out_dev);
-        HIPCHK(h, hipGetLastError());
-        return XARM_OK;
-    }
-    if (h->cfg.reward_type == XARM_REWARD_DENSE)
-        return fail(h, XARM_E_INVALID, "%s", "xarm_compute_reward: reward_type 'dense' depends on the contact state and cannot be relabelled");
+    if (h->ops->fixed_reward_msg && h->cfg.reward_type == h->ops->fixed_reward_type) return fail(h, XARM_E_INVALID, "%s", h->ops->fixed_reward_msg);
     if (n == 0) return XARM_OK;
-    k_compute_reward<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->cfg.reward_type, ag_dev, g_dev, n, out_dev);
+    h->ops->reward(h, ag_dev, g_dev, n, out_dev, (hipStream_t)stream);
     HIPCHK(h, hipGetLastError());
     return XARM_OK;
 }
@@ -689,9 +661,7 @@ int xarm_set_state(xarm_handle *h, const float *state_dev, void *stream) {
 int xarm_episode_steps(xarm_handle *h, int32_t *steps_dev, void *stream) {
     if (!h || !steps_dev) return XARM_E_INVALID;
     DEVGUARD(h);
-    const int field = h->cfg.env_kind == XARM_ENV_REACH ? (int)xr::R_STEPS : (h->cfg.env_kind == XARM_ENV_HANDOVER ? (h->cfg.num_obj == 2 ? (int)xh2::G_STEPS : (int)xh::H_STEPS) :
-                      (h->cfg.env_kind == XARM_ENV_STACK_TOWER ? (int)xs::K_STEPS : (h->cfg.env_kind == XARM_ENV_REARRANGE ? (int)xra::K_STEPS : (int)xk::S_STEPS)));
-    k_episode_steps<<<dim3((unsigned)((h->kp.num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->kp, field, steps_dev);
+    k_episode_steps<<<dim3((unsigned)((h->kp.num_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(h->kp, h->ops->steps_field, steps_dev);
     HIPCHK(h, hipGetLastError());
     return XARM_OK;
 }
@@ -699,8 +669,8 @@ int xarm_episode_steps(xarm_handle *h, int32_t *steps_dev, void *stream) {
 int xarm_debug_substeps(xarm_handle *h, const float *qtarget_dev, int32_t n, void *stream) {
     if (!h || !qtarget_dev || n < 0) return XARM_E_INVALID;
     DEVGUARD(h);
-    if (h->cfg.env_kind != XARM_ENV_PICK_AND_PLACE) return fail(h, XARM_E_INVALID, "%s", "xarm_debug_substeps: PickAndPlace only");
-    k_substeps<<<dim3((unsigned)(h->kp.stride / WG)), dim3(WG), 0, (hipStream_t)stream>>>(h->kp, qtarget_dev, n);
+    if (h->ops != &KIND_PNP) return fail(h, XARM_E_INVALID, "%s", "xarm_debug_substeps: PickAndPlace only");
+    k_substeps<<<dim3(env_grid(h)), dim3(WG), 0, (hipStream_t)stream>>>(h->kp, qtarget_dev, n);
     HIPCHK(h, hipGetLastError());
     return XARM_OK;
 }
@@ -752,28 +722,28 @@ int xarm_kernel_limits(const xarm_handle *h, int32_t *reset_coop_limit, int32_t 
 int xarm_debug_counts(xarm_handle *h, int32_t *finished, int32_t *handed_off, void *stream) {
     if (!h || !finished || !handed_off) return XARM_E_INVALID;
     DEVGUARD(h);
-    int c[4 + xarm_handle::MAX_ST] = {0};
+    int c[CNT_STAGE_INTS] = {0};
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
     HIPCHK(h, hipMemcpy(c, h->counters, sizeof c, hipMemcpyDeviceToHost));
-    *finished = c[0];
-    *handed_off = h->fast_pipeline ? c[1] : 0;
-    for (int k = 1; k < h->ho_stages; k++) *handed_off += c[3 + k];   // staged Handover step: one list per stage
+    *finished = c[CNT_DONE];
+    *handed_off = 0;
+    if (h->fast_pipeline) for (int k = 0; k < h->ho_stages; k++) *handed_off += c[cnt_stage(k)];   // staged step: one list per stage
     return XARM_OK;
 }
 int xarm_stage_info(const xarm_handle *h, int32_t *stages, int32_t *ticks) {
     if (!h || !stages || !ticks) return XARM_E_INVALID;
-    const bool staged = h->fast_pipeline && h->ho_stages > 1 && h->kp.num_envs > (int64_t)h->coop_step_limit;
+    const bool staged = h->fast_pipeline && h->ho_stages > 1 && !small_batch(h);
     *stages = staged ? h->ho_stages : 1;
     for (int c = 0; c <= XARM_HO_MAX_STAGES; c++) ticks[c] = 0;
     if (staged) for (int c = 0; c <= h->ho_stages; c++) ticks[c] = h->ho_tick[c];
-    else if (h->cfg.env_kind == XARM_ENV_HANDOVER || h->cfg.env_kind == XARM_ENV_PICK_AND_PLACE) ticks[1] = xm::HO_N_TICKS;   // (15 ticks / 15 substeps)
+    else ticks[1] = h->ops->unstaged_ticks;   // (15 ticks / 15 substeps)
     return XARM_OK;
 }
 int xarm_pipeline_info(const xarm_handle *h, int32_t *fast_pipeline, int32_t *reset_overlap, int32_t *eject_coop_cap,
                        int32_t *solver_iterations) {
     if (!h || !fast_pipeline || !reset_overlap || !eject_coop_cap || !solver_iterations) return XARM_E_INVALID;
-    const bool small = h->kp.num_envs <= (int64_t)h->coop_step_limit;   // (the limit is 0 for the env kinds without a cooperative step kernel)
-    *fast_pipeline = (h->fast_pipeline && !small) ? 1 : 0;
+    // (the step limit is 0 for the env kinds without a cooperative step kernel)
+    *fast_pipeline = (h->fast_pipeline && !small_batch(h)) ? 1 : 0;
     *reset_overlap = (*fast_pipeline && h->reset_overlap) ? 1 : 0;
     *eject_coop_cap = h->kp.eject_coop_cap;
 #if defined(XARM_SWEEP_VARIANT)
