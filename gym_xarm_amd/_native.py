@@ -19,9 +19,12 @@ RESET_COOP_LIMIT_DEFAULT = STEP_COOP_LIMIT_DEFAULT = 8192   # include/xarm_hip.h
 
 EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step", "xarm_compute_reward",
            "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
-           "xarm_version", "xarm_default_camera", "xarm_render"]
+           "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views"]
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
+VIEW_FLOATS = 16            # XARM_VIEW_FLOATS: eye 0-2, target 3-5, up 6-8, fov_deg 9, near_z 10, far_z 11, mount 12
+RENDER_MAX_VIEWS = 8        # XARM_RENDER_MAX_VIEWS
+MOUNTS = {"world": 0, "hand0": 1, "hand1": 2}   # XARM_MOUNT_WORLD / _HAND0 / _HAND1
 
 
 class XarmConfig(C.Structure):
@@ -85,6 +88,9 @@ def load(path=None):
     L.xarm_class_keys.argtypes = [vp, vp, vp]
     L.xarm_default_camera.argtypes = [vp, C.POINTER(XarmCamera)]
     L.xarm_render.argtypes = [vp, C.POINTER(XarmCamera), vp, C.c_int32, vp, vp, vp, vp]
+    L.xarm_view_from_camera.argtypes = [C.POINTER(XarmCamera), C.POINTER(C.c_float)]
+    L.xarm_default_view.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
+    L.xarm_render_views.argtypes = [vp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, fp, u8p, vp]
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

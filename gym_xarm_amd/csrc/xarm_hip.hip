@@ -777,4 +777,45 @@ int xarm_render(xarm_handle *h, const xarm_camera *cam, const int32_t *env_ids_d
     return XARM_OK;
 }
 
+int xarm_view_from_camera(const xarm_camera *cam, float *view16_host) {
+    if (!cam || !view16_host) return XARM_E_INVALID;
+    float v[XARM_VIEW_FLOATS];
+    if (const char *why = xrc_render::rc_view_from_camera(*cam, v)) return fail(nullptr, XARM_E_INVALID, "xarm_view_from_camera: %s", why);
+    for (int k = 0; k < XARM_VIEW_FLOATS; k++) view16_host[k] = v[k];
+    return XARM_OK;
+}
+
+int xarm_default_view(const xarm_handle *h, int32_t which, float *view16_host) {
+    if (!h || !view16_host) return XARM_E_INVALID;
+    float v[XARM_VIEW_FLOATS];
+    if (xrc_render::rc_default_view(h->cfg.env_kind, which, v) != 0)
+        return fail(const_cast<xarm_handle *>(h), XARM_E_INVALID, "%s",
+                    "xarm_default_view: which must be 0 (world), 1 (wrist of arm 0) or, on a two-arm kind, 2 (wrist of arm 1)");
+    for (int k = 0; k < XARM_VIEW_FLOATS; k++) view16_host[k] = v[k];
+    return XARM_OK;
+}
+
+int xarm_render_views(xarm_handle *h, const float *views_dev, int32_t num_views, int32_t per_env, int32_t width, int32_t height,
+                      int32_t flags, const int32_t *env_ids_dev, int32_t n, uint32_t *rgba_dev, float *depth_dev, uint8_t *seg_dev,
+                      void *stream) {
+    if (!h) return XARM_E_INVALID;
+    if (!views_dev) return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: views_dev is NULL");
+    if (!rgba_dev) return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: rgba_dev is NULL");
+    if (num_views < 1 || num_views > XARM_RENDER_MAX_VIEWS)
+        return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: num_views must lie in [1, XARM_RENDER_MAX_VIEWS]");
+    if (per_env != 0 && per_env != 1) return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: per_env must be 0 or 1");
+    if (!(width >= 1 && width <= XARM_RENDER_MAX_DIM && height >= 1 && height <= XARM_RENDER_MAX_DIM))
+        return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: width and height must lie in [1, XARM_RENDER_MAX_DIM]");
+    if (n < 1 || (int64_t)n > h->kp.num_envs) return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: need 1 <= n <= num_envs");
+    if (flags & ~XARM_RENDER_SHADOWS) return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: unknown flag bits");
+    xrc_render::RScene sc;
+    if (xrc_render::rc_scene_of(h->cfg.env_kind, h->cfg.num_obj, h->kp.hcfg.use_stand, sc) != 0)
+        return fail(h, XARM_E_INVALID, "%s", "xarm_render_views: unknown env kind");
+    DEVGUARD(h);
+    const int le = xrc_render::launch_render_views(h->kp.state, h->kp.stride, h->kp.num_envs, sc, views_dev, num_views, per_env, width, height,
+                                                   flags, env_ids_dev, n, rgba_dev, depth_dev, seg_dev, stream);
+    if (le != 0) return fail(h, XARM_E_HIP, "xarm_render_views: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
 } // extern "C"

@@ -132,6 +132,15 @@ XARM_HD void rc_arm(const RScene &sc, const float *S, int64_t n, int arm, RPrim 
         rc_box_local(P[base + 8 + k], B[base + 8 + k], ff, lo, hi, pal_g, seg_g);
     }
 }
+// the hand frame of an arm: the link-7 frame rc_arm ends its FK with (+z to the fingertips, the fingers slide along y; Reach:
+// the same frame under the xArm gripper box) - the mount of a wrist view.  The same calls in the same order as rc_arm's, apart
+// from it so that rc_arm, and with it k_render's code, stays as it is.
+XARM_HD Frame<float> rc_hand_frame(const RScene &sc, const float *S, int64_t n, int arm) {
+    Frame<float> f = rc_base_frame(sc.kind, arm);
+#pragma unroll
+    for (int i = 0; i < 7; i++) xk::fk_advance(f, i, S[(sc.q_off + 9 * arm + i) * n]);
+    return f;
+}
 
 XARM_HD void rc_object(const RScene &sc, const float *S, int64_t n, int k, RPrim *P, RBound *B) {
     const int slot = sc.narms * sc.arm_prims + k;
@@ -185,6 +194,13 @@ XARM_HD void rc_static(const RScene &sc, const float *S, int64_t n, RPrim *P, RB
 // every primitive of one env (the host build; the kernel spreads the same calls over the lanes of its first wavefront)
 XARM_HD void rc_build_scene(const RScene &sc, const float *S, int64_t n, RPrim *P, RBound *B) {
     for (int a = 0; a < sc.narms; a++) rc_arm(sc, S, n, a, P, B);
+    for (int k = 0; k < sc.nobj; k++) rc_object(sc, S, n, k, P, B);
+    for (int k = 0; k < sc.ngoal; k++) rc_goal(sc, S, n, k, P, B);
+    rc_static(sc, S, n, P, B);
+}
+// the same, keeping the hand frame of every arm (hands[0 .. narms)) for the mounted views
+XARM_HD void rc_build_scene_hands(const RScene &sc, const float *S, int64_t n, RPrim *P, RBound *B, Frame<float> *hands) {
+    for (int a = 0; a < sc.narms; a++) { rc_arm(sc, S, n, a, P, B); hands[a] = rc_hand_frame(sc, S, n, a); }
     for (int k = 0; k < sc.nobj; k++) rc_object(sc, S, n, k, P, B);
     for (int k = 0; k < sc.ngoal; k++) rc_goal(sc, S, n, k, P, B);
     rc_static(sc, S, n, P, B);
@@ -337,6 +353,66 @@ XARM_HD bool rc_bound_visible(const RBound &b, const RCam &cam, int i0, int i1, 
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------- views
+// A view record (include/xarm_hip.h XARM_VIEW_FLOATS = 16 float32, device-resident): eye [0..2], target [3..5], up [6..8] in
+// the MOUNT's frame (PyBullet's computeViewMatrix arguments), fov_deg [9] (vertical), near_z [10], far_z [11], mount [12]
+// (XARM_MOUNT_WORLD 0, XARM_MOUNT_HAND0 1, XARM_MOUNT_HAND1 2: the hand frame of arm 0 / 1); [13..15] ignored.
+//
+// VALIDITY RULE (decided here, per (env, view), because the host never sees the record).  A view is valid iff all of:
+//   floats 0-12 are finite (and so are the world-frame target - eye and up they give);
+//   mount is exactly 0, 1 or 2 and a hand mount names an arm the scene has (mount <= narms);
+//   0 < fov_deg < 180;  0 < near_z < far_z < 1e30;  |target - eye| > 1e-6;  |up| > 1e-6;  |f x up / |up|| > 1e-6
+//   (f the unit view direction: the view direction is not parallel to up).
+// An invalid view renders the invalid image (rgba 0, depth 0, segmentation SEG_INVALID), as an env id out of range does.
+//
+// rc_make_view builds the camera of a valid record in float32: world eye / target / up through the mount frame, then
+// f = (target - eye) / |.|, s = f x up / |.|, u = s x f, right = s tan(fov / 2) W / H, up = u tan(fov / 2) - RCam's ray and
+// depth convention (the ray parameter is the view-axis depth, row 0 the top).  Returns false for an invalid record
+// (`out` is then unspecified).  hands[a] = the hand frame of arm a (rc_hand_frame), a < narms.
+XARM_HD bool rc_finite(float x) { return fabsf(x) < RC_INF; }
+// |v| without overflow or underflow of the squares (any finite v)
+XARM_HD float rc_norm(V3<float> v) {
+    const float m = fmaxf(fabsf(v.x), fmaxf(fabsf(v.y), fabsf(v.z)));
+    if (!(m > 0.0f)) return 0.0f;
+    const V3<float> w = v * (1.0f / m);
+    return m * sqrtf(xk::dot(w, w));
+}
+
+XARM_HD bool rc_make_view(const float *view16, const Frame<float> *hands, int narms, int W, int H, int flags, RCam &out) {
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 13; k++) fin = fin && rc_finite(view16[k]);
+    if (!fin) return false;
+    const float fov = view16[9], near_z = view16[10], far_z = view16[11], m = view16[12];
+    if (!(m == 0.0f || m == 1.0f || m == 2.0f)) return false;
+    const int mount = (int)m;
+    if (mount > narms) return false;
+    if (!(fov > 0.0f && fov < 180.0f)) return false;
+    if (!(near_z > 0.0f && far_z > near_z && far_z < 1e30f)) return false;
+    Frame<float> F = xk::frame_identity<float>();
+    if (mount != XARM_MOUNT_WORLD) F = hands[mount - 1];
+    const V3<float> eye = F.o + F.c0 * view16[0] + F.c1 * view16[1] + F.c2 * view16[2];
+    const V3<float> tgt = F.o + F.c0 * view16[3] + F.c1 * view16[4] + F.c2 * view16[5];
+    const V3<float> up = F.c0 * view16[6] + F.c1 * view16[7] + F.c2 * view16[8];
+    const V3<float> d = tgt - eye;
+    if (!(rc_finite(d.x) && rc_finite(d.y) && rc_finite(d.z) && rc_finite(up.x) && rc_finite(up.y) && rc_finite(up.z))) return false;
+    const float dl = rc_norm(d), ul = rc_norm(up);
+    if (!(dl > 1e-6f && ul > 1e-6f)) return false;
+    const V3<float> f = d * (1.0f / dl);
+    V3<float> s = xk::cross(f, up * (1.0f / ul));
+    const float sl = sqrtf(xk::dot(s, s));
+    if (!(sl > 1e-6f)) return false;
+    s = s * (1.0f / sl);
+    const V3<float> u = xk::cross(s, f);
+    const float ty = tanf(0.5f * fov * 0.017453292519943295f), tx = ty * (float)W / (float)H;
+    out.eye[0] = eye.x; out.eye[1] = eye.y; out.eye[2] = eye.z;
+    out.fwd[0] = f.x; out.fwd[1] = f.y; out.fwd[2] = f.z;
+    out.right[0] = s.x * tx; out.right[1] = s.y * tx; out.right[2] = s.z * tx;
+    out.up[0] = u.x * ty; out.up[1] = u.y * ty; out.up[2] = u.z * ty;
+    out.near_z = near_z; out.far_z = far_z; out.width = W; out.height = H; out.flags = flags;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------------- host-side setup
 // the scene layout of a handle's configuration; returns 0, or -1 for an unknown kind
 inline int rc_scene_of(int kind, int num_obj, int use_stand, RScene &sc) {
@@ -382,6 +458,25 @@ inline int rc_default_camera(int kind, xarm_camera &c) {
     return 0;
 }
 
+// eye and up of a camera: eye = M (0, -distance, 0) + target, up = M (0, 0, 1), M = Rz(yaw) Ry(roll) Rx(pitch)
+inline void rc_camera_pose(const xarm_camera &c, double (&eye)[3], double (&up)[3]) {
+    const double D = 3.14159265358979323846 / 180.0;
+    const double cy = cos(c.yaw_deg * D), sy = sin(c.yaw_deg * D), cr = cos(c.roll_deg * D), sr = sin(c.roll_deg * D);
+    const double cp = cos(c.pitch_deg * D), sp = sin(c.pitch_deg * D);
+    const double Rz[3][3] = {{cy, -sy, 0}, {sy, cy, 0}, {0, 0, 1}}, Ry[3][3] = {{cr, 0, sr}, {0, 1, 0}, {-sr, 0, cr}},
+                 Rx[3][3] = {{1, 0, 0}, {0, cp, -sp}, {0, sp, cp}};
+    double A[3][3], M[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            A[i][j] = 0; for (int k = 0; k < 3; k++) A[i][j] += Rz[i][k] * Ry[k][j];
+        }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            M[i][j] = 0; for (int k = 0; k < 3; k++) M[i][j] += A[i][k] * Rx[k][j];
+        }
+    for (int i = 0; i < 3; i++) { eye[i] = -c.distance * M[i][1] + c.target[i]; up[i] = M[i][2]; }
+}
+
 // PyBullet's computeViewMatrixFromYawPitchRoll (upAxisIndex 2) + computeProjectionMatrixFOV in closed form:
 // eye = Rz(yaw) Ry(roll) Rx(pitch) (0, -distance, 0) + target, up = the same rotation of (0, 0, 1), then a look-at.
 // Returns a message for an argument out of range, 0 when the camera is valid.
@@ -396,22 +491,9 @@ inline const char *rc_make_camera(const xarm_camera &c, RCam &out) {
         if (!(fabsf(c.target[k]) < 1e30f)) return "target must be finite";
     if (!(fabsf(c.yaw_deg) < 1e6f && fabsf(c.pitch_deg) < 1e6f && fabsf(c.roll_deg) < 1e6f)) return "angles must be finite";
     const double D = 3.14159265358979323846 / 180.0;
-    const double cy = cos(c.yaw_deg * D), sy = sin(c.yaw_deg * D), cr = cos(c.roll_deg * D), sr = sin(c.roll_deg * D);
-    const double cp = cos(c.pitch_deg * D), sp = sin(c.pitch_deg * D);
-    // M = Rz(yaw) Ry(roll) Rx(pitch)
-    const double Rz[3][3] = {{cy, -sy, 0}, {sy, cy, 0}, {0, 0, 1}}, Ry[3][3] = {{cr, 0, sr}, {0, 1, 0}, {-sr, 0, cr}},
-                 Rx[3][3] = {{1, 0, 0}, {0, cp, -sp}, {0, sp, cp}};
-    double A[3][3], M[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            A[i][j] = 0; for (int k = 0; k < 3; k++) A[i][j] += Rz[i][k] * Ry[k][j];
-        }
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            M[i][j] = 0; for (int k = 0; k < 3; k++) M[i][j] += A[i][k] * Rx[k][j];
-        }
     double eye[3], up[3], f[3], s[3], u[3];
-    for (int i = 0; i < 3; i++) { eye[i] = -c.distance * M[i][1] + c.target[i]; up[i] = M[i][2]; f[i] = c.target[i] - eye[i]; }
+    rc_camera_pose(c, eye, up);
+    for (int i = 0; i < 3; i++) f[i] = c.target[i] - eye[i];
     double fn = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
     for (int i = 0; i < 3; i++) f[i] /= fn;
     s[0] = f[1] * up[2] - f[2] * up[1]; s[1] = f[2] * up[0] - f[0] * up[2]; s[2] = f[0] * up[1] - f[1] * up[0];
@@ -427,10 +509,47 @@ inline const char *rc_make_camera(const xarm_camera &c, RCam &out) {
     return 0;
 }
 
+// the view record of a camera: mount WORLD, the eye / target / up rc_make_camera looks along, its fov and clip planes (the
+// image size and the flags are arguments of the render call, not of the view).  Returns a message for an argument out of
+// range, 0 when the record was written.
+inline const char *rc_view_from_camera(const xarm_camera &c, float (&out)[XARM_VIEW_FLOATS]) {
+    xarm_camera probe = c;
+    probe.width = probe.height = 1; probe.flags = 0;
+    RCam rc;
+    if (const char *why = rc_make_camera(probe, rc)) return why;
+    double eye[3], up[3];
+    rc_camera_pose(c, eye, up);
+    for (int k = 0; k < XARM_VIEW_FLOATS; k++) out[k] = 0.0f;
+    for (int k = 0; k < 3; k++) { out[k] = (float)eye[k]; out[3 + k] = c.target[k]; out[6 + k] = (float)up[k]; }
+    out[9] = c.fov_deg; out[10] = c.near_z; out[11] = c.far_z; out[12] = (float)XARM_MOUNT_WORLD;
+    return 0;
+}
+
+// the default views of an env kind: which = 0 the default camera as a world view, 1 / 2 the wrist view of arm 0 / 1
+// (render_scene.json "views").  Returns 0, or -1 for an unknown kind / which or an arm the kind does not have.
+inline int rc_default_view(int kind, int which, float (&out)[XARM_VIEW_FLOATS]) {
+    RScene sc;
+    if (rc_scene_of(kind, 1, 0, sc) != 0 || which < 0 || which > sc.narms) return -1;
+    if (which == 0) {
+        xarm_camera c;
+        if (rc_default_camera(kind, c) != 0) return -1;
+        return rc_view_from_camera(c, out) ? -1 : 0;
+    }
+    for (int k = 0; k < XARM_VIEW_FLOATS; k++) out[k] = 0.0f;
+    for (int k = 0; k < 3; k++) { out[k] = xrm::WRIST_EYE[k]; out[3 + k] = xrm::WRIST_TARGET[k]; out[6 + k] = xrm::WRIST_UP[k]; }
+    out[9] = xrm::WRIST_FOV; out[10] = xrm::WRIST_NEAR; out[11] = xrm::WRIST_FAR;
+    out[12] = (float)(which == 1 ? XARM_MOUNT_HAND0 : XARM_MOUNT_HAND1);
+    return 0;
+}
+
 #if defined(__HIPCC__) && !defined(XARM_HOST_BUILD)
 // k_render over the n envs ids[0 .. n) (null: 0 .. n-1) on `stream` (xarm_k_render.hip); returns the launch's hipError_t
 int launch_render(const float *state, int64_t stride, int64_t num_envs, const RScene &sc, const RCam &cam, const int32_t *ids, int32_t n,
                   uint32_t *rgba, float *depth, uint8_t *seg, void *stream);
+// k_render_views: the V views views[(per_env ? k * V : 0) + v] of each env ids[k], into [n, V, height, width] outputs
+int launch_render_views(const float *state, int64_t stride, int64_t num_envs, const RScene &sc, const float *views, int32_t num_views,
+                        int32_t per_env, int32_t width, int32_t height, int32_t flags, const int32_t *ids, int32_t n, uint32_t *rgba,
+                        float *depth, uint8_t *seg, void *stream);
 #endif
 
 }  // namespace xrc_render

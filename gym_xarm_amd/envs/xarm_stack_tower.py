@@ -41,9 +41,12 @@ class XarmStackTowerEnv:
     def seed(self, seed=None):
         return self._vec.seed(seed)
 
-    def render(self, mode="rgb_array", width=None, height=None):
+    def render(self, mode="rgb_array", width=None, height=None, view=None):
         """env 0's image, a NumPy uint8 (H, W, 4) RGBA array (the reference's render(mode='rgb_array')); width / height default
-        to the env kind's camera (VecEnv.default_camera)"""
+        to the env kind's camera (VecEnv.default_camera).  view: a name of VecEnv.default_views() ('world', 'wrist0', 'wrist1')
+        or a [16] view record (VecEnv.view) instead of the default camera"""
+        if view is not None:
+            return self._vec.render(mode, width=width, height=height, views=[view])[0, 0].cpu().numpy()
         return self._vec.render(mode, width=width, height=height)[0].cpu().numpy()
 
     def close(self):

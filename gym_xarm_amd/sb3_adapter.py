@@ -243,8 +243,8 @@ class XarmHandoverNoGoal:
     def seed(self, seed=None):
         return self._env.seed(seed)
 
-    def render(self, mode="rgb_array", width=None, height=None):
-        return self._env.render(mode, width=width, height=height)
+    def render(self, mode="rgb_array", width=None, height=None, view=None):
+        return self._env.render(mode, width=width, height=height, view=view)
 
     def close(self):
         self._env.close()

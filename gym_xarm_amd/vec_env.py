@@ -291,14 +291,117 @@ class XarmPickAndPlaceVecEnv:
         rc = self._L.xarm_render(self._h, C.byref(cam), _ptr(ids), int(n), _ptr(rgba), _ptr(depth), _ptr(seg), self._stream())
         _native.check(self._L, self._h, rc, "xarm_render")
 
-    def render(self, mode="rgb_array", width=None, height=None, env_ids=None, camera=None, depth=False, segmentation=False):
+    # ------------------------------------------------------------------ views (include/xarm_hip.h xarm_render_views)
+    def view(self, mount="world", eye=None, target=None, up=None, fov_deg=60.0, near_z=0.01, far_z=100.0):
+        """a view record: float32 [16] device tensor (eye, target, up in the mount's frame - 'world', or 'hand0' / 'hand1' = the
+        hand frame of arm 0 / 1: +z to the fingertips, the fingers slide along y; vertical fov_deg, near_z, far_z, mount).  up
+        defaults to world z for a world view and to the hand's x for a hand mount.  The record is checked where it is used, on
+        the device: an invalid one renders the invalid image (include/xarm_hip.h: the validity rule)."""
+        if mount not in _native.MOUNTS:
+            raise ValueError("mount %r: one of %s" % (mount, ", ".join(_native.MOUNTS)))
+        if eye is None or target is None:
+            raise ValueError("view() needs eye and target")
+        if up is None:
+            up = (0.0, 0.0, 1.0) if mount == "world" else (1.0, 0.0, 0.0)
+        row = [float(x) for x in eye] + [float(x) for x in target] + [float(x) for x in up]
+        if len(row) != 9:
+            raise ValueError("eye, target and up have three components each")
+        row += [float(fov_deg), float(near_z), float(far_z), float(_native.MOUNTS[mount]), 0.0, 0.0, 0.0]
+        return torch.tensor(row, dtype=torch.float32, device=self.device)
+
+    def view_from_camera(self, camera=None):
+        """the world view with the eye / target / up, fov and clip planes of a camera (dict of xarm_camera fields over
+        default_camera(), as render(camera=...) takes): float32 [16] device tensor"""
+        v = (C.c_float * _native.VIEW_FLOATS)()
+        rc = self._L.xarm_view_from_camera(C.byref(self._camera(camera, None, None)), v)
+        _native.check(self._L, None, rc, "xarm_view_from_camera")
+        return torch.tensor(list(v), dtype=torch.float32, device=self.device)
+
+    def default_views(self):
+        """{'world': the default camera as a view, 'wrist0': the default wrist view on arm 0's hand[, 'wrist1': on arm 1's]}"""
+        out = {}
+        for which, name in enumerate(("world", "wrist0", "wrist1")):
+            v = (C.c_float * _native.VIEW_FLOATS)()
+            if self._L.xarm_default_view(self._h, which, v) != _native.XARM_OK:
+                if which == 2:
+                    break                                   # a one-arm kind
+                _native.check(self._L, self._h, -1, "xarm_default_view")
+            out[name] = torch.tensor(list(v), dtype=torch.float32, device=self.device)
+        return out
+
+    def _views(self, views, n):
+        """views as render() takes them -> (float32 device tensor [V, 16] or [n, V, 16], per_env)"""
+        if isinstance(views, (list, tuple)):
+            if not views:
+                raise ValueError("views is empty")
+            named = None
+            rows = []
+            for v in views:
+                if isinstance(v, str):
+                    named = named or self.default_views()
+                    if v not in named:
+                        raise ValueError("view %r: this env has %s" % (v, ", ".join(named)))
+                    v = named[v]
+                rows.append(torch.as_tensor(v, dtype=torch.float32).to(self.device))
+            views = torch.stack(rows)
+        t = torch.as_tensor(views, dtype=torch.float32).to(self.device).contiguous()
+        if t.dim() not in (2, 3) or t.shape[-1] != _native.VIEW_FLOATS or (t.dim() == 3 and t.shape[0] != n):
+            raise ValueError("views must be [V, %d] or [n, V, %d] with n = %d, got %s" % (_native.VIEW_FLOATS, _native.VIEW_FLOATS, n, tuple(t.shape)))
+        return t, int(t.dim() == 3)
+
+    def render_views_into(self, views, per_env, width, height, flags, ids, rgba, depth=None, seg=None):
+        """xarm_render_views into caller-owned buffers on the current stream (no allocation, no host sync: graph-capturable; the
+        views are read when the kernel runs, so a captured call follows in-place changes of the tensor).  views: float32 device
+        tensor [V, 16] (per_env 0) or [n, V, 16] (per_env 1, by position in ids); ids: int32 device tensor or None (= envs
+        0 .. n-1); rgba [n, V, height, width(, 4)] int32 / uint8 device memory, depth / seg of the same shape or None"""
+        n, V = rgba.shape[0], views.shape[-2]
+        rc = self._L.xarm_render_views(self._h, _ptr(views), int(V), int(per_env), int(width), int(height), int(flags), _ptr(ids), int(n),
+                                       _ptr(rgba), _ptr(depth), _ptr(seg), self._stream())
+        _native.check(self._L, self._h, rc, "xarm_render_views")
+
+    def _render_views(self, views, width, height, env_ids, flags, depth, segmentation):
+        d = self.default_camera()
+        W, H = int(d["width"] if width is None else width), int(d["height"] if height is None else height)
+        ids = torch.as_tensor([0] if env_ids is None else env_ids, dtype=torch.int32)
+        if ids.dim() != 1 or ids.numel() < 1:
+            raise ValueError("env_ids must be a non-empty 1-D sequence")
+        ids = ids.to(self.device)
+        n = ids.numel()
+        vt, per_env = self._views(views, n)
+        V = vt.shape[-2]
+        rgba = torch.empty(n, V, max(H, 0), max(W, 0), 4, device=self.device, dtype=torch.uint8)
+        dep = torch.empty(n, V, max(H, 0), max(W, 0), device=self.device, dtype=torch.float32) if depth else None
+        seg = torch.empty(n, V, max(H, 0), max(W, 0), device=self.device, dtype=torch.uint8) if segmentation else None
+        self.render_views_into(vt, per_env, W, H, flags, ids, rgba, dep, seg)
+        if not (depth or segmentation):
+            return rgba
+        out = {"rgba": rgba}
+        if depth:
+            out["depth"] = dep
+        if segmentation:
+            out["seg"] = seg
+        return out
+
+    def render(self, mode="rgb_array", width=None, height=None, env_ids=None, camera=None, depth=False, segmentation=False, views=None,
+               shadows=False):
         """Images of the envs env_ids (default [0]) as the last step / reset on the current stream left them: a device
         torch.uint8 [n, H, W, 4] RGBA tensor (the reference's getCameraImage layout), or with depth / segmentation a dict
         {'rgba', 'depth' (float32 [n, H, W], view-axis metres, far for the background), 'seg' (uint8 [n, H, W])}.
         camera: dict of xarm_camera fields overriding default_camera(); width / height override its size.  With auto-reset
-        a finished env shows its new episode; with auto_reset='lazy' its terminal frame until its next step."""
+        a finished env shows its new episode; with auto_reset='lazy' its terminal frame until its next step.
+        views: V views per env in one launch instead of the one camera - a list of names of default_views() and / or [16]
+        rows (view(), view_from_camera()), a [V, 16] tensor shared by the envs or an [n, V, 16] tensor with one set per
+        position in env_ids; the images are then [n, V, H, W, 4] (depth / seg [n, V, H, W]), width / height default to the
+        default camera's and shadows=True sets XARM_RENDER_SHADOWS (a camera carries it in its flags field).  An invalid view
+        record gives the invalid image (rgba 0, depth 0, seg 255), not an error."""
         if mode != "rgb_array":
             raise NotImplementedError("render mode %r: only 'rgb_array' (a window is outside the HIP hot path)" % (mode,))
+        if views is not None:
+            if camera is not None:
+                raise ValueError("camera= and views= exclude each other (view_from_camera(camera) turns a camera into a view)")
+            return self._render_views(views, width, height, env_ids, _native.RENDER_SHADOWS if shadows else 0, depth, segmentation)
+        if shadows:
+            raise ValueError("shadows= goes with views=; a camera takes camera={'flags': RENDER_SHADOWS}")
         cam = self._camera(camera, width, height)
         ids = torch.as_tensor([0] if env_ids is None else env_ids, dtype=torch.int32)
         if ids.dim() != 1 or ids.numel() < 1:

@@ -245,6 +245,46 @@ int xarm_default_camera(const xarm_handle *h, xarm_camera *out);
 int xarm_render(xarm_handle *h, const xarm_camera *cam, const int32_t *env_ids_dev /* NULL = 0..n-1 */, int32_t n,
                 uint32_t *rgba_dev, float *depth_dev /* may be NULL */, uint8_t *seg_dev /* may be NULL */, void *stream);
 
+/* ---- views: link-mounted and per-env cameras, V views per call (k_render_views in xarm_k_render.hip).
+ * A view is XARM_VIEW_FLOATS float32 in DEVICE memory, so that it can differ per env and change between the replays of a
+ * captured graph:
+ *   [0..2] eye, [3..5] target, [6..8] up - in the MOUNT's frame (PyBullet's computeViewMatrix arguments);
+ *   [9] fov_deg (vertical), [10] near_z, [11] far_z, [12] mount, [13..15] ignored.
+ * mount is a small integer stored exactly in the float: XARM_MOUNT_WORLD, or XARM_MOUNT_HAND0 / XARM_MOUNT_HAND1 = the hand
+ * frame of arm 0 / 1 (the link-7 frame the arm's FK ends with: +z points to the fingertips, the fingers slide along y; for
+ * Reach the same link-7 frame under the xArm gripper box).  The camera basis is built in the kernel in float32: world eye /
+ * target / up through the mount frame, f = (target - eye) / |.|, s = f x up / |.|, u = s x f; rays, depth and row order as
+ * xarm_render's.
+ * VALIDITY RULE - the host never sees a record, so it is decided per (env, view) on the device.  A view is valid iff all of:
+ *   floats 0-12 are finite (and so are the world-frame target - eye and up they give);  mount is exactly 0, 1 or 2 and a
+ *   hand mount names an arm the scene has;  0 < fov_deg < 180;  0 < near_z < far_z < 1e30;  |target - eye| > 1e-6;
+ *   |up| > 1e-6;  |f x up / |up|| > 1e-6 (the view direction is not parallel to up).
+ * An invalid view renders the invalid image (rgba 0, depth 0, segmentation 255), exactly as an env id out of range does;
+ * the call still returns XARM_OK and the other (env, view) images are unaffected. */
+#define XARM_VIEW_FLOATS 16
+#define XARM_RENDER_MAX_VIEWS 8
+#define XARM_MOUNT_WORLD 0
+#define XARM_MOUNT_HAND0 1
+#define XARM_MOUNT_HAND1 2
+/* host helpers, both write XARM_VIEW_FLOATS floats of HOST memory.  The world view with the eye / target / up, fov and clip
+ * planes of a camera (its width / height / flags are arguments of the render call instead); XARM_E_INVALID for a camera
+ * xarm_render would refuse on those fields. */
+int xarm_view_from_camera(const xarm_camera *cam, float *view16_host);
+/* which = 0: the env kind's default camera as a world view; 1 / 2: the default wrist view (render_scene.json "views") on
+ * the hand of arm 0 / 1.  XARM_E_INVALID for which outside [0, 2] and for which = 2 on a one-arm kind. */
+int xarm_default_view(const xarm_handle *h, int32_t which, float *view16_host);
+/* xarm_render through num_views views per env in one launch: env env_ids_dev[k] (NULL = env k) through view v lands in
+ * image [k, v] of rgba_dev (uint32 [n, num_views, height, width]) and, when not NULL, depth_dev (float32) / seg_dev (uint8)
+ * of the same shape.  views_dev is float32 [num_views, 16] when per_env == 0 (shared by all envs) and [n, num_views, 16]
+ * when per_env == 1, indexed by the POSITION k in the id list, the order of the output.  flags: XARM_RENDER_SHADOWS.
+ * Stream-ordered, never synchronises the host, one kernel launch, no workspace (safe inside graph capture; the views are
+ * read when the kernel runs), reads the state and writes none of it.  XARM_E_INVALID: views_dev or rgba_dev NULL, num_views
+ * outside [1, XARM_RENDER_MAX_VIEWS], per_env not 0 or 1, width / height outside [1, XARM_RENDER_MAX_DIM], n < 1 or
+ * n > num_envs, unknown flags. */
+int xarm_render_views(xarm_handle *h, const float *views_dev, int32_t num_views, int32_t per_env, int32_t width, int32_t height,
+                      int32_t flags, const int32_t *env_ids_dev /* NULL = 0..n-1 */, int32_t n, uint32_t *rgba_dev,
+                      float *depth_dev /* may be NULL */, uint8_t *seg_dev /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
