@@ -19,12 +19,15 @@ RESET_COOP_LIMIT_DEFAULT = STEP_COOP_LIMIT_DEFAULT = 8192   # include/xarm_hip.h
 
 EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step", "xarm_compute_reward",
            "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
-           "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views"]
+           "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
+           "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample"]
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
 VIEW_FLOATS = 16            # XARM_VIEW_FLOATS: eye 0-2, target 3-5, up 6-8, fov_deg 9, near_z 10, far_z 11, mount 12
 RENDER_MAX_VIEWS = 8        # XARM_RENDER_MAX_VIEWS
 MOUNTS = {"world": 0, "hand0": 1, "hand1": 2}   # XARM_MOUNT_WORLD / _HAND0 / _HAND1
+HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}   # XARM_HER_FUTURE / _FINAL / _EPISODE
+HER_MAX_TRIES = 64          # csrc/xarm_her_core.h XARM_HER_MAX_TRIES
 
 
 class XarmConfig(C.Structure):
@@ -45,6 +48,12 @@ class XarmCamera(C.Structure):
     _fields_ = [("target", C.c_float * 3), ("distance", C.c_float), ("yaw_deg", C.c_float), ("pitch_deg", C.c_float),
                 ("roll_deg", C.c_float), ("fov_deg", C.c_float), ("near_z", C.c_float), ("far_z", C.c_float),
                 ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32)]
+
+
+class XarmHerLayout(C.Structure):
+    """include/xarm_hip.h xarm_her_layout (20 bytes)"""
+    _fields_ = [("num_envs", C.c_int32), ("horizon", C.c_int32), ("obs_dim", C.c_int32), ("goal_dim", C.c_int32),
+                ("act_dim", C.c_int32)]
 
 
 class XarmNativeError(RuntimeError):
@@ -91,6 +100,10 @@ def load(path=None):
     L.xarm_view_from_camera.argtypes = [C.POINTER(XarmCamera), C.POINTER(C.c_float)]
     L.xarm_default_view.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     L.xarm_render_views.argtypes = [vp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, fp, u8p, vp]
+    hl = C.POINTER(XarmHerLayout)
+    L.xarm_her_record_floats.argtypes = [hl]
+    L.xarm_her_add.argtypes = [hl] + [vp] * 14
+    L.xarm_her_sample.argtypes = [hl, vp, vp, vp, vp, C.c_uint64, C.c_int32, C.c_int32, C.c_int32] + [vp] * 14
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

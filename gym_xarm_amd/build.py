@@ -9,10 +9,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libxarm_hip.so")
 # one translation unit per kernel family (the fused kernels take ~30 s each to compile; the units are compiled in parallel)
 UNITS = ["xarm_hip.hip", "xarm_k_pnp.hip", "xarm_k_pnp_coop.hip", "xarm_k_reach.hip", "xarm_k_handover.hip", "xarm_k_handover_coop.hip",
-         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip"]
+         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip"]
 HEADERS = ["xarm_dev.h", "xarm_core.h", "xarm7_pd_model.h", "xarm_reach_core.h", "xarm7_reach_model.h", "xarm_handover_core.h", "xarm_handover2_core.h",
            "xarm_stack_core.h", "xarm_rearrange_core.h", "xarm_coop_core.h", "xarm_reach_coop_core.h", "xarm_handover_coop_core.h", "xarm_render_core.h",
-           "xarm_render_model.h"]
+           "xarm_render_model.h", "xarm_her_core.h"]
 SOURCES = UNITS + HEADERS
 # per-unit extra flags.  Tried and not shipped: "-ffp-contract=on" for xarm_k_pnp.hip / xarm_k_handover.hip (fused multiply-adds
 # only where the source writes them, so that k_step_fast / k_ho_step_fast compute the BITS of k_step / k_ho_step on every env

@@ -29,6 +29,7 @@
 #include <new>
 #include "xarm_dev.h"
 #include "xarm_render_core.h"
+#include "xarm_her_core.h"
 
 using namespace xd;
 
@@ -815,6 +816,53 @@ int xarm_render_views(xarm_handle *h, const float *views_dev, int32_t num_views,
     const int le = xrc_render::launch_render_views(h->kp.state, h->kp.stride, h->kp.num_envs, sc, views_dev, num_views, per_env, width, height,
                                                    flags, env_ids_dev, n, rgba_dev, depth_dev, seg_dev, stream);
     if (le != 0) return fail(h, XARM_E_HIP, "xarm_render_views: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------- HER replay (xarm_k_her.hip)
+int xarm_her_record_floats(const xarm_her_layout *layout) {
+    if (const char *why = xher::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_her_record_floats: %s", why);
+    return xher::make_layout(*layout).R;
+}
+
+int xarm_her_add(const xarm_her_layout *layout, float *ring, int64_t *ep_end, int64_t *ep_first, int64_t *ep_start, int64_t *clock,
+                 const float *obs, const float *next_obs, const float *ag, const float *next_ag, const float *dg, const float *act,
+                 const float *rew, const uint8_t *done_u8, void *stream) {
+    if (const char *why = xher::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_her_add: %s", why);
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!ring || !ep_end || !ep_first || !ep_start || !clock || !obs || !next_obs || !ag || !next_ag || !dg || !act || !rew || !done_u8)
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_her_add: NULL pointer");
+    xher::AddArgs a;
+    a.L = xher::make_layout(*layout);
+    a.ring = ring; a.ep_end = ep_end; a.ep_first = ep_first; a.ep_start = ep_start; a.clock = clock;
+    a.obs = obs; a.next_obs = next_obs; a.ag = ag; a.next_ag = next_ag; a.dg = dg; a.act = act; a.rew = rew; a.done = done_u8;
+    const int le = xher::launch_her_add(a, clock, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_her_add: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int64_t *ep_end, const int64_t *ep_first, int64_t *clock,
+                    uint64_t seed, int32_t strategy, int32_t batch, int32_t n_her, float *out_obs, float *out_next_obs, float *out_ag,
+                    float *out_next_ag, float *out_goal, float *out_act, float *out_rew, uint8_t *out_done_u8, int64_t *out_env_i64,
+                    int64_t *out_time_i64, int64_t *out_goal_time_i64, uint8_t *out_ok_u8, int64_t *fail_count_i64, void *stream) {
+    if (const char *why = xher::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_her_sample: %s", why);
+    if (batch < 0) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_her_sample: batch must be >= 0");
+    if (n_her < 0 || n_her > batch) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_her_sample: n_her must lie in [0, batch]");
+    if (strategy != XARM_HER_FUTURE && strategy != XARM_HER_FINAL && strategy != XARM_HER_EPISODE)
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_her_sample: unknown strategy (XARM_HER_FUTURE, XARM_HER_FINAL or XARM_HER_EPISODE)");
+    if (batch == 0 || layout->num_envs == 0) return XARM_OK;
+    if (!ring || !ep_end || !ep_first || !clock || !out_obs || !out_next_obs || !out_ag || !out_next_ag || !out_goal || !out_act || !out_rew ||
+        !out_done_u8 || !out_env_i64 || !out_time_i64 || !out_goal_time_i64 || !out_ok_u8 || !fail_count_i64)
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_her_sample: NULL pointer");
+    xher::SampleArgs a;
+    a.L = xher::make_layout(*layout);
+    a.ring = ring; a.ep_end = ep_end; a.ep_first = ep_first; a.clock = clock; a.seed = seed;
+    a.strategy = strategy; a.batch = batch; a.n_her = n_her;
+    a.obs = out_obs; a.next_obs = out_next_obs; a.ag = out_ag; a.next_ag = out_next_ag; a.goal = out_goal; a.act = out_act; a.rew = out_rew;
+    a.done = out_done_u8; a.ok = out_ok_u8; a.env = out_env_i64; a.time = out_time_i64; a.goal_time = out_goal_time_i64;
+    a.fail_count = fail_count_i64;
+    const int le = xher::launch_her_sample(a, clock, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_her_sample: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -285,6 +285,53 @@ int xarm_render_views(xarm_handle *h, const float *views_dev, int32_t num_views,
                       int32_t flags, const int32_t *env_ids_dev /* NULL = 0..n-1 */, int32_t n, uint32_t *rgba_dev,
                       float *depth_dev /* may be NULL */, uint8_t *seg_dev /* may be NULL */, void *stream);
 
+/* ---- device-resident hindsight-experience replay (gym_xarm_amd/csrc/xarm_her_core.h, xarm_k_her.hip).
+ * The three calls need no env handle: the buffer is caller-owned DEVICE memory described by an xarm_her_layout, and the
+ * launches go to `stream` on the caller's current device.  Messages of their XARM_E_INVALID go to xarm_last_error(NULL).
+ *   ring      float32 [horizon, num_envs, R], one record per (slot, env):
+ *             obs | next_obs | achieved_goal | next_achieved_goal | desired_goal | action | reward | done,
+ *             R = 2 obs_dim + 3 goal_dim + act_dim + 2 floats
+ *   ep_end    int64 [horizon, num_envs]: absolute time of the last transition of the entry's episode; the caller fills it with
+ *             -1 before the first add (-1 = that episode is still running, or the slot was never written)
+ *   ep_first  int64 [horizon, num_envs]: absolute time of that episode's first transition, written when the episode closes
+ *   ep_start  int64 [num_envs]: absolute time each env's running episode began; zero before the first add
+ *   clock     int64 [2] = {t, sample_calls}, zero before the first add: the add call stores time t and then advances t, the
+ *             sample call draws with sample_calls and then advances it - both on the device, behind the kernel that read
+ *             them, so the replays of a captured graph advance the clock as eager calls do
+ * Neither call allocates, synchronises, or reads device memory from the host; each is two kernel launches. */
+#define XARM_HER_FUTURE 0   /* goal time uniform on [time, episode end]: SB3's 'future' with online sampling */
+#define XARM_HER_FINAL 1    /* goal time = episode end */
+#define XARM_HER_EPISODE 2  /* goal time uniform on the part of the episode that is still in the ring */
+typedef struct xarm_her_layout {
+    int32_t num_envs;
+    int32_t horizon;        /* ring slots, >= 2; at least twice the longest episode for every closed entry to stay reachable */
+    int32_t obs_dim;
+    int32_t goal_dim;
+    int32_t act_dim;
+} xarm_her_layout;          /* 20 bytes */
+/* R, the floats of one record; XARM_E_INVALID for a NULL or unusable layout (dims < 1, horizon < 2, num_envs < 0) */
+int xarm_her_record_floats(const xarm_her_layout *layout);
+/* store one transition per env at slot t mod horizon ([num_envs, dim] float32 rows, rew float32 [num_envs], done uint8
+ * [num_envs]; for a finished env next_obs / next_ag are the TERMINAL ones) and close the episodes of the envs with done set:
+ * O(episode length) writes for those envs only.  num_envs == 0 launches nothing.  XARM_E_INVALID: unusable layout, or a NULL
+ * pointer with num_envs > 0. */
+int xarm_her_add(const xarm_her_layout *layout, float *ring, int64_t *ep_end, int64_t *ep_first, int64_t *ep_start, int64_t *clock,
+                 const float *obs, const float *next_obs, const float *ag, const float *next_ag, const float *dg, const float *act,
+                 const float *rew, const uint8_t *done_u8, void *stream);
+/* draw `batch` rows uniformly from the stored entries of closed episodes (ep_end >= 0) into the [batch, dim] outputs, by
+ * rejection: Philox(seed; row, sample_calls, attempt) proposes one of the min(t, horizon) num_envs stored entries, at most 64
+ * times.  Rows [0, n_her) are relabelled: out_goal = next_achieved_goal of the same env at out_goal_time, chosen by `strategy`
+ * inside the row's episode; the other rows keep the stored desired_goal.  out_rew is the STORED reward in every row: the caller
+ * recomputes rows [0, n_her) with xarm_compute_reward on out_next_ag / out_goal, which are contiguous there.
+ * out_env / out_time / out_goal_time (int64 [batch]) name the entry and the goal's source; out_ok_u8[b] = 0 marks a row whose 64
+ * proposals all failed: its outputs are all zero and *fail_count_i64 (device, never cleared by this call) is incremented.
+ * An empty buffer fails every row.  batch == 0 or num_envs == 0 launches nothing.  XARM_E_INVALID: unusable layout, batch < 0,
+ * n_her outside [0, batch], unknown strategy, or a NULL pointer with batch > 0. */
+int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int64_t *ep_end, const int64_t *ep_first, int64_t *clock,
+                    uint64_t seed, int32_t strategy, int32_t batch, int32_t n_her, float *out_obs, float *out_next_obs, float *out_ag,
+                    float *out_next_ag, float *out_goal, float *out_act, float *out_rew, uint8_t *out_done_u8, int64_t *out_env_i64,
+                    int64_t *out_time_i64, int64_t *out_goal_time_i64, uint8_t *out_ok_u8, int64_t *fail_count_i64, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
