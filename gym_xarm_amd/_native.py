@@ -20,7 +20,8 @@ RESET_COOP_LIMIT_DEFAULT = STEP_COOP_LIMIT_DEFAULT = 8192   # include/xarm_hip.h
 EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step", "xarm_compute_reward",
            "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
-           "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample"]
+           "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
+           "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step"]
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
 VIEW_FLOATS = 16            # XARM_VIEW_FLOATS: eye 0-2, target 3-5, up 6-8, fov_deg 9, near_z 10, far_z 11, mount 12
@@ -28,6 +29,7 @@ RENDER_MAX_VIEWS = 8        # XARM_RENDER_MAX_VIEWS
 MOUNTS = {"world": 0, "hand0": 1, "hand1": 2}   # XARM_MOUNT_WORLD / _HAND0 / _HAND1
 HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}   # XARM_HER_FUTURE / _FINAL / _EPISODE
 HER_MAX_TRIES = 64          # csrc/xarm_her_core.h XARM_HER_MAX_TRIES
+NORM_MAX_DIM = 96           # XARM_NORM_MAX_DIM
 
 
 class XarmConfig(C.Structure):
@@ -54,6 +56,17 @@ class XarmHerLayout(C.Structure):
     """include/xarm_hip.h xarm_her_layout (20 bytes)"""
     _fields_ = [("num_envs", C.c_int32), ("horizon", C.c_int32), ("obs_dim", C.c_int32), ("goal_dim", C.c_int32),
                 ("act_dim", C.c_int32)]
+
+
+class XarmNormLayout(C.Structure):
+    """include/xarm_hip.h xarm_norm_layout (16 bytes)"""
+    _fields_ = [("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("goal_dim", C.c_int32), ("monitor_capacity", C.c_int32)]
+
+
+class XarmNormParams(C.Structure):
+    """include/xarm_hip.h xarm_norm_params (40 bytes)"""
+    _fields_ = [("clip_obs", C.c_double), ("clip_reward", C.c_double), ("eps", C.c_double), ("gamma", C.c_float),
+                ("t_seconds", C.c_float), ("update", C.c_int32)]
 
 
 class XarmNativeError(RuntimeError):
@@ -104,6 +117,10 @@ def load(path=None):
     L.xarm_her_record_floats.argtypes = [hl]
     L.xarm_her_add.argtypes = [hl] + [vp] * 14
     L.xarm_her_sample.argtypes = [hl, vp, vp, vp, vp, C.c_uint64, C.c_int32, C.c_int32, C.c_int32] + [vp] * 14
+    nl, npar = C.POINTER(XarmNormLayout), C.POINTER(XarmNormParams)
+    L.xarm_norm_work_bytes.argtypes = [nl, C.POINTER(C.c_int64)]
+    L.xarm_norm_obs.argtypes = [nl, npar] + [vp] * 6 + [C.c_int32, vp, vp]
+    L.xarm_norm_step.argtypes = [nl, npar] + [vp] * 16
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

@@ -9,10 +9,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libxarm_hip.so")
 # one translation unit per kernel family (the fused kernels take ~30 s each to compile; the units are compiled in parallel)
 UNITS = ["xarm_hip.hip", "xarm_k_pnp.hip", "xarm_k_pnp_coop.hip", "xarm_k_reach.hip", "xarm_k_handover.hip", "xarm_k_handover_coop.hip",
-         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip"]
+         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip"]
 HEADERS = ["xarm_dev.h", "xarm_core.h", "xarm7_pd_model.h", "xarm_reach_core.h", "xarm7_reach_model.h", "xarm_handover_core.h", "xarm_handover2_core.h",
            "xarm_stack_core.h", "xarm_rearrange_core.h", "xarm_coop_core.h", "xarm_reach_coop_core.h", "xarm_handover_coop_core.h", "xarm_render_core.h",
-           "xarm_render_model.h", "xarm_her_core.h"]
+           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h"]
 SOURCES = UNITS + HEADERS
 # per-unit extra flags.  Tried and not shipped: "-ffp-contract=on" for xarm_k_pnp.hip / xarm_k_handover.hip (fused multiply-adds
 # only where the source writes them, so that k_step_fast / k_ho_step_fast compute the BITS of k_step / k_ho_step on every env
@@ -23,7 +23,9 @@ SOURCES = UNITS + HEADERS
 # after an unrelated, bit-exact change to the shared sweep (round 4: the commit-free pair step - old and new source are bit for bit
 # equal on the host and, built with this flag, on the device; in the default build 45 % of the contact envs differed after one
 # step).  With the flag the unit's bits are a function of its source alone.
-UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on"]}
+# "-ffp-contract=off" for the VecNormalize / monitor unit: its float64 statistics are specified operation by operation
+# (csrc/xarm_norm_core.h) and the g++ build of the same header, compiled with the same flag, gives the same bits.
+UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes
 # 1.3 KB/lane into scratch.  Without it the step kernel needs 28 B/lane of scratch and 18 % fewer instructions.

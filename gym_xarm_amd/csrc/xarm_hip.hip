@@ -30,6 +30,7 @@
 #include "xarm_dev.h"
 #include "xarm_render_core.h"
 #include "xarm_her_core.h"
+#include "xarm_norm_core.h"
 
 using namespace xd;
 
@@ -863,6 +864,59 @@ int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int6
     a.fail_count = fail_count_i64;
     const int le = xher::launch_her_sample(a, clock, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_her_sample: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------- VecNormalize + monitor (xarm_k_norm.hip)
+int xarm_norm_work_bytes(const xarm_norm_layout *layout, int64_t *bytes) {
+    if (const char *why = xnorm::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_norm_work_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_norm_work_bytes: NULL pointer");
+    *bytes = xnorm::work_bytes(xnorm::make_layout(*layout));
+    return XARM_OK;
+}
+
+static void norm_args(xnorm::Args &a, const xarm_norm_layout *layout, const xarm_norm_params *p, void *work) {
+    a.L = xnorm::make_layout(*layout);
+    a.clip_obs = p->clip_obs; a.clip_rew = p->clip_reward; a.eps = p->eps; a.gamma = p->gamma; a.t_seconds = p->t_seconds;
+    a.update = p->update != 0;
+    xnorm::carve_work(a, work);
+}
+
+int xarm_norm_obs(const xarm_norm_layout *layout, const xarm_norm_params *params, double *stats, float *ret, void *work,
+                  const float *obs, const float *achieved_goal, const float *desired_goal, int32_t zero_ret, float *out_nobs,
+                  void *stream) {
+    if (const char *why = xnorm::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_norm_obs: %s", why);
+    if (const char *why = xnorm::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_norm_obs: %s", why);
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!stats || !work || !obs || !out_nobs || (layout->goal_dim > 0 && (!achieved_goal || !desired_goal)) || (zero_ret && !ret))
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_norm_obs: NULL pointer");
+    xnorm::Args a = {};
+    norm_args(a, layout, params, work);
+    a.step = 0; a.zero_ret = zero_ret != 0;
+    a.stats = stats; a.ret = ret; a.obs = obs; a.ag = achieved_goal; a.dg = desired_goal; a.nobs = out_nobs;
+    const int le = xnorm::launch_norm(a, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_norm_obs: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_norm_step(const xarm_norm_layout *layout, const xarm_norm_params *params, double *stats, float *ret, float *ep_ret,
+                   float *ep_len, float *ring, int64_t *n_i64, void *work, const float *obs, const float *achieved_goal,
+                   const float *desired_goal, const float *rew, const uint8_t *done_u8, const uint8_t *keep_u8, float *out_nobs,
+                   float *out_nrew, void *stream) {
+    if (const char *why = xnorm::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_norm_step: %s", why);
+    if (const char *why = xnorm::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_norm_step: %s", why);
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!stats || !ret || !ep_ret || !ep_len || !ring || !n_i64 || !work || !obs || !rew || !done_u8 || !out_nobs || !out_nrew ||
+        (layout->goal_dim > 0 && (!achieved_goal || !desired_goal)))
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_norm_step: NULL pointer");
+    xnorm::Args a = {};
+    norm_args(a, layout, params, work);
+    a.step = 1; a.zero_ret = 0;
+    a.stats = stats; a.ret = ret; a.ep_ret = ep_ret; a.ep_len = ep_len; a.ring = ring; a.n = n_i64;
+    a.obs = obs; a.ag = achieved_goal; a.dg = desired_goal; a.rew = rew; a.done = done_u8; a.keep = keep_u8;
+    a.nobs = out_nobs; a.nrew = out_nrew;
+    const int le = xnorm::launch_norm(a, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_norm_step: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

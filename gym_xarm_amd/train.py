@@ -246,19 +246,26 @@ class ActorCritic(nn.Module):
 
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.99, lr=7e-4, seed=0, config=None, log_every=50,
-          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None):
+          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
-    (benchmark/train.py:74,99,107-108).  env: an already built VecEnv (tests)."""
+    (benchmark/train.py:74,99,107-108).  env: an already built VecEnv (tests).
+    device_normalize: normalisation and the Monitor in HIP kernels (gym_xarm_amd/normalize.py DeviceVecNormalize) instead of the
+    torch classes of this file."""
     torch.manual_seed(seed)
     if env is None:
         import gym_xarm_amd
         env = gym_xarm_amd.make(env_id, num_envs=num_envs, seed=seed, config=config, auto_reset=auto_reset)
     num_envs = env.num_envs
-    venv = VecNormalize(env, gamma=gamma)
     dev = env.device
-    monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
+    if device_normalize:
+        from .normalize import DeviceVecNormalize
+        venv = DeviceVecNormalize(env, gamma=gamma, monitor_capacity=max(1 << 20, num_envs), log_dir=log_dir, env_id=env_id)
+        monitor = venv.monitor                    # updated inside venv.step
+    else:
+        venv = VecNormalize(env, gamma=gamma)
+        monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     model = ActorCritic(venv.dim, env.act_dim).to(dev)
     opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
@@ -272,7 +279,8 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
                 a = model.dist(obs).sample()
             nobs, nrew, done, info, raw = venv.step(a.clamp(-1, 1))
             resetting = info["resetting"].float() if "resetting" in info else torch.zeros_like(nrew)
-            monitor.update(raw, done, ~info["resetting"] if "resetting" in info else None)
+            if not device_normalize:
+                monitor.update(raw, done, ~info["resetting"] if "resetting" in info else None)
             if callback is not None:
                 callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (len(obs_buf) + 1) * num_envs)
             obs_buf.append(obs); act_buf.append(a); rew_buf.append(nrew * (1.0 - resetting))
@@ -328,12 +336,13 @@ def main():
     ap.add_argument("--lazy-reset", action="store_true", help="opt-in lazy auto-reset (PickAndPlace), masked in the update")
     ap.add_argument("--log-dir", default=None, help="Monitor CSV, best_model.safetensors (every --check-freq calls), vec_normalize.safetensors")
     ap.add_argument("--check-freq", type=int, default=1000)
+    ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
     args = ap.parse_args()
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
-                              log_dir=args.log_dir, check_freq=args.check_freq)
+                              log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize)
     if args.save:
         save_model(args.save, model, venv)
 

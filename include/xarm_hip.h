@@ -332,6 +332,63 @@ int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int6
                     float *out_next_ag, float *out_goal, float *out_act, float *out_rew, uint8_t *out_done_u8, int64_t *out_env_i64,
                     int64_t *out_time_i64, int64_t *out_goal_time_i64, uint8_t *out_ok_u8, int64_t *fail_count_i64, void *stream);
 
+/* ---- device-resident VecNormalize + episode monitor (gym_xarm_amd/csrc/xarm_norm_core.h, xarm_k_norm.hip):
+ * the running observation / return statistics, the normalised observation and reward and the Monitor's per-env return and length
+ * of gym_xarm_amd/train.py (VecNormalize.step + EpisodeMonitor.update) in one stream-ordered call.  Like the HER calls these
+ * need no env handle: the state is caller-owned DEVICE memory described by an xarm_norm_layout, the launches go to `stream` on
+ * the caller's current device, and the messages of XARM_E_INVALID go to xarm_last_error(NULL).  D = obs_dim + 2 goal_dim.
+ *   stats    double [2 D + 4]: obs_mean[D] | obs_var[D] | ret_mean | ret_var | obs_count | ret_count; before the first call the
+ *            caller sets means 0, variances 1, counts 1e-4.  Every intermediate of the moments and of the normalisation is
+ *            float64; the outputs are rounded to float32 once, after the clamp
+ *   ret      float [num_envs]: running discounted return (zero at the start)
+ *   ep_ret   float [num_envs], ep_len float [num_envs]: return and length of the running episode (zero at the start)
+ *   ring     float [monitor_capacity, 3]: one (r, l, t) row per finished episode, episode k of the run at row k mod capacity
+ *   n        int64 [1]: episodes recorded so far (zero at the start); the call advances it on the device
+ *   work     xarm_norm_work_bytes() bytes, 8-byte aligned, scratch: every call rewrites what it reads, nothing survives a call
+ * The result is a function of the inputs alone: rows are reduced in chunks of 128 in a fixed order, the chunks merged in index
+ * order, no float atomics.  No call allocates, synchronises or reads device memory from the host; a call is three kernel
+ * launches (the observation-only call with update == 0: one), num_envs == 0 launches nothing. */
+#define XARM_NORM_MAX_DIM 96       /* D <= this: a chunk of 128 rows is staged in LDS */
+typedef struct xarm_norm_layout {
+    int32_t num_envs;
+    int32_t obs_dim;
+    int32_t goal_dim;           /* 0: `obs` is the whole row (a flat-observation env), achieved / desired goal are not read */
+    int32_t monitor_capacity;   /* ring rows, >= num_envs: every env can finish in one call and no two rows may share a slot */
+} xarm_norm_layout;             /* 16 bytes */
+typedef struct xarm_norm_params {
+    double clip_obs;            /* > 0 */
+    double clip_reward;         /* > 0 */
+    double eps;                 /* finite, > 0 */
+    float gamma;                /* in [0, 1]; ret = ret * gamma + rew is a float32 multiply, then a float32 add */
+    float t_seconds;            /* the t column of the rows this call appends.  Passed BY VALUE: the replays of a captured graph
+                                 * repeat the value of the capture */
+    int32_t update;             /* 0: the statistics are read, not updated (VecNormalize.training = False) */
+} xarm_norm_params;             /* 40 bytes */
+/* *bytes = size of `work` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (num_envs < 0, obs_dim < 1,
+ * goal_dim < 0, D > XARM_NORM_MAX_DIM, monitor_capacity < max(1, num_envs)) */
+int xarm_norm_work_bytes(const xarm_norm_layout *layout, int64_t *bytes);
+/* the reset path, VecNormalize.reset: if params->update, merge the per-column moments of all num_envs rows into the observation
+ * statistics; out_nobs[num_envs, D] = clamp((row - mean) / sqrt(var + eps), +-clip_obs) with the updated statistics, the row
+ * being obs | achieved_goal | desired_goal ([num_envs, dim] float32 each; the kernels concatenate).  zero_ret != 0 also zeroes
+ * ret.  Return statistics, monitor and n are not touched.  XARM_E_INVALID: unusable layout or params (eps not finite or <= 0,
+ * a clip <= 0, gamma outside [0, 1]), or with num_envs > 0 a NULL stats / work / obs / out_nobs, a NULL achieved_goal /
+ * desired_goal with goal_dim > 0, a NULL ret with zero_ret. */
+int xarm_norm_obs(const xarm_norm_layout *layout, const xarm_norm_params *params, double *stats, float *ret, void *work,
+                  const float *obs, const float *achieved_goal, const float *desired_goal, int32_t zero_ret, float *out_nobs,
+                  void *stream);
+/* one env step's bookkeeping, in VecNormalize.step + EpisodeMonitor.update order: ret = ret * gamma + rew; the moments of the
+ * kept envs' ret merged into (ret_mean, ret_var, ret_count); out_nrew = clamp(rew / sqrt(ret_var + eps), +-clip_reward); ret = 0
+ * where done; the kept rows' moments merged into the observation statistics; out_nobs as in xarm_norm_obs; ep_ret += rew c,
+ * ep_len += c with c = keep as 0 / 1; every env with done_u8 != 0 appends (ep_ret, ep_len, t_seconds) at row (n + rank) mod
+ * monitor_capacity, rank = its position among this call's finished envs in env order, and its ep_ret / ep_len are zeroed;
+ * n += finished envs.  keep_u8 (may be NULL = every env) marks the envs whose row feeds the statistics and the episode sums: under
+ * lazy auto-reset, the envs that are not spending the call on a reset tick.  A call without kept rows leaves stats bit for bit
+ * unchanged, as does update == 0.  XARM_E_INVALID: as xarm_norm_obs, or a NULL pointer other than keep_u8 with num_envs > 0. */
+int xarm_norm_step(const xarm_norm_layout *layout, const xarm_norm_params *params, double *stats, float *ret, float *ep_ret,
+                   float *ep_len, float *ring, int64_t *n_i64, void *work, const float *obs, const float *achieved_goal,
+                   const float *desired_goal, const float *rew, const uint8_t *done_u8, const uint8_t *keep_u8 /* may be NULL */,
+                   float *out_nobs, float *out_nrew, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
