@@ -25,7 +25,12 @@ SOURCES = UNITS + HEADERS
 # step).  With the flag the unit's bits are a function of its source alone.
 # "-ffp-contract=off" for the VecNormalize / monitor unit: its float64 statistics are specified operation by operation
 # (csrc/xarm_norm_core.h) and the g++ build of the same header, compiled with the same flag, gives the same bits.
-UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
+# "-DXC_SWEEP_COPY" for the cooperative Handover unit: xc::sweep_all keeps its one-set form there (csrc/xarm_coop_core.h).  The two-set
+# form is bit for bit the same arithmetic and what the PickAndPlace unit runs, but built into this unit it made an env's result
+# depend on the env that shares its wavefront (tests/test_edge_cases.py::test_an_env_does_not_depend_on_its_batch, Handover, batch
+# 33 against 1 000: reproducible; the one-set build of the same tree passes).  Cause not found - the unit has a history of that kind
+# (the v_permlane32_swap hazard in xarm_k_handover_coop.hip, the contraction note above) - so it keeps the code it had.
+UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes
 # 1.3 KB/lane into scratch.  Without it the step kernel needs 28 B/lane of scratch and 18 % fewer instructions.

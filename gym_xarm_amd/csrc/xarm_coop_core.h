@@ -520,27 +520,35 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
     // and only lane i's entry is ever used: its difference to the new pair is what step i broadcasts.  Keeping the 14 pairs
     // in registers replaces the per-step write of lane i into ONE pair (two v_cndmask_b32 per step: 8 of the 48 cycles of a pair
     // step, tools/probes/commit_probe.hip) by 14 writes after the last sweep - same values, same arithmetic.
-    LV2<T> NL[NA1];
+    // TWO sets, NL[0] and NL[1]: a sweep reads the pairs of the sweep before it from one set and writes its own into the other,
+    // and the loop is unrolled by two so that which set is which is fixed in the code.  With one set (XC_SWEEP_COPY: the form
+    // the host build keeps for comparison and the cooperative Handover unit is built with, build.py) `NL[i] = nl` after `dl = nl - NL[i]` cannot reuse the old pair's registers while dl
+    // is still to be formed, and the compiler pays two v_mov_b32 per pair step - 28 of the 114 instructions of the pad-free
+    // sweep loop.  Same values, same arithmetic, same order.
+#ifdef XC_SWEEP_COPY
+    constexpr int NL_SETS = 1;
+#else
+    constexpr int NL_SETS = 2;
+#endif
+    LV2<T> NL[NL_SETS][NA1];
 #pragma unroll
-    for (int i = 0; i < NA1; i++) NL[i] = lam01;
+    for (int i = 0; i < NA1; i++) NL[0][i] = lam01;
     // which arm-limit rows are live somewhere in the wavefront (usually one joint near one limit): the others are
     // exact no-ops and are skipped, the launch lasts as long as its slowest wavefront
     bool law[NLA];
 #define XC_LAW(i) law[i] = LA && XARM_ANY_X(lv_get<i>(W.invd[3]) != (T)0);
     XC_LAW(0) XC_LAW(1) XC_LAW(2) XC_LAW(3) XC_LAW(4) XC_LAW(5) XC_LAW(6)
 #undef XC_LAW
-#pragma unroll 1
-    for (int it = 0; it < XC_SWEEP_ITERS; it++) {
-        LV<T> lim = lv_fill((T)0);
-        // pair step i: table row i (normal of point i/3 when i % 3 == 0, else friction; none for i >= 12) + slot-1 row i
-#define XC_PAIR(i)                                                                                           \
+    // pair step i: table row i (normal of point i/3 when i % 3 == 0, else friction; none for i >= 12) + slot-1 row i;
+    // RD: the set that holds the pairs of the sweep before, WR: the set this sweep writes
+#define XC_PAIR(i, RD, WR)                                                                                   \
         {                                                                                                    \
             LV<T> nx = lv2_x(c01);                                                                           \
             if ((i) % 3 == 0 || (i) >= NT) nx = lv_max0(nx);                                                 \
             else nx = lv_med3(nx, lv_neg(lim), lim);                                                         \
             const LV2<T> nl = lv2_make(nx, lv_med3(lv2_y(c01), W.lo1, W.hi1));                               \
-            const LV2<T> dl = lv2_sub(nl, NL[i]);                                                            \
-            NL[i] = nl; /* no commit inside the loop: see NL above */                                        \
+            const LV2<T> dl = lv2_sub(nl, NL[RD][i]);                                                        \
+            NL[WR][i] = nl; /* no commit inside the loop: see NL above */                                    \
             if ((i) % 3 == 0 && (i) < NT) lim = lv_mul(lv_bcast<i>(nx), mu_tv); /* friction limit of this point */ \
             const LV2<T> b = lv2_bcast<i>(dl);                                                               \
             c01 = lv2_fma(A01[i], b, c01);                                                                   \
@@ -576,16 +584,36 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
             if (LA) c3 = lv_fma(W.nA3[C1_F + 3 * p + a], b, c3);                                             \
         }
 #define XC_F_PAD(p) if (padw[p]) { XC_F_ROW(p, 0) XC_F_ROW(p, 1) XC_F_ROW(p, 2) }
-        XC_PAIR(0) XC_PAIR(1) XC_PAIR(2) XC_PAIR(3) XC_PAIR(4) XC_PAIR(5) XC_PAIR(6) XC_PAIR(7) XC_PAIR(8)
-        if (LA) { XC_L_ROW(0) XC_L_ROW(1) XC_L_ROW(2) XC_L_ROW(3) XC_L_ROW(4) XC_L_ROW(5) XC_L_ROW(6) }
-        XC_PAIR(9) XC_PAIR(10) XC_PAIR(11) XC_PAIR(12) XC_PAIR(13)
-        if (PAD) { XC_F_PAD(0) XC_F_PAD(1) XC_F_PAD(2) XC_F_PAD(3) }
+    // one sweep over every row
+#define XC_SWEEP(RD, WR)                                                                                     \
+    {                                                                                                        \
+        LV<T> lim = lv_fill((T)0);                                                                           \
+        XC_PAIR(0, RD, WR) XC_PAIR(1, RD, WR) XC_PAIR(2, RD, WR) XC_PAIR(3, RD, WR) XC_PAIR(4, RD, WR)       \
+        XC_PAIR(5, RD, WR) XC_PAIR(6, RD, WR) XC_PAIR(7, RD, WR) XC_PAIR(8, RD, WR)                          \
+        if (LA) { XC_L_ROW(0) XC_L_ROW(1) XC_L_ROW(2) XC_L_ROW(3) XC_L_ROW(4) XC_L_ROW(5) XC_L_ROW(6) }      \
+        XC_PAIR(9, RD, WR) XC_PAIR(10, RD, WR) XC_PAIR(11, RD, WR) XC_PAIR(12, RD, WR) XC_PAIR(13, RD, WR)   \
+        if (PAD) { XC_F_PAD(0) XC_F_PAD(1) XC_F_PAD(2) XC_F_PAD(3) }                                         \
+    }
+    constexpr int NSW = XC_SWEEP_ITERS;
+#ifdef XC_SWEEP_COPY
+    constexpr int LAST = 0;
+#pragma unroll 1
+    for (int it = 0; it < NSW; it++) XC_SWEEP(0, 0)
+#else
+    constexpr int LAST = NSW & 1;   // the set the last sweep wrote
+#pragma unroll 1
+    for (int it = 0; it + 1 < NSW; it += 2) {
+        XC_SWEEP(0, 1)
+        XC_SWEEP(1, 0)
+    }
+    if (NSW & 1) XC_SWEEP(0, 1)     // an odd sweep count (the timing variants)
+#endif
+#undef XC_SWEEP
 #undef XC_PAIR
 #undef XC_L_ROW
 #undef XC_F_ROW
 #undef XC_F_PAD
-    }
-#define XC_KEEP(i) lv2_commit<i>(G, lam01, NL[i]);
+#define XC_KEEP(i) lv2_commit<i>(G, lam01, NL[LAST][i]);
     XC_KEEP(0) XC_KEEP(1) XC_KEEP(2) XC_KEEP(3) XC_KEEP(4) XC_KEEP(5) XC_KEEP(6) XC_KEEP(7) XC_KEEP(8) XC_KEEP(9)
     XC_KEEP(10) XC_KEEP(11) XC_KEEP(12) XC_KEEP(13)
 #undef XC_KEEP
