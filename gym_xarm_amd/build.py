@@ -30,7 +30,10 @@ SOURCES = UNITS + HEADERS
 # depend on the env that shares its wavefront (tests/test_edge_cases.py::test_an_env_does_not_depend_on_its_batch, Handover, batch
 # 33 against 1 000: reproducible; the one-set build of the same tree passes).  Cause not found - the unit has a history of that kind
 # (the v_permlane32_swap hazard in xarm_k_handover_coop.hip, the contraction note above) - so it keeps the code it had.
-UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
+# "-DXC_PAD_ROWS_V1" for the same unit and for the same reason: the pad rows of xc::sweep_all keep their first form there (friction limit
+# read back from the committed impulse, a commit per pad row, one loop with a test per pad); with both macros the unit's gfx950 assembly is
+# instruction for instruction what it was before the product forms existed (profiles/r06a_pnp_pad_rows.txt).
+UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY", "-DXC_PAD_ROWS_V1"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes
 # 1.3 KB/lane into scratch.  Without it the step kernel needs 28 B/lane of scratch and 18 % fewer instructions.

@@ -456,6 +456,13 @@ XARM_HD void pad_columns(const Grp &G, const Setup<T> &S, const LV<T> (&J)[R_G],
 // G (gear), F (pad points).  The table rows never couple to the single-joint rows (A is block diagonal there; only
 // the pad rows touch both), so table row i and single-joint row i - both owned by lane i - are advanced in one PAIR
 // step on packed registers: same arithmetic per row, same order within each block, 14 steps instead of 26.
+// XC_ROW_CENSUS(pad, la, padw, law): host-only counting hook, one call per substep with the row set the sweep runs
+// (tools/row_census.py builds tests/hostbuild/xarm_row_census.cpp with it); nothing in every other build.
+#ifndef XC_ROW_CENSUS
+#define XC_ROW_CENSUS(pad, la, padw, law)
+#elif !defined(XARM_HOST_BUILD)
+#error "XC_ROW_CENSUS is a host-build hook"
+#endif
 #if defined(XC_SWEEP_ITERS) && !defined(XARM_SWEEP_VARIANT)
 #define XARM_SWEEP_VARIANT XC_SWEEP_ITERS      // xarm_version() reports it (xarm_hip.hip)
 #endif
@@ -484,6 +491,17 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
 #pragma unroll
         for (int i = 0; i < 7; i++) AL1[i] = lv_mul(W.nA1[C1_L + i], W.invd[1]);
     }
+    // XC_PAD_ROWS_V1 keeps the first form of the pad rows (the form the host build keeps for comparison and the cooperative Handover
+    // unit is built with, build.py).  The product form differs in two places, same values, same arithmetic, same order of every sum:
+    //  the friction limit of a pad comes from the FRESH normal impulse of its normal row (XC_F_ROW below);
+    //  FCF - where pad rows are the only extra rows (what the slowest wavefront of a reset or a hand-off runs, DESIGN.md 5: the
+    //        row-set census) the pad rows go commit-free as the pair steps did (NLF below), and a wavefront in which all four
+    //        pads are live - half to two thirds of the pad-carrying substeps - takes a sweep loop without the per-pad branches.
+#ifdef XC_PAD_ROWS_V1
+    constexpr bool FRESH_FLIM = false, FCF = false;
+#else
+    constexpr bool FRESH_FLIM = true, FCF = PAD && !LA;
+#endif
     LV<T> c2 = lv_fill((T)0), c3 = lv_fill((T)0);
     if (PAD) {
         c2 = lv_fma(W.g[2], W.invd[2], W.lam[2]);
@@ -533,12 +551,20 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
     LV2<T> NL[NL_SETS][NA1];
 #pragma unroll
     for (int i = 0; i < NA1; i++) NL[0][i] = lam01;
+    // NLF[r]: the same for pad row r where the pad rows are commit-free (FCF): lane r of NLF[.][r] is the impulse row r last took,
+    // what W.lam[2] holds on that lane in the committing form; W.lam[2] is written once, after the last sweep
+    LV<T> NLF[NL_SETS][NF];
+    if (FCF) {
+#pragma unroll
+        for (int r = 0; r < NF; r++) NLF[0][r] = W.lam[2];
+    }
     // which arm-limit rows are live somewhere in the wavefront (usually one joint near one limit): the others are
     // exact no-ops and are skipped, the launch lasts as long as its slowest wavefront
     bool law[NLA];
 #define XC_LAW(i) law[i] = LA && XARM_ANY_X(lv_get<i>(W.invd[3]) != (T)0);
     XC_LAW(0) XC_LAW(1) XC_LAW(2) XC_LAW(3) XC_LAW(4) XC_LAW(5) XC_LAW(6)
 #undef XC_LAW
+    XC_ROW_CENSUS(PAD, LA, padw, law)
     // pair step i: table row i (normal of point i/3 when i % 3 == 0, else friction; none for i >= 12) + slot-1 row i;
     // RD: the set that holds the pairs of the sweep before, WR: the set this sweep writes
 #define XC_PAIR(i, RD, WR)                                                                                   \
@@ -568,46 +594,57 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
             if (PAD) c2 = lv_fma(W.nA2[C2_L + i], b, c2);                                                    \
             c3 = lv_fma(W.nA3[C1_L + i], b, c3);                                                             \
         }
-#define XC_F_ROW(p, a)                                                                                       \
+    // pad row (p, a).  The friction rows clamp to mu_p times the normal impulse of their pad.  First form: both friction rows
+    // broadcast it from W.lam[2], behind the commit of the normal row.  Product form: the normal row broadcasts its fresh nl once
+    // (as the table rows form lim) - lane 3p of nl is what the commit writes and nothing else writes that lane before the pad's
+    // friction rows, so flim is the same value; the commit comes off the chain and one broadcast and one product per pad go.
+#define XC_F_ROW(p, a, RD, WR)                                                                               \
         {                                                                                                    \
             LV<T> nl;                                                                                        \
-            if ((a) == 0) nl = lv_max0(c2);                                                                  \
-            else {                                                                                           \
-                const LV<T> flim = lv_mul(lv_bcast<3 * p>(W.lam[2]), mu_pv);                                 \
+            if ((a) == 0) {                                                                                  \
+                nl = lv_max0(c2);                                                                            \
+                if (FRESH_FLIM) flim = lv_mul(lv_bcast<3 * p>(nl), mu_pv);                                   \
+            } else {                                                                                         \
+                if (!FRESH_FLIM) flim = lv_mul(lv_bcast<3 * p>(W.lam[2]), mu_pv);                            \
                 nl = lv_med3(c2, lv_neg(flim), flim);                                                        \
             }                                                                                                \
-            const LV<T> dl = lv_sub(nl, W.lam[2]);                                                           \
-            lv_commit<3 * p + a>(G, W.lam[2], nl);                                                           \
+            const LV<T> dl = lv_sub(nl, FCF ? NLF[RD][3 * p + a] : W.lam[2]);                                \
+            if (FCF) NLF[WR][3 * p + a] = nl;                                                                \
+            else lv_commit<3 * p + a>(G, W.lam[2], nl);                                                      \
             const LV<T> b = lv_bcast<3 * p + a>(dl);                                                         \
             c01 = lv2_fma(AF01[3 * p + a], lv2_make(b, b), c01);                                             \
             c2 = lv_fma(W.nA2[C2_F + 3 * p + a], b, c2);                                                     \
             if (LA) c3 = lv_fma(W.nA3[C1_F + 3 * p + a], b, c3);                                             \
         }
-#define XC_F_PAD(p) if (padw[p]) { XC_F_ROW(p, 0) XC_F_ROW(p, 1) XC_F_ROW(p, 2) }
-    // one sweep over every row
-#define XC_SWEEP(RD, WR)                                                                                     \
+#define XC_F_PAD(p, RD, WR, ALLP) if (ALLP || padw[p]) { LV<T> flim = lv_fill((T)0); XC_F_ROW(p, 0, RD, WR) XC_F_ROW(p, 1, RD, WR) XC_F_ROW(p, 2, RD, WR) }
+    // one sweep over every row; ALLP: all four pads are live, no test per pad
+#define XC_SWEEP(RD, WR, ALLP)                                                                               \
     {                                                                                                        \
         LV<T> lim = lv_fill((T)0);                                                                           \
         XC_PAIR(0, RD, WR) XC_PAIR(1, RD, WR) XC_PAIR(2, RD, WR) XC_PAIR(3, RD, WR) XC_PAIR(4, RD, WR)       \
         XC_PAIR(5, RD, WR) XC_PAIR(6, RD, WR) XC_PAIR(7, RD, WR) XC_PAIR(8, RD, WR)                          \
         if (LA) { XC_L_ROW(0) XC_L_ROW(1) XC_L_ROW(2) XC_L_ROW(3) XC_L_ROW(4) XC_L_ROW(5) XC_L_ROW(6) }      \
         XC_PAIR(9, RD, WR) XC_PAIR(10, RD, WR) XC_PAIR(11, RD, WR) XC_PAIR(12, RD, WR) XC_PAIR(13, RD, WR)   \
-        if (PAD) { XC_F_PAD(0) XC_F_PAD(1) XC_F_PAD(2) XC_F_PAD(3) }                                         \
+        if (PAD) { XC_F_PAD(0, RD, WR, ALLP) XC_F_PAD(1, RD, WR, ALLP) XC_F_PAD(2, RD, WR, ALLP) XC_F_PAD(3, RD, WR, ALLP) } \
     }
     constexpr int NSW = XC_SWEEP_ITERS;
 #ifdef XC_SWEEP_COPY
     constexpr int LAST = 0;
-#pragma unroll 1
-    for (int it = 0; it < NSW; it++) XC_SWEEP(0, 0)
+#define XC_LOOP(ALLP)                                                                                        \
+    _Pragma("unroll 1") for (int it = 0; it < NSW; it++) XC_SWEEP(0, 0, ALLP)
 #else
     constexpr int LAST = NSW & 1;   // the set the last sweep wrote
-#pragma unroll 1
-    for (int it = 0; it + 1 < NSW; it += 2) {
-        XC_SWEEP(0, 1)
-        XC_SWEEP(1, 0)
-    }
-    if (NSW & 1) XC_SWEEP(0, 1)     // an odd sweep count (the timing variants)
+#define XC_LOOP(ALLP)                                                                                        \
+    _Pragma("unroll 1") for (int it = 0; it + 1 < NSW; it += 2) {                                            \
+        XC_SWEEP(0, 1, ALLP)                                                                                 \
+        XC_SWEEP(1, 0, ALLP)                                                                                 \
+    }                                                                                                        \
+    if (NSW & 1) XC_SWEEP(0, 1, ALLP)     /* an odd sweep count (the timing variants) */
 #endif
+    // padw[] is wave-uniform and fixed for the sweeps: the loop is chosen once per substep
+    if (FCF && padw[0] && padw[1] && padw[2] && padw[3]) { XC_LOOP(true) }
+    else { XC_LOOP(false) }
+#undef XC_LOOP
 #undef XC_SWEEP
 #undef XC_PAIR
 #undef XC_L_ROW
@@ -617,6 +654,12 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
     XC_KEEP(0) XC_KEEP(1) XC_KEEP(2) XC_KEEP(3) XC_KEEP(4) XC_KEEP(5) XC_KEEP(6) XC_KEEP(7) XC_KEEP(8) XC_KEEP(9)
     XC_KEEP(10) XC_KEEP(11) XC_KEEP(12) XC_KEEP(13)
 #undef XC_KEEP
+    if (FCF) {
+#define XC_KEEPF(r) if (padw[(r) / 3]) lv_commit<r>(G, W.lam[2], NLF[LAST][r]);
+        XC_KEEPF(0) XC_KEEPF(1) XC_KEEPF(2) XC_KEEPF(3) XC_KEEPF(4) XC_KEEPF(5) XC_KEEPF(6) XC_KEEPF(7) XC_KEEPF(8) XC_KEEPF(9)
+        XC_KEEPF(10) XC_KEEPF(11)
+#undef XC_KEEPF
+    }
     W.lam[0] = lv2_x(lam01);
     W.lam[1] = lv2_y(lam01);
 }
