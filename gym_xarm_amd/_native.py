@@ -21,7 +21,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
-           "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step"]
+           "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
+           "xarm_policy_act"]
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
 VIEW_FLOATS = 16            # XARM_VIEW_FLOATS: eye 0-2, target 3-5, up 6-8, fov_deg 9, near_z 10, far_z 11, mount 12
@@ -30,6 +31,9 @@ MOUNTS = {"world": 0, "hand0": 1, "hand1": 2}   # XARM_MOUNT_WORLD / _HAND0 / _H
 HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}   # XARM_HER_FUTURE / _FINAL / _EPISODE
 HER_MAX_TRIES = 64          # csrc/xarm_her_core.h XARM_HER_MAX_TRIES
 NORM_MAX_DIM = 96           # XARM_NORM_MAX_DIM
+POLICY_MAX_DIM = 96         # XARM_POLICY_MAX_DIM
+POLICY_MAX_ACT = 16         # XARM_POLICY_MAX_ACT
+POLICY_HIDDEN = 64          # XARM_POLICY_HIDDEN
 
 
 class XarmConfig(C.Structure):
@@ -67,6 +71,25 @@ class XarmNormParams(C.Structure):
     """include/xarm_hip.h xarm_norm_params (40 bytes)"""
     _fields_ = [("clip_obs", C.c_double), ("clip_reward", C.c_double), ("eps", C.c_double), ("gamma", C.c_float),
                 ("t_seconds", C.c_float), ("update", C.c_int32)]
+
+
+class XarmPolicyLayout(C.Structure):
+    """include/xarm_hip.h xarm_policy_layout (32 bytes)"""
+    _fields_ = [("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("goal_dim", C.c_int32), ("act_dim", C.c_int32),
+                ("hidden", C.c_int32), ("row_offset", C.c_int64)]
+
+
+class XarmPolicyParams(C.Structure):
+    """include/xarm_hip.h xarm_policy_params (32 bytes)"""
+    _fields_ = [("seed", C.c_uint64), ("clip_obs", C.c_double), ("eps", C.c_double), ("deterministic", C.c_int32)]
+
+
+POLICY_WEIGHT_FIELDS = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_w3", "vf_b3", "log_std")
+
+
+class XarmPolicyWeights(C.Structure):
+    """include/xarm_hip.h xarm_policy_weights (13 device pointers)"""
+    _fields_ = [(k, C.c_void_p) for k in POLICY_WEIGHT_FIELDS]
 
 
 class XarmNativeError(RuntimeError):
@@ -121,6 +144,7 @@ def load(path=None):
     L.xarm_norm_work_bytes.argtypes = [nl, C.POINTER(C.c_int64)]
     L.xarm_norm_obs.argtypes = [nl, npar] + [vp] * 6 + [C.c_int32, vp, vp]
     L.xarm_norm_step.argtypes = [nl, npar] + [vp] * 16
+    L.xarm_policy_act.argtypes = [C.POINTER(XarmPolicyLayout), C.POINTER(XarmPolicyParams), C.POINTER(XarmPolicyWeights)] + [vp] * 10
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

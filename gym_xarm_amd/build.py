@@ -9,10 +9,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libxarm_hip.so")
 # one translation unit per kernel family (the fused kernels take ~30 s each to compile; the units are compiled in parallel)
 UNITS = ["xarm_hip.hip", "xarm_k_pnp.hip", "xarm_k_pnp_coop.hip", "xarm_k_reach.hip", "xarm_k_handover.hip", "xarm_k_handover_coop.hip",
-         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip"]
+         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip", "xarm_k_policy.hip"]
 HEADERS = ["xarm_dev.h", "xarm_core.h", "xarm7_pd_model.h", "xarm_reach_core.h", "xarm7_reach_model.h", "xarm_handover_core.h", "xarm_handover2_core.h",
            "xarm_stack_core.h", "xarm_rearrange_core.h", "xarm_coop_core.h", "xarm_reach_coop_core.h", "xarm_handover_coop_core.h", "xarm_render_core.h",
-           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h"]
+           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h", "xarm_policy_core.h"]
 SOURCES = UNITS + HEADERS
 # per-unit extra flags.  Tried and not shipped: "-ffp-contract=on" for xarm_k_pnp.hip / xarm_k_handover.hip (fused multiply-adds
 # only where the source writes them, so that k_step_fast / k_ho_step_fast compute the BITS of k_step / k_ho_step on every env
@@ -25,6 +25,8 @@ SOURCES = UNITS + HEADERS
 # step).  With the flag the unit's bits are a function of its source alone.
 # "-ffp-contract=off" for the VecNormalize / monitor unit: its float64 statistics are specified operation by operation
 # (csrc/xarm_norm_core.h) and the g++ build of the same header, compiled with the same flag, gives the same bits.
+# "-ffp-contract=off" for the MlpPolicy unit as well (csrc/xarm_policy_core.h): its float32 chains and elementary functions are
+# spelled out operation by operation, and the MFMA it runs on is itself an fmaf chain.
 # "-DXC_SWEEP_COPY" for the cooperative Handover unit: xc::sweep_all keeps its one-set form there (csrc/xarm_coop_core.h).  The two-set
 # form is bit for bit the same arithmetic and what the PickAndPlace unit runs, but built into this unit it made an env's result
 # depend on the env that shares its wavefront (tests/test_edge_cases.py::test_an_env_does_not_depend_on_its_batch, Handover, batch
@@ -33,7 +35,8 @@ SOURCES = UNITS + HEADERS
 # "-DXC_PAD_ROWS_V1" for the same unit and for the same reason: the pad rows of xc::sweep_all keep their first form there (friction limit
 # read back from the committed impulse, a commit per pad row, one loop with a test per pad); with both macros the unit's gfx950 assembly is
 # instruction for instruction what it was before the product forms existed (profiles/r06a_pnp_pad_rows.txt).
-UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY", "-DXC_PAD_ROWS_V1"], "xarm_k_norm.hip": ["-ffp-contract=off"]}
+UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY", "-DXC_PAD_ROWS_V1"], "xarm_k_norm.hip": ["-ffp-contract=off"],
+              "xarm_k_policy.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes
 # 1.3 KB/lane into scratch.  Without it the step kernel needs 28 B/lane of scratch and 18 % fewer instructions.

@@ -31,6 +31,7 @@
 #include "xarm_render_core.h"
 #include "xarm_her_core.h"
 #include "xarm_norm_core.h"
+#include "xarm_policy_core.h"
 
 using namespace xd;
 
@@ -917,6 +918,26 @@ int xarm_norm_step(const xarm_norm_layout *layout, const xarm_norm_params *param
     a.nobs = out_nobs; a.nrew = out_nrew;
     const int le = xnorm::launch_norm(a, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_norm_step: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ MlpPolicy (xarm_k_policy.hip)
+int xarm_policy_act(const xarm_policy_layout *layout, const xarm_policy_params *params, const xarm_policy_weights *weights,
+                    const double *stats, int64_t *calls_i64, const float *obs, const float *achieved_goal, const float *desired_goal,
+                    float *out_action, float *out_env_action, float *out_logp, float *out_value, void *stream) {
+    if (const char *why = xpol::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_policy_act: %s", why);
+    if (const char *why = xpol::params_error(params, stats != nullptr)) return fail(nullptr, XARM_E_INVALID, "xarm_policy_act: %s", why);
+    if (!weights) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_policy_act: weights is NULL");
+    if (layout->num_envs == 0) return XARM_OK;
+    if (const char *why = xpol::pointer_error(layout, params, weights, calls_i64, obs, achieved_goal, desired_goal, out_action, out_env_action,
+                                              out_value))
+        return fail(nullptr, XARM_E_INVALID, "xarm_policy_act: %s", why);
+    xpol::Args a = {};
+    xpol::fill_args(a, layout, params, weights);
+    a.stats = stats; a.calls = calls_i64; a.x0 = obs; a.x1 = achieved_goal; a.x2 = desired_goal;
+    a.action = out_action; a.env_action = out_env_action; a.logp = out_logp; a.value = out_value;
+    const int le = xpol::launch_policy(a, calls_i64, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_policy_act: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -246,13 +246,16 @@ class ActorCritic(nn.Module):
 
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.99, lr=7e-4, seed=0, config=None, log_every=50,
-          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False):
+          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
     (benchmark/train.py:74,99,107-108).  env: an already built VecEnv (tests).
     device_normalize: normalisation and the Monitor in HIP kernels (gym_xarm_amd/normalize.py DeviceVecNormalize) instead of the
-    torch classes of this file."""
+    torch classes of this file.
+    device_policy: the rollout's sample and clamp in one HIP launch (gym_xarm_amd/device_policy.py DevicePolicy) instead of
+    `model.dist(obs).sample().clamp(-1, 1)`; the update is unchanged and recomputes log-probabilities and values with autograd
+    from the stored actions."""
     torch.manual_seed(seed)
     if env is None:
         import gym_xarm_amd
@@ -269,15 +272,25 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     model = ActorCritic(venv.dim, env.act_dim).to(dev)
     opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
+    if device_policy:
+        from .device_policy import DevicePolicy
+        policy = DevicePolicy(model, seed=seed, row_offset=int(getattr(env, "_env_id_offset", 0)))
     obs = venv.reset()
     hist, t0 = [], time.perf_counter()
     succ_sum, done_sum, raw_sum = torch.zeros((), device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)
     for it in range(1, updates + 1):
         obs_buf, act_buf, rew_buf, done_buf, use_buf = [], [], [], [], []
         for _ in range(n_steps):
-            with torch.no_grad():
-                a = model.dist(obs).sample()
-            nobs, nrew, done, info, raw = venv.step(a.clamp(-1, 1))
+            if device_policy:
+                # fresh tensors every step: the buffers below keep `a`, and the update reads it
+                out = policy.act_into({"action": torch.empty(num_envs, env.act_dim, device=dev),
+                                       "env_action": torch.empty(num_envs, env.act_dim, device=dev)}, obs)
+                a, a_env = out["action"], out["env_action"]
+            else:
+                with torch.no_grad():
+                    a = model.dist(obs).sample()
+                a_env = a.clamp(-1, 1)
+            nobs, nrew, done, info, raw = venv.step(a_env)
             resetting = info["resetting"].float() if "resetting" in info else torch.zeros_like(nrew)
             if not device_normalize:
                 monitor.update(raw, done, ~info["resetting"] if "resetting" in info else None)
@@ -337,12 +350,14 @@ def main():
     ap.add_argument("--log-dir", default=None, help="Monitor CSV, best_model.safetensors (every --check-freq calls), vec_normalize.safetensors")
     ap.add_argument("--check-freq", type=int, default=1000)
     ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
+    ap.add_argument("--device-policy", action="store_true", help="the rollout's sample + clamp in one HIP launch (gym_xarm_amd/device_policy.py)")
     args = ap.parse_args()
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
-                              log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize)
+                              log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
+                              device_policy=args.device_policy)
     if args.save:
         save_model(args.save, model, venv)
 

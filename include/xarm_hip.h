@@ -389,6 +389,58 @@ int xarm_norm_step(const xarm_norm_layout *layout, const xarm_norm_params *param
                    const float *desired_goal, const float *rew, const uint8_t *done_u8, const uint8_t *keep_u8 /* may be NULL */,
                    float *out_nobs, float *out_nrew, void *stream);
 
+/* ---- device-resident MlpPolicy (gym_xarm_amd/csrc/xarm_policy_core.h, xarm_k_policy.hip): the forward of
+ * gym_xarm_amd/train.py's ActorCritic - two 64-64 tanh towers and a state-independent log_std - with the Gaussian sample, the
+ * clamp to [-1, 1], the log-probability and the value, in ONE kernel launch per call (a stochastic call is followed by a
+ * one-thread launch that advances `calls`).  Like the normaliser calls it needs no env handle; everything is caller-owned DEVICE
+ * memory, the launches go to `stream` on the caller's current device, and the messages of XARM_E_INVALID go to
+ * xarm_last_error(NULL).  D = obs_dim + 2 goal_dim.
+ *   weights  the 13 float32 parameter tensors, W in [out, in] row-major layout (torch.nn.Linear): W1 [64, D], b1 [64], W2 [64, 64],
+ *            b2 [64], W3 [act_dim, 64] (value tower: [1, 64]), b3, and log_std [act_dim].  They are read in place on every call;
+ *            b1, W2, b2 and W3 must be 16-byte aligned (they are read in 16-byte pieces).
+ *   stats    NULL, or the normaliser's double [2 D + 4]: the row is then normalised inline with these FROZEN statistics -
+ *            clamp((x - mean) / sqrt(var + eps), +-clip_obs) in float64, rounded to float32 once - and never updated
+ *   calls    int64 [1], zero at the start: the noise of a stochastic call is keyed by (seed, row_offset + row, *calls, column
+ *            block); the call advances it on the device behind the kernel that read it, so the replays of a captured graph draw
+ *            fresh noise.  A deterministic call neither reads nor advances it.
+ *   outputs  out_action [num_envs, act_dim] = mean + exp(log_std) z (mean when deterministic), out_env_action = out_action clamped
+ *            to [-1, 1], out_logp [num_envs] (may be NULL) = sum over columns of -z^2 / 2 - log_std - log(2 pi) / 2, out_value
+ *            [num_envs] (may be NULL: the value tower is then skipped)
+ * Every dot product is a float32 fused-multiply-add chain from the bias in a fixed order, the elementary functions are spelled
+ * out in float32 operations: a row's result depends on that row, the weights, seed, row_offset + row and *calls alone - not on the
+ * batch it is in.  No call allocates, synchronises or reads device memory from the host; num_envs == 0 launches nothing. */
+#define XARM_POLICY_MAX_DIM 96     /* D <= this */
+#define XARM_POLICY_MAX_ACT 16     /* 1 <= act_dim <= this */
+#define XARM_POLICY_HIDDEN 64      /* the only hidden width */
+typedef struct xarm_policy_layout {
+    int32_t num_envs;
+    int32_t obs_dim;
+    int32_t goal_dim;           /* 0: `obs` is the whole row, achieved / desired goal are not read */
+    int32_t act_dim;
+    int32_t hidden;             /* XARM_POLICY_HIDDEN */
+    int64_t row_offset;         /* global index of row 0 (>= 0): a shard of a larger batch draws the noise of its global rows */
+} xarm_policy_layout;           /* 32 bytes (4 bytes of padding before row_offset) */
+typedef struct xarm_policy_params {
+    uint64_t seed;
+    double clip_obs;            /* > 0; read with stats only */
+    double eps;                 /* finite, > 0; read with stats only */
+    int32_t deterministic;      /* != 0: action = mean, no noise is drawn, calls is not advanced */
+} xarm_policy_params;           /* 32 bytes */
+typedef struct xarm_policy_weights {
+    const float *pi_w1, *pi_b1, *pi_w2, *pi_b2, *pi_w3, *pi_b3;
+    const float *vf_w1, *vf_b1, *vf_w2, *vf_b2, *vf_w3, *vf_b3;   /* read only when out_value is set */
+    const float *log_std;
+} xarm_policy_weights;          /* 13 device pointers */
+/* XARM_E_INVALID: NULL layout / params / weights, num_envs < 0, obs_dim < 1, goal_dim < 0, D > XARM_POLICY_MAX_DIM, act_dim outside
+ * [1, XARM_POLICY_MAX_ACT], hidden != XARM_POLICY_HIDDEN, row_offset < 0, with stats an eps that is not finite and > 0 or a
+ * clip_obs <= 0, or with num_envs > 0 a NULL policy weight, log_std, obs, out_action or out_env_action, a NULL achieved_goal /
+ * desired_goal with goal_dim > 0, a NULL value weight with out_value set, a misaligned b1 / W2 / b2 / W3, a NULL calls with
+ * deterministic == 0. */
+int xarm_policy_act(const xarm_policy_layout *layout, const xarm_policy_params *params, const xarm_policy_weights *weights,
+                    const double *stats /* may be NULL */, int64_t *calls_i64, const float *obs, const float *achieved_goal,
+                    const float *desired_goal, float *out_action, float *out_env_action, float *out_logp /* may be NULL */,
+                    float *out_value /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
