@@ -35,7 +35,10 @@ SOURCES = UNITS + HEADERS
 # "-DXC_PAD_ROWS_V1" for the same unit and for the same reason: the pad rows of xc::sweep_all keep their first form there (friction limit
 # read back from the committed impulse, a commit per pad row, one loop with a test per pad); with both macros the unit's gfx950 assembly is
 # instruction for instruction what it was before the product forms existed (profiles/r06a_pnp_pad_rows.txt).
-UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY", "-DXC_PAD_ROWS_V1"], "xarm_k_norm.hip": ["-ffp-contract=off"],
+# "-DXC_PAD_SETUP_V1" likewise: the per-substep pad setup (xc::pad_columns, the column scaling at the head of xc::sweep_all) keeps its first form
+# in this unit - a broadcast per operand, a division per pad row, the columns scaled in sweep_all; with the three macros the unit's assembly is
+# still the parent's, instruction for instruction (profiles/r07a_pnp_pad_setup.txt).
+UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY", "-DXC_PAD_ROWS_V1", "-DXC_PAD_SETUP_V1"], "xarm_k_norm.hip": ["-ffp-contract=off"],
               "xarm_k_policy.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes

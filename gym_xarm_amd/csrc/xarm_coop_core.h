@@ -80,6 +80,16 @@ template <typename T> XARM_HD LV<T> lv_scale(LV<T> a, T u) { XC_NO_CONTRACT LV<T
 template <typename T> XARM_HD LV<T> lv_fmas(LV<T> a, T u, LV<T> c) { LV<T> r; XC_LANES r.v[i_] = fm(a.v[i_], u, c.v[i_]); return r; }
 // act ? 1 / x : 0 (act is uniform over the row)
 template <typename T> XARM_HD LV<T> lv_rcp_if(LV<T> x, bool act) { LV<T> r; XC_LANES r.v[i_] = act ? (T)1 / x.v[i_] : (T)0; return r; }
+// 1 / x on the lanes that own a row of a live pad (lane l < 12: pad l / 3), 0 elsewhere
+template <typename T> XARM_HD LV<T> lv_rcp_pads(const Grp &G, LV<T> x, const bool (&pact)[4]) {
+    LV<T> r;
+    XC_LANES {
+        const int l = lane_of(G, i_);
+        const bool act = l < 3 ? pact[0] : (l < 6 ? pact[1] : (l < 9 ? pact[2] : (l < 12 ? pact[3] : false)));
+        r.v[i_] = act ? (T)1 / x.v[i_] : (T)0;
+    }
+    return r;
+}
 template <typename T> XARM_HD LV<T> lv_neg(LV<T> a) { LV<T> r; XC_LANES r.v[i_] = -a.v[i_]; return r; }
 XARM_HD double med3(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 #if defined(__HIPCC__) && !defined(XARM_HOST_BUILD)
@@ -400,6 +410,10 @@ template <typename T> struct Sweep {
     LV<T> g[4], lam[4], invd[4];
     LV<T> lo1, hi1;
     LV<T> nA0[C0_N], nA1[C1_N], nA2[C2_N], nA3[C1_N];
+#ifndef XC_PAD_SETUP_V1
+    LV2<T> AF01[NF];   // pad columns of the table / single-joint rows, scaled: pad_columns forms them, sweep_all takes them
+    LV<T> AF2[NF];     // pad columns of the pad rows, scaled, a row's own entry zero
+#endif
 };
 
 // Columns of A that belong to the pad rows.  M^-1 J_r^T of a pad row is expensive (full 9x9 product), so the lane
@@ -422,10 +436,94 @@ XARM_HD void pad_minv_jt(const Setup<T> &S, const LV<T> (&J)[R_G], LV<T> (&Ba)[9
     Bb[4] = lv_fmas(J[R_J2B + 5], S.Iinv[4], lv_fmas(J[R_J2B + 4], S.Iinv[3], lv_scale(J[R_J2B + 3], S.Iinv[1])));
     Bb[5] = lv_fmas(J[R_J2B + 5], S.Iinv[5], lv_fmas(J[R_J2B + 4], S.Iinv[4], lv_scale(J[R_J2B + 3], S.Iinv[2])));
 }
+// XC_PAD_SETUP_V1 keeps the first form of the per-substep pad setup (the form the host build keeps for comparison and the cooperative
+// Handover unit is built with, build.py).  The product form differs in three places, same values, same arithmetic, same order of every
+// sum (DESIGN.md 5 iii-c):
+//  the dot products of a pad row's column take lane r's M^-1 J_r^T as the DPP operand of the multiply-add itself (v_mul_f32_dpp /
+//      v_fmac_f32_dpp row_newbcast).  hipcc folds a row broadcast into a v_mul_f32 but never into a v_fmac_f32, so the first form pays 15
+//      v_mov_b32_dpp per pad row, 180 per substep, for nothing;
+//  the reciprocal diagonals of the pad rows come from ONE division in front of the columns instead of one per pad row: entry r of column r
+//      on lane r is J_r . M^-1 J_r^T with lane r's own operands, which every lane can form for itself;
+//  the columns are scaled by the receiving rows' 1 / d where they are made (Sweep::AF01, AF2), not at the head of sweep_all: the compiler
+//      parked the unscaled table entries in scratch between the two places.
+#if defined(__HIPCC__) && !defined(XARM_HOST_BUILD) && !defined(XC_PAD_SETUP_V1)
+#define XC_DPP_BC(r) " row_newbcast:" #r " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+// a0 = J0 . cb, a1 = J1 . ca, a2 = J2A . ca + J2B . cb, (ca, cb) = (Ba, Bb) of lane r; each chain in the order of the first form, the three
+// interleaved.  The statement is opaque to the compiler's hazard recognizer: the s_nop covers the two wait states between a VALU write of
+// a register (a v_accvgpr_read that has just brought Ba / Bb back counts) and a DPP read of it; nothing inside writes a DPP operand.
+#define XC_PAD_DOTS(r, a0, a1, a2)                                                                           \
+    asm("s_nop 1\n\t"                                                                                        \
+        "v_mul_f32_dpp %[x2], %[p0], %[f0]" XC_DPP_BC(r) "v_mul_f32_dpp %[x1], %[p0], %[s0]" XC_DPP_BC(r) "v_mul_f32_dpp %[x0], %[o0], %[t0]" XC_DPP_BC(r)    \
+        "v_fmac_f32_dpp %[x2], %[p1], %[f1]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p1], %[s1]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x0], %[o1], %[t1]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[p2], %[f2]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p2], %[s2]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x0], %[o2], %[t2]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[p3], %[f3]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p3], %[s3]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x0], %[o3], %[t3]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[p4], %[f4]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p4], %[s4]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x0], %[o4], %[t4]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[p5], %[f5]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p5], %[s5]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x0], %[o5], %[t5]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[p6], %[f6]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p6], %[s6]" XC_DPP_BC(r)                                                    \
+        "v_fmac_f32_dpp %[x2], %[p7], %[f7]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p7], %[s7]" XC_DPP_BC(r)                                                    \
+        "v_fmac_f32_dpp %[x2], %[p8], %[f8]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x1], %[p8], %[s8]" XC_DPP_BC(r)                                                    \
+        "v_fmac_f32_dpp %[x2], %[o0], %[g0]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x2], %[o1], %[g1]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x2], %[o2], %[g2]" XC_DPP_BC(r) \
+        "v_fmac_f32_dpp %[x2], %[o3], %[g3]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x2], %[o4], %[g4]" XC_DPP_BC(r) "v_fmac_f32_dpp %[x2], %[o5], %[g5]" XC_DPP_BC(r) \
+        : [x0] "=&v"(a0.v[0]), [x1] "=&v"(a1.v[0]), [x2] "=&v"(a2.v[0])                                      \
+        : [p0] "v"(Ba[0].v[0]), [p1] "v"(Ba[1].v[0]), [p2] "v"(Ba[2].v[0]), [p3] "v"(Ba[3].v[0]), [p4] "v"(Ba[4].v[0]), [p5] "v"(Ba[5].v[0]),                 \
+          [p6] "v"(Ba[6].v[0]), [p7] "v"(Ba[7].v[0]), [p8] "v"(Ba[8].v[0]),                                  \
+          [o0] "v"(Bb[0].v[0]), [o1] "v"(Bb[1].v[0]), [o2] "v"(Bb[2].v[0]), [o3] "v"(Bb[3].v[0]), [o4] "v"(Bb[4].v[0]), [o5] "v"(Bb[5].v[0]),                 \
+          [t0] "v"(J[R_J0 + 0].v[0]), [t1] "v"(J[R_J0 + 1].v[0]), [t2] "v"(J[R_J0 + 2].v[0]), [t3] "v"(J[R_J0 + 3].v[0]), [t4] "v"(J[R_J0 + 4].v[0]),         \
+          [t5] "v"(J[R_J0 + 5].v[0]),                                                                        \
+          [s0] "v"(J[R_J1 + 0].v[0]), [s1] "v"(J[R_J1 + 1].v[0]), [s2] "v"(J[R_J1 + 2].v[0]), [s3] "v"(J[R_J1 + 3].v[0]), [s4] "v"(J[R_J1 + 4].v[0]),         \
+          [s5] "v"(J[R_J1 + 5].v[0]), [s6] "v"(J[R_J1 + 6].v[0]), [s7] "v"(J[R_J1 + 7].v[0]), [s8] "v"(J[R_J1 + 8].v[0]),                                     \
+          [f0] "v"(J[R_J2A + 0].v[0]), [f1] "v"(J[R_J2A + 1].v[0]), [f2] "v"(J[R_J2A + 2].v[0]), [f3] "v"(J[R_J2A + 3].v[0]), [f4] "v"(J[R_J2A + 4].v[0]),    \
+          [f5] "v"(J[R_J2A + 5].v[0]), [f6] "v"(J[R_J2A + 6].v[0]), [f7] "v"(J[R_J2A + 7].v[0]), [f8] "v"(J[R_J2A + 8].v[0]),                                 \
+          [g0] "v"(J[R_J2B + 0].v[0]), [g1] "v"(J[R_J2B + 1].v[0]), [g2] "v"(J[R_J2B + 2].v[0]), [g3] "v"(J[R_J2B + 3].v[0]), [g4] "v"(J[R_J2B + 4].v[0]),    \
+          [g5] "v"(J[R_J2B + 5].v[0]))
+#endif
 template <typename T, bool LA, typename Scene = xk::PnpScene>
 XARM_HD void pad_columns(const Grp &G, const Setup<T> &S, const LV<T> (&J)[R_G], LV<T> cfm, Sweep<T> &W, const bool (&padw)[NP]) {
     LV<T> Ba[9], Bb[6];
     pad_minv_jt<T, Scene>(S, J, Ba, Bb);
+#ifndef XC_PAD_SETUP_V1
+#ifndef XC_PAD_DOTS   // host: the same three chains spelled out
+#define XC_PAD_DOTS(r, a0, a1, a2)                                                                           \
+    {                                                                                                        \
+        LV<T> ca[9], cb[6];                                                                                  \
+        _Pragma("unroll") for (int q = 0; q < 9; q++) ca[q] = lv_bcast<r>(Ba[q]);                            \
+        _Pragma("unroll") for (int d = 0; d < 6; d++) cb[d] = lv_bcast<r>(Bb[d]);                            \
+        a0 = lv_mul(J[R_J0], cb[0]); a1 = lv_mul(J[R_J1], ca[0]); a2 = lv_mul(J[R_J2A], ca[0]);              \
+        _Pragma("unroll") for (int d = 1; d < 6; d++) a0 = lv_fma(J[R_J0 + d], cb[d], a0);                   \
+        _Pragma("unroll") for (int q = 1; q < 9; q++) { a1 = lv_fma(J[R_J1 + q], ca[q], a1); a2 = lv_fma(J[R_J2A + q], ca[q], a2); } \
+        _Pragma("unroll") for (int d = 0; d < 6; d++) a2 = lv_fma(J[R_J2B + d], cb[d], a2);                  \
+    }
+#endif
+    // every lane's own diagonal first: entry r of column r is J_r . M^-1 J_r^T, the chain below with lane r's OWN (Ba, Bb) - the operands
+    // and the order column r's dot product has on lane r - so all 1 / d of the pad rows come from ONE division
+    LV<T> dg = lv_mul(J[R_J2A], Ba[0]);
+#pragma unroll
+    for (int q = 1; q < 9; q++) dg = lv_fma(J[R_J2A + q], Ba[q], dg);
+#pragma unroll
+    for (int d = 0; d < 6; d++) dg = lv_fma(J[R_J2B + d], Bb[d], dg);
+    W.invd[2] = lv_rcp_pads(G, lv_add(dg, cfm), S.pact);
+    const LV2<T> invd01 = lv2_make(W.invd[0], W.invd[1]);
+#define XC_PAD_COL(r)                                                                                        \
+    if (padw[(r) / 3]) {                                                                                     \
+        LV<T> a0, a1, a2;                                                                                    \
+        XC_PAD_DOTS(r, a0, a1, a2);                                                                          \
+        LV<T> diag = a2;                                                                                     \
+        lv_commit<r>(G, diag, lv_add(a2, cfm)); /* the owner of a pad normal adds its cfm: g_r carries -cfm lam_r */ \
+        W.nA0[C0_F + r] = lv_neg(a0);                                                                        \
+        W.nA1[C1_F + r] = lv_neg(a1);                                                                        \
+        W.nA2[C2_F + r] = lv_neg(diag);                                                                      \
+        /* the column scaled by the receiving rows' 1 / d here, where it is made, as sweep_all wants it (a row's own entry zero); \
+           unscaled, only the normal rows' columns are read again (apply_warm_start) */                      \
+        W.AF01[r] = lv2_mul(lv2_make(W.nA0[C0_F + r], W.nA1[C1_F + r]), invd01);                             \
+        W.AF2[r] = lv_mul(lv_neg(a2), W.invd[2]);                                                            \
+        lv_commit<r>(G, W.AF2[r], lv_fill((T)0));                                                            \
+        if (LA) { /* the arm-limit rows (no substep of the census carries one) keep the broadcast form */    \
+            LV<T> a3 = lv_mul(J[R_J3], lv_bcast<r>(Ba[0]));                                                  \
+            _Pragma("unroll") for (int q = 1; q < 7; q++) a3 = lv_fma(J[R_J3 + q], lv_bcast<r>(Ba[q]), a3);  \
+            W.nA3[C1_F + r] = lv_neg(a3);                                                                    \
+        }                                                                                                    \
+    }
+#else
 #define XC_PAD_COL(r)                                                                                        \
     if (padw[(r) / 3]) {                                                                                     \
         LV<T> ca[9], cb[6];                                                                                  \
@@ -447,6 +545,7 @@ XARM_HD void pad_columns(const Grp &G, const Setup<T> &S, const LV<T> (&J)[R_G],
         }                                                                                                    \
         lv_commit<r>(G, W.invd[2], lv_rcp_if(diag, S.pact[(r) / 3]));                                        \
     }
+#endif
     XC_PAD_COL(0) XC_PAD_COL(1) XC_PAD_COL(2) XC_PAD_COL(3) XC_PAD_COL(4) XC_PAD_COL(5)
     XC_PAD_COL(6) XC_PAD_COL(7) XC_PAD_COL(8) XC_PAD_COL(9) XC_PAD_COL(10) XC_PAD_COL(11)
 #undef XC_PAD_COL
@@ -513,15 +612,22 @@ XARM_HD void sweep_all(const Grp &G, Sweep<T> &W, T mu_t, T mu_p, const bool (&p
 #pragma unroll
             for (int i = 0; i < 7; i++) W.nA2[C2_L + i] = lv_mul(W.nA2[C2_L + i], W.invd[2]);
         }
-#define XC_COLF(r)                                                                                           \
-        if (padw[(r) / 3]) {                                                                                 \
+#ifdef XC_PAD_SETUP_V1
+#define XC_AF01(r)                                                                                           \
             AF01[r] = lv2_mul(lv2_make(W.nA0[C0_F + r], W.nA1[C1_F + r]), invd01);                           \
             W.nA2[C2_F + r] = lv_mul(W.nA2[C2_F + r], W.invd[2]);                                            \
-            lv_commit<r>(G, W.nA2[C2_F + r], lv_fill((T)0));                                                 \
+            lv_commit<r>(G, W.nA2[C2_F + r], lv_fill((T)0));
+#else
+#define XC_AF01(r) AF01[r] = W.AF01[r]; W.nA2[C2_F + r] = W.AF2[r];   /* scaled where pad_columns made them */
+#endif
+#define XC_COLF(r)                                                                                           \
+        if (padw[(r) / 3]) {                                                                                 \
+            XC_AF01(r)                                                                                       \
             if (LA) W.nA3[C1_F + r] = lv_mul(W.nA3[C1_F + r], W.invd[3]);                                    \
         }
         XC_COLF(0) XC_COLF(1) XC_COLF(2) XC_COLF(3) XC_COLF(4) XC_COLF(5) XC_COLF(6) XC_COLF(7) XC_COLF(8) XC_COLF(9) XC_COLF(10) XC_COLF(11)
 #undef XC_COLF
+#undef XC_AF01
     }
     if (LA) {
         c3 = lv_fma(W.g[3], W.invd[3], W.lam[3]);
