@@ -1375,28 +1375,10 @@ template <typename T, typename Lds>
 XARM_HD void env_step(const Grp &G, const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&obs)[xk::OBS_DIM], T &reward, bool &done,
                       bool &success, Lds lds) {
     const ArmLane<T> C = arm_lane_consts<T>(G);
-    st.steps += (T)1;
-    T a[4], qt[9];
-#pragma unroll
-    for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
-    xk::Frame<T> f = xk::frame_identity<T>();
-#pragma unroll
-    for (int i = 0; i < 7; i++) xk::fk_advance(f, i, st.q[i]);
-    const T sc = (T)(xm::PNP_MAX_VEL * xm::PNP_ACTION_DT);
-    const V3<T> target = mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
-                               clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
-                               clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
-    const T g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
-    xk::ik_solve(st.q, target, qt);
-    qt[7] = qt[8] = g;
-    st.mug = st.touch;
+    T qt[9];
+    xk::step_open(st, act, qt);
     sim_tick<T, Lds>(G, C, st, qt, lds);
-    xk::get_obs(st, obs);
-    const T dx = st.bp[0] - st.goal[0], dy = st.bp[1] - st.goal[1], dz = st.bp[2] - st.goal[2];
-    const T dist = xsqrt(dx * dx + dy * dy + dz * dz);
-    success = dist < (T)xm::PNP_DISTANCE_THRESHOLD;
-    reward = cfg.reward_type == 2 ? xk::dense_reward<T>(st, obs, dist) : xk::reward_of<T>(cfg.reward_type, dist);
-    done = success || ((int)st.steps == xm::PNP_MAX_EPISODE_STEPS);
+    xk::step_close(cfg, st, obs, reward, done, success);
 }
 
 // substeps [k0, 15) of a step on a 16-lane row: k0 == 0 is env_step, a later one continues the step a fast stage opened (xk::env_step_fast_range)

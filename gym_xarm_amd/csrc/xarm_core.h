@@ -606,7 +606,7 @@ XARM_HD void arm_dynamics(const T (&q_in)[9], const T (&qd_in)[9], const T dt, L
 // default device build contracts the two instantiations differently: last bits) for as long as no pad of the environment
 // is within the solver margin of the object, and it says so: the return value is "a pad row of this environment is active in this substep".  The fast step kernel
 // runs it on every environment and hands the ones that answer true to a kernel that solves pad rows (xarm_hip.hip,
-// k_step_fast): ~2 % of the environments hold a finger contact, but that is >= 1 lane in most wavefronts, and a wavefront
+// k_step_fast_stage): ~2 % of the environments hold a finger contact, but that is >= 1 lane in most wavefronts, and a wavefront
 // with one such lane sweeps the pad blocks for all 64 (k_step 1.88 ms against 0.74 ms for a contact-free batch).
 template <typename T, typename Lds, typename Scene = PnpScene, typename Xchg = NoXchg, bool FAST = false>
 XARM_HD bool substep(EnvState<T> &st, const T (&qt)[9], const T dt, Lds lds, const int arm = 0, const Xchg xchg = Xchg()) {
@@ -1310,12 +1310,9 @@ template <typename T, typename Lds> XARM_HD void env_reset(const EnvCfg &cfg, in
     st.episode = (T)episode;
 }
 
-// XarmPickAndPlace.step (:107-119)
-template <typename T, typename Lds>
-XARM_HD void env_step(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&obs)[OBS_DIM], T &reward, bool &done,
-                      bool &success, Lds lds) {
-    st.steps += (T)1;
-    T a[4], qt[9];
+// _set_action (:199-218): the clamped action as the Cartesian target of link_eef (returned) and the finger target g
+template <typename T> XARM_HD V3<T> action_targets(const EnvState<T> &st, const T (&act)[4], T &g) {
+    T a[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
     // current link_eef position
@@ -1323,75 +1320,21 @@ XARM_HD void env_step(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (
 #pragma unroll
     for (int i = 0; i < 7; i++) fk_advance(f, i, st.q[i]);
     const T sc = (T)(xm::PNP_MAX_VEL * xm::PNP_ACTION_DT);
-    const V3<T> target = mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
-                               clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
-                               clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
-    const T g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
+    g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
+    return mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
+                 clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
+                 clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
+}
+
+// The two ends of XarmPickAndPlace.step (:107-119).  step_open: the action becomes the joint targets qt of the step's 15 substeps;
+// step_close: observation, reward and flags after them.  Every step below is open, substeps, close.
+template <typename T> XARM_HD void step_open(EnvState<T> &st, const T (&act)[4], T (&qt)[9]) {
+    st.steps += (T)1;
+    T g;
+    const V3<T> target = action_targets(st, act, g);
     ik_solve(st.q, target, qt);
     qt[7] = qt[8] = g;
     st.mug = st.touch; // friction toggle from the LAST step's contacts (:212-218)
-    sim_tick<T, Lds>(st, qt, lds);
-    get_obs(st, obs);
-    const T dx = st.bp[0] - st.goal[0], dy = st.bp[1] - st.goal[1], dz = st.bp[2] - st.goal[2];
-    const T dist = xsqrt(dx * dx + dy * dy + dz * dz);
-    success = dist < (T)xm::PNP_DISTANCE_THRESHOLD;
-    reward = cfg.reward_type == 2 ? dense_reward<T>(st, obs, dist) : reward_of<T>(cfg.reward_type, dist);
-    done = success || ((int)st.steps == xm::PNP_MAX_EPISODE_STEPS);
-}
-
-// XarmPickAndPlace.step on the pad-free fast substep.  Returns false when a finger-pad row of this environment was
-// active in any of the 15 substeps: the outputs are then meaningless and the caller must not store them (the
-// environment is stepped again, from its untouched state, by a kernel that solves pad rows).
-template <typename T, typename Lds>
-XARM_HD bool env_step_fast(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&obs)[OBS_DIM], T &reward, bool &done,
-                           bool &success, Lds lds) {
-    st.steps += (T)1;
-    T a[4], qt[9];
-#pragma unroll
-    for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
-    Frame<T> f = frame_identity<T>();
-#pragma unroll
-    for (int i = 0; i < 7; i++) fk_advance(f, i, st.q[i]);
-    const T sc = (T)(xm::PNP_MAX_VEL * xm::PNP_ACTION_DT);
-    const V3<T> target = mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
-                               clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
-                               clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
-    const T g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
-    ik_solve(st.q, target, qt);
-    qt[7] = qt[8] = g;
-    st.mug = st.touch;
-    const T dt = (T)(xm::PNP_TIME_STEP / xm::PNP_N_SUBSTEPS);
-    bool pad = false;
-#pragma unroll 1
-    for (int k = 0; k < xm::PNP_N_SUBSTEPS; k++) pad = substep<T, Lds, PnpScene, NoXchg, true>(st, qt, dt, lds) || pad;
-    get_obs(st, obs);
-    const T dx = st.bp[0] - st.goal[0], dy = st.bp[1] - st.goal[1], dz = st.bp[2] - st.goal[2];
-    const T dist = xsqrt(dx * dx + dy * dy + dz * dz);
-    success = dist < (T)xm::PNP_DISTANCE_THRESHOLD;
-    reward = cfg.reward_type == 2 ? dense_reward<T>(st, obs, dist) : reward_of<T>(cfg.reward_type, dist);
-    done = success || ((int)st.steps == xm::PNP_MAX_EPISODE_STEPS);
-    return !pad;
-}
-
-// ---- the STAGED step (xarm_step, xarm_hip.hip; as for Handover, xarm_handover_core.h lane_step_fast_range): the 15 substeps of a
-// step in stages.  step_open / step_close are the two ends of env_step above; a stage that begins at substep k0 > 0 continues the
-// step with the joint targets qt the opening stage left.
-template <typename T> XARM_HD void step_open(EnvState<T> &st, const T (&act)[4], T (&qt)[9]) {
-    st.steps += (T)1;
-    T a[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
-    Frame<T> f = frame_identity<T>();
-#pragma unroll
-    for (int i = 0; i < 7; i++) fk_advance(f, i, st.q[i]);
-    const T sc = (T)(xm::PNP_MAX_VEL * xm::PNP_ACTION_DT);
-    const V3<T> target = mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
-                               clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
-                               clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
-    const T g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
-    ik_solve(st.q, target, qt);
-    qt[7] = qt[8] = g;
-    st.mug = st.touch;
 }
 template <typename T> XARM_HD void step_close(const EnvCfg &cfg, EnvState<T> &st, T (&obs)[OBS_DIM], T &reward, bool &done, bool &success) {
     get_obs(st, obs);
@@ -1401,6 +1344,19 @@ template <typename T> XARM_HD void step_close(const EnvCfg &cfg, EnvState<T> &st
     reward = cfg.reward_type == 2 ? dense_reward<T>(st, obs, dist) : reward_of<T>(cfg.reward_type, dist);
     done = success || ((int)st.steps == xm::PNP_MAX_EPISODE_STEPS);
 }
+
+// XarmPickAndPlace.step (:107-119)
+template <typename T, typename Lds>
+XARM_HD void env_step(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&obs)[OBS_DIM], T &reward, bool &done,
+                      bool &success, Lds lds) {
+    T qt[9];
+    step_open(st, act, qt);
+    sim_tick<T, Lds>(st, qt, lds);
+    step_close(cfg, st, obs, reward, done, success);
+}
+
+// ---- the STAGED step (xarm_step, xarm_hip.hip; as for Handover, xarm_handover_core.h lane_step_fast_range): the 15 substeps of a
+// step in stages.  A stage that begins at substep k0 > 0 continues the step with the joint targets qt the opening stage left.
 // substeps [k0, k1) on the pad-free fast substep; false: a pad row was active in one of them (store nothing)
 template <typename T, typename Lds>
 XARM_HD bool env_step_fast_range(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&qt)[9], int k0, int k1, T (&obs)[OBS_DIM], T &reward,
@@ -1412,6 +1368,15 @@ XARM_HD bool env_step_fast_range(const EnvCfg &cfg, EnvState<T> &st, const T (&a
     for (int k = k0; k < k1; k++) pad = substep<T, Lds, PnpScene, NoXchg, true>(st, qt, dt, lds) || pad;
     if (k1 == xm::PNP_N_SUBSTEPS) step_close(cfg, st, obs, reward, done, success);
     return !pad;
+}
+// XarmPickAndPlace.step on the pad-free fast substep: the one stage [0, 15).  Returns false when a finger-pad row of this
+// environment was active in any of the 15 substeps: the outputs are then meaningless and the caller must not store them (the
+// environment is stepped again, from its untouched state, by a kernel that solves pad rows).
+template <typename T, typename Lds>
+XARM_HD bool env_step_fast(const EnvCfg &cfg, EnvState<T> &st, const T (&act)[4], T (&obs)[OBS_DIM], T &reward, bool &done,
+                           bool &success, Lds lds) {
+    T qt[9];
+    return env_step_fast_range<T, Lds>(cfg, st, act, qt, 0, xm::PNP_N_SUBSTEPS, obs, reward, done, success, lds);
 }
 // substeps [k0, 15) on the full substep (the long-list fall-back of a staged hand-off)
 template <typename T, typename Lds>
@@ -1439,19 +1404,10 @@ XARM_HD void env_step_lazy(const EnvCfg &cfg, int64_t env, EnvState<T> &st, cons
     const bool resetting = st.steps < (T)0;
     const int left = resetting ? -(int)st.steps : 0;          // reset ticks still to run, 6 .. 1
     const bool teleport = resetting && left == 1;
-    T a[4], qt[9];
-#pragma unroll
-    for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
-    Frame<T> f = frame_identity<T>();
-#pragma unroll
-    for (int i = 0; i < 7; i++) fk_advance(f, i, st.q[i]);
-    const T sc = (T)(xm::PNP_MAX_VEL * xm::PNP_ACTION_DT);
-    const V3<T> tstep = mk<T>(clampT(f.o.x + a[0] * sc, (T)xm::PNP_POS_LOW[0], (T)xm::PNP_POS_HIGH[0]),
-                              clampT(f.o.y + a[1] * sc, (T)xm::PNP_POS_LOW[1], (T)xm::PNP_POS_HIGH[1]),
-                              clampT(f.o.z + a[2] * sc, (T)xm::PNP_POS_LOW[2], (T)xm::PNP_POS_HIGH[2]));
+    T qt[9], g;
+    const V3<T> tstep = action_targets(st, act, g);
     const V3<T> start = mk<T>((T)xm::PNP_START_GRIPPER_POS[0], (T)xm::PNP_START_GRIPPER_POS[1], (T)xm::PNP_START_GRIPPER_POS[2]);
     ik_solve(st.q, resetting ? start : tstep, qt);
-    const T g = clampT(st.q[7] + a[3] * (T)(xm::PNP_ACTION_DT * xm::PNP_MAX_GRIPPER_VEL), (T)xm::PNP_GRIPPER_LOW, (T)xm::PNP_GRIPPER_HIGH);
     qt[7] = qt[8] = resetting ? (T)xm::PNP_RESET_FINGER_TARGET : g;
     if (teleport) {
         // the pose target stays the one of the previous tick; then respawn the object and draw the goal (:259-266, :124)

@@ -93,10 +93,30 @@ __device__ __forceinline__ void write_obs(const float (&obs)[xk::OBS_DIM], const
     for (int k = 0; k < 3; k++) { ag_out[e * 3 + k] = s.bp[k]; dg_out[e * 3 + k] = s.goal[k]; }
 }
 
+// the output epilogue of every PickAndPlace step kernel: observation, reward, flags; a finished episode also leaves its terminal
+// observation and is appended to done_list
+__device__ __forceinline__ void pnp_finish(const KParams &P, int64_t e, const xk::EnvState<float> &s, const float (&obs)[xk::OBS_DIM], float reward,
+                                           bool done, bool success, float *obs_out, float *ag_out, float *dg_out, float *rew_out, uint8_t *done_out,
+                                           uint8_t *succ_out, float *term_obs, int *done_list, int *done_count) {
+    write_obs(obs, s, e, obs_out, ag_out, dg_out);
+    rew_out[e] = reward;
+    done_out[e] = done ? 1 : 0;
+    succ_out[e] = success ? 1 : 0;
+    if (done && P.auto_reset) {
+        if (term_obs) {
+            float4 *o = reinterpret_cast<float4 *>(term_obs + e * xk::OBS_DIM);
+#pragma unroll
+            for (int k = 0; k < xk::OBS_DIM / 4; k++) o[k] = make_float4(obs[4 * k], obs[4 * k + 1], obs[4 * k + 2], obs[4 * k + 3]);
+        }
+        const int pos = atomicAdd(done_count, 1);
+        done_list[pos] = (int)e;
+    }
+}
+
 // The fast step: XarmPickAndPlace.step on the pad-free substep (xk::substep<.., FAST>) for every env.  An env none of
 // whose finger pads comes within the solver margin of the object during the step - ~98 % of them - is finished here
 // with the arithmetic of k_step (same bits in the host build / with -ffp-contract=on; float32 last bits apart otherwise).  An env with an active pad row stores NOTHING and is appended to eject_list: it is
-// stepped again from its untouched state by k_step_coop_list (or k_step when the list is long).  Why: a wavefront with ONE
+// stepped again from its untouched state by k_step_coop_list_stage (or k_step / k_step_from_stage when the list is long).  Why: a wavefront with ONE
 // such lane sweeps the pad blocks for all 64 lanes, and with ~2 % of the envs in contact that is most wavefronts - k_step
 // takes 1.88 ms where a contact-free batch takes 0.74 ms (tools/fastpath_probe.py).  Only the table-slot columns live in
 // LDS (8 KB per workgroup instead of 38 KB).
@@ -214,12 +234,6 @@ __global__ __launch_bounds__(WG) void k_step(KParams P, const float *__restrict_
                                              uint8_t *__restrict__ succ_out, float *__restrict__ term_obs,
                                              int *__restrict__ done_list, int *__restrict__ done_count,
                                              const int *__restrict__ list, const int *__restrict__ count);
-__global__ __launch_bounds__(WG) void k_step_fast(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
-                                                  float *__restrict__ ag_out, float *__restrict__ dg_out,
-                                                  float *__restrict__ rew_out, uint8_t *__restrict__ done_out,
-                                                  uint8_t *__restrict__ succ_out, float *__restrict__ term_obs,
-                                                  int *__restrict__ done_list, int *__restrict__ done_count,
-                                                  int *__restrict__ eject_list, int *__restrict__ eject_count);
 __global__ __launch_bounds__(WG) void k_step_lazy(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
                                                   float *__restrict__ ag_out, float *__restrict__ dg_out,
                                                   float *__restrict__ rew_out, uint8_t *__restrict__ done_out,
@@ -235,13 +249,7 @@ __global__ __launch_bounds__(WG) void k_step_coop(KParams P, const float *__rest
                                                   float *__restrict__ rew_out, uint8_t *__restrict__ done_out,
                                                   uint8_t *__restrict__ succ_out, float *__restrict__ term_obs,
                                                   int *__restrict__ done_list, int *__restrict__ done_count);
-__global__ __launch_bounds__(WG) void k_step_coop_list(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
-                                                       float *__restrict__ ag_out, float *__restrict__ dg_out,
-                                                       float *__restrict__ rew_out, uint8_t *__restrict__ done_out,
-                                                       uint8_t *__restrict__ succ_out, float *__restrict__ term_obs,
-                                                       int *__restrict__ done_list, int *__restrict__ done_count,
-                                                       const int *__restrict__ list, const int *__restrict__ count);
-// the staged PickAndPlace step (xarm_k_pnp.hip, xarm_k_pnp_coop.hip)
+// the PickAndPlace step in stages (xarm_k_pnp.hip, xarm_k_pnp_coop.hip)
 __global__ __launch_bounds__(WG) void k_step_fast_stage(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
                                                         float *__restrict__ ag_out, float *__restrict__ dg_out,
                                                         float *__restrict__ rew_out, uint8_t *__restrict__ done_out,

@@ -13,9 +13,11 @@
 //                 (hence 1 wave per SIMD, __launch_bounds__(64)) plus 149 floats per env of LDS (hand Jacobian S, T =
 //                 M^-1 S^T, A_hh, table slots: lane-private columns, 38 KB per workgroup).  65 536 envs = 1024 workgroups =
 //                 4 per CU; workgroups never communicate, so no XCD-aware remap is needed.
-//   k_step_fast + k_step_coop_list   the default for batches above 8 192 envs: the pad-free fast step, then the envs with an
-//                 active finger-pad row on the cooperative core; XarmHandover the same way at every batch
-//                 size (xarm_k_handover_coop.hip: k_ho_step_fast + k_ho_step_coop_list, two 16-lane rows per env).
+//   k_step_fast_stage + k_step_coop_list_stage   the default for batches above 8 192 envs: the pad-free fast step in stages
+//                 (three by default; XARM_PNP_STAGES=1: the one stage {0, 15}), the envs with an active finger-pad row handed
+//                 off to the cooperative core from their stage's first substep on; hand-off lists above
+//                 XARM_EJECT_COOP_CAP fall back to k_step_from_stage (one stage: k_step).  XarmHandover the same way at every
+//                 batch size (xarm_k_handover_coop.hip: k_ho_step_fast + k_ho_step_coop_list, two 16-lane rows per env).
 //   k_step_coop / k_reset_coop   one environment per DPP row of 16 lanes (4 per wavefront), impulse-space sweep spread
 //                 over the row: the latency-optimal form for small batches and for the resets that follow a step.
 //   k_reset       the one-env-per-lane reset, for bulk resets (> coop_limit finished envs in one call).
@@ -47,9 +49,9 @@ struct xarm_handle {
                       // call (no host-side state: a captured step can be replayed)
     int *mask_count;  // [1]
     int coop_step_limit; // PickAndPlace, Reach, Handover (one stick): batches of at most this many envs step on the cooperative kernel
-    int fast_pipeline;   // PickAndPlace, larger batches: k_step_fast + hand-off of the envs with finger-pad rows (1) or k_step (0)
+    int fast_pipeline;   // PickAndPlace, larger batches: k_step_fast_stage + hand-off of the envs with finger-pad rows (1) or k_step (0)
     int *eject_list;     // [stages][E] envs handed off by the fast kernel, one list per stage
-    // the two reset launches of a pipelined step (xarm_step): episodes that ended in k_step_fast are reset on `side`
+    // the two reset launches of a pipelined step (xarm_step): episodes that ended in the fast kernel are reset on `side`
     // while the hand-off still runs on the caller's stream, the few that end in the hand-off after it
     int *done_list_b;    // [E] episodes that ended in the hand-off kernels
     hipStream_t side;
@@ -60,8 +62,8 @@ struct xarm_handle {
     static constexpr int MAX_ST = XARM_HO_MAX_STAGES;
     int ho_stages;        // 1 = one fast launch, one hand-off
     int ho_tick[MAX_ST + 1]; // stage c runs the ticks [ho_tick[c], ho_tick[c + 1])
-    float *ho_qt;         // [18][stride] joint targets of the step the first stage opened
-    uint8_t *ho_flag;     // [stride] handed off in an earlier stage of this call
+    float *ho_qt;         // [18][stride] joint targets of the step the first stage opened (ho_stages > 1)
+    uint8_t *ho_flag;     // [stride] handed off in an earlier stage of this call (every pipelined handle)
     hipStream_t st_side[MAX_ST];
     hipEvent_t st_fork[MAX_ST], st_join[MAX_ST];
     int ho_force_coupled; // test hook (XARM_HO_FORCE_COUPLED=1): every substep of the cooperative Handover step through the coupled sweep
@@ -227,10 +229,9 @@ static int pipelined_step(xarm_handle *h, const StepIO &io, hipStream_t st,
     return XARM_OK;
 }
 
-// PickAndPlace.  The unstaged pipeline (XARM_PNP_STAGES=1) is the one-stage case with kernels of its own.
+// PickAndPlace.  The unstaged pipeline (XARM_PNP_STAGES=1) is the one stage {0, 15} of the same kernels, as for Handover.
 static void pnp_fast(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage sg, hipStream_t st) {
-    if (h->ho_stages > 1) launch_step(k_step_fast_stage, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, sg);
-    else launch_step(k_step_fast, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt);
+    launch_step(k_step_fast_stage, env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, sg);
 }
 // With the reset overlap the episodes that end in the hand-off go to a list of their own (done_list_b): the reset of the ~98 %
 // that ended on the fast path need not wait for it.  Without the side stream (XARM_RESET_OVERLAP=0): one list, one reset after
@@ -239,13 +240,11 @@ static void pnp_handoff(xarm_handle *h, const StepIO &io, int *elist, int *ecnt,
     int *list_b = h->reset_overlap ? h->done_list_b : h->done_list, *cnt_b = slot(h, h->reset_overlap ? CNT_DONE_B : CNT_DONE);
     const int64_t cap = capped(h, h->kp.eject_coop_cap);
     const unsigned cgrid = coop_grid(cap) < 1024u ? coop_grid(cap) : 1024u;
-    if (h->ho_stages > 1) {
-        launch_step(k_step_coop_list_stage, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt, rest);
-        if (h->kp.num_envs > cap) launch_step(k_step_from_stage, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt, rest);
-    } else {
-        launch_step(k_step_coop_list, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt);
-        if (h->kp.num_envs > cap) launch_step(k_step, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt);
-    }
+    launch_step(k_step_coop_list_stage, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt, rest);
+    if (h->kp.num_envs <= cap) return;
+    // the long-list fall-back (lists above eject_coop_cap): k_step for an unstaged step, k_step_from_stage for a staged one
+    if (h->ho_stages > 1) launch_step(k_step_from_stage, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt, rest);
+    else launch_step(k_step, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt);
 }
 // a reset is six sequential ticks of latency on a few hundred wavefronts (2.9 ms), the hand-off 0.55 ms on a few hundred
 // others: started after the last fast stage on the side stream, the first reset overlaps the hand-off.  The call still waits
@@ -515,8 +514,10 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
             h->reset_overlap = e4 == hipSuccess;
         }
     }
-    if (e4 == hipSuccess && h->fast_pipeline && h->ho_stages > 1) {
-        e4 = hipMalloc(&h->ho_qt, sizeof(float) * 18 * stride);
+    if (e4 == hipSuccess && h->fast_pipeline) {
+        // the joint targets travel between stages only; the flags belong to every pipelined handle: k_step_fast_stage marks an env it
+        // hands off whatever the stage count
+        if (h->ho_stages > 1) e4 = hipMalloc(&h->ho_qt, sizeof(float) * 18 * stride);
         if (e4 == hipSuccess) e4 = hipMalloc(&h->ho_flag, stride);
         if (e4 == hipSuccess) e4 = hipMemset(h->ho_flag, 0, stride);
         for (int c = 0; c + 1 < h->ho_stages && e4 == hipSuccess; c++) {

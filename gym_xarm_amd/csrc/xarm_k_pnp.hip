@@ -1,4 +1,4 @@
-// xarm_k_pnp.hip - PickAndPlace, one environment per lane (k_step / k_step_fast / k_step_lazy / k_reset) and the small generic kernels.
+// xarm_k_pnp.hip - PickAndPlace, one environment per lane (k_step / k_step_fast_stage / k_step_from_stage / k_step_lazy / k_reset) and the small generic kernels.
 // Part of libxarm_hip.so (gfx950); shared declarations: xarm_dev.h, C ABI: xarm_hip.hip.
 #include "xarm_dev.h"
 
@@ -12,7 +12,7 @@ __global__ __launch_bounds__(WG) void k_init(KParams P) {
     store_state(P, e, s);
 }
 
-// XarmPickAndPlace.step for every env (list == null) or for the envs list[0 .. *count) (the hand-off of k_step_fast when it
+// XarmPickAndPlace.step for every env (list == null) or for the envs list[0 .. *count) (the hand-off of an unstaged k_step_fast_stage when it
 // is too long for the cooperative kernel); finished episodes are appended to done_list
 __global__ __launch_bounds__(WG) void k_step(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
                                              float *__restrict__ ag_out, float *__restrict__ dg_out,
@@ -23,7 +23,7 @@ __global__ __launch_bounds__(WG) void k_step(KParams P, const float *__restrict_
     __shared__ float smem[xk::LDS_FLOATS * WG];
     const int64_t i_in = (int64_t)blockIdx.x * WG + threadIdx.x;
     const int64_t n = count ? (int64_t)*count : P.num_envs;
-    if (count && n <= P.eject_coop_cap) return;     // k_step_coop_list's range
+    if (count && n <= P.eject_coop_cap) return;     // k_step_coop_list_stage's range
     if (i_in >= n) return;
     const int64_t e_in = list ? (int64_t)list[i_in] : i_in;
     DevLds lds{smem + threadIdx.x};
@@ -36,79 +36,11 @@ __global__ __launch_bounds__(WG) void k_step(KParams P, const float *__restrict_
     xk::env_step<float, DevLds>(P.cfg, s, act, obs, reward, done, success, lds);
     const int64_t e = late_index(e_in);
     store_state(P, e, s);
-    write_obs(obs, s, e, obs_out, ag_out, dg_out);
-    rew_out[e] = reward;
-    done_out[e] = done ? 1 : 0;
-    succ_out[e] = success ? 1 : 0;
-    if (done && P.auto_reset) {
-        if (term_obs) {
-            float4 *o = reinterpret_cast<float4 *>(term_obs + e * xk::OBS_DIM);
-#pragma unroll
-            for (int k = 0; k < xk::OBS_DIM / 4; k++) o[k] = make_float4(obs[4 * k], obs[4 * k + 1], obs[4 * k + 2], obs[4 * k + 3]);
-        }
-        const int pos = atomicAdd(done_count, 1);
-        done_list[pos] = (int)e;
-    }
+    pnp_finish(P, e, s, obs, reward, done, success, obs_out, ag_out, dg_out, rew_out, done_out, succ_out, term_obs, done_list, done_count);
 }
 
-__global__ __launch_bounds__(WG) void k_step_fast(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
-                                                  float *__restrict__ ag_out, float *__restrict__ dg_out,
-                                                  float *__restrict__ rew_out, uint8_t *__restrict__ done_out,
-                                                  uint8_t *__restrict__ succ_out, float *__restrict__ term_obs,
-                                                  int *__restrict__ done_list, int *__restrict__ done_count,
-                                                  int *__restrict__ eject_list, int *__restrict__ eject_count) {
-    __shared__ float smem[FAST_LDS_FLOATS * WG];
-    const int64_t e_in = (int64_t)blockIdx.x * WG + threadIdx.x;
-    if (e_in >= P.num_envs) return;
-    FastLds lds{smem + threadIdx.x};
-    xk::EnvState<float> s;
-    load_state(P, e_in, s);
-    const float4 a4 = reinterpret_cast<const float4 *>(actions)[e_in];
-    const float act[4] = {a4.x, a4.y, a4.z, a4.w};
-    float obs[xk::OBS_DIM], reward;
-    bool done, success;
-    const bool ok = xk::env_step_fast<float, FastLds>(P.cfg, s, act, obs, reward, done, success, lds);
-    const int64_t e = late_index(e_in);
-    if (!ok) {
-        const int pos = atomicAdd(eject_count, 1);
-        eject_list[pos] = (int)e;
-        return;
-    }
-    store_state(P, e, s);
-    write_obs(obs, s, e, obs_out, ag_out, dg_out);
-    rew_out[e] = reward;
-    done_out[e] = done ? 1 : 0;
-    succ_out[e] = success ? 1 : 0;
-    if (done && P.auto_reset) {
-        if (term_obs) {
-            float4 *o = reinterpret_cast<float4 *>(term_obs + e * xk::OBS_DIM);
-#pragma unroll
-            for (int k = 0; k < xk::OBS_DIM / 4; k++) o[k] = make_float4(obs[4 * k], obs[4 * k + 1], obs[4 * k + 2], obs[4 * k + 3]);
-        }
-        const int pos = atomicAdd(done_count, 1);
-        done_list[pos] = (int)e;
-    }
-}
-
-// ---- the STAGED step (XARM_PNP_STAGES > 1; xarm_step): stage kernels beside the unstaged ones above, which stay as they are.
-// qt[9][stride]: the joint targets the opening stage computed; flag[e] != 0: env e was handed off in an earlier stage of this call.
-__device__ __forceinline__ void pnp_finish(const KParams &P, int64_t e, const xk::EnvState<float> &s, const float (&obs)[xk::OBS_DIM], float reward,
-                                           bool done, bool success, float *obs_out, float *ag_out, float *dg_out, float *rew_out, uint8_t *done_out,
-                                           uint8_t *succ_out, float *term_obs, int *done_list, int *done_count) {
-    write_obs(obs, s, e, obs_out, ag_out, dg_out);
-    rew_out[e] = reward;
-    done_out[e] = done ? 1 : 0;
-    succ_out[e] = success ? 1 : 0;
-    if (done && P.auto_reset) {
-        if (term_obs) {
-            float4 *o = reinterpret_cast<float4 *>(term_obs + e * xk::OBS_DIM);
-#pragma unroll
-            for (int k = 0; k < xk::OBS_DIM / 4; k++) o[k] = make_float4(obs[4 * k], obs[4 * k + 1], obs[4 * k + 2], obs[4 * k + 3]);
-        }
-        const int pos = atomicAdd(done_count, 1);
-        done_list[pos] = (int)e;
-    }
-}
+// ---- the step in stages (xarm_step; XARM_PNP_STAGES=1: the one stage {0, 15}).  qt[9][stride]: the joint targets the opening stage
+// computed; flag[e] != 0: env e was handed off in an earlier stage of this call.
 // substeps [stage.tick0, stage.tick1) of the step on the pad-free fast substep; an env with an active pad row in them stores nothing,
 // is flagged and appended to eject_list (its hand-off re-runs the substeps from stage.tick0 on)
 __global__ __launch_bounds__(WG) void k_step_fast_stage(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,

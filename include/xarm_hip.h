@@ -127,7 +127,8 @@ typedef struct xarm_config {
  * configuration, never of its neighbours. */
 #define XARM_HO_STAGES_DEFAULT 3
 /* The pipelined PickAndPlace step (batches above step_coop_limit) is staged the same way over its 15 substeps: XARM_PNP_STAGES_DEFAULT
- * fast launches (env XARM_PNP_STAGES = 1 .. 5 at xarm_create; 1 = one fast launch and one hand-off, round 3's pipeline). */
+ * fast launches (env XARM_PNP_STAGES = 1 .. 5 at xarm_create; 1 = one fast launch and one hand-off: the unstaged pipeline, which is
+ * the single stage {0, 15} of the same kernels, as XARM_HO_STAGES=1 is for Handover). */
 #define XARM_PNP_STAGES_DEFAULT 3
 /* test hook: XARM_HO_FORCE_COUPLED=1 at xarm_create sends every substep of the cooperative Handover step and reset through the
  * coupled (both-arms) sweep - same bits by construction (tests/test_handover_coop.py) */

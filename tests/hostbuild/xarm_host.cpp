@@ -70,6 +70,35 @@ template <typename T> void do_step_fast(const xk::EnvCfg &c, int64_t E, double *
         rew[e] = r; done[e] = d; succ[e] = su;
     }
 }
+// the staged pipeline of xarm_step (xarm_hip.hip) with nst stages: fast substeps stage by stage on a copy, from the last accepted state;
+// the first stage that reports a pad row is dropped and the cooperative rows finish the step from its first substep on the untouched
+// state.  stage[e] = 0: finished on the fast path, 1 + c: handed off in stage c
+template <typename T> void pnp_staged(const xk::EnvCfg &c, int64_t E, int nst, double *state, const double *act, double *obs, double *rew, uint8_t *done, uint8_t *succ, uint8_t *stage) {
+    const int N = xm::PNP_N_SUBSTEPS;
+    for (int64_t e = 0; e < E; e++) {
+        xk::EnvState<T> s; load(state + e * xk::STATE_DIM, s);
+        T lds[xk::LDS_FLOATS]; HostLds<T> hl{lds};
+        T a[4], o[xk::OBS_DIM], r = 0, qt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; bool d = false, su = false;
+        for (int k = 0; k < 4; k++) a[k] = (T)act[e * 4 + k];
+        stage[e] = 0;
+        for (int k = 0; k < nst; k++) {
+            xk::EnvState<T> s2 = s;
+            T qt2[9];
+            for (int i = 0; i < 9; i++) qt2[i] = qt[i];
+            if (xk::env_step_fast_range<T>(c, s2, a, qt2, k * N / nst, (k + 1) * N / nst, o, r, d, su, hl)) {
+                s = s2;
+                for (int i = 0; i < 9; i++) qt[i] = qt2[i];
+            } else {
+                xc::env_step_from<T>(xc::Grp(), c, s, a, qt, k * N / nst, o, r, d, su, hl);
+                stage[e] = (uint8_t)(1 + k);
+                break;
+            }
+        }
+        store(s, state + e * xk::STATE_DIM);
+        for (int k = 0; k < xk::OBS_DIM; k++) obs[e * xk::OBS_DIM + k] = o[k];
+        rew[e] = r; done[e] = d; succ[e] = su;
+    }
+}
 template <typename T>
 void do_step_lazy(const xk::EnvCfg &cfg, int64_t E, double *state, const double *act, double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ) {
     for (int64_t e = 0; e < E; e++) {
@@ -478,6 +507,10 @@ void xh_reset(int f32, CFGARGS, int64_t E, double *state, const uint8_t *mask, d
 void xh_step_fast(int f32, CFGARGS, int64_t E, double *state, const double *act, double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ, uint8_t *ok) {
     auto c = mkcfg(seed, off, igr, ggr, gs, rt);
     if (f32) do_step_fast<float>(c, E, state, act, obs, ag, dg, rew, done, succ, ok); else do_step_fast<double>(c, E, state, act, obs, ag, dg, rew, done, succ, ok);
+}
+void xh_pnp_staged(int f32, CFGARGS, int64_t E, int stages, double *state, const double *act, double *obs, double *rew, uint8_t *done, uint8_t *succ, uint8_t *stage_out) {
+    auto c = mkcfg(seed, off, igr, ggr, gs, rt);
+    if (f32) pnp_staged<float>(c, E, stages, state, act, obs, rew, done, succ, stage_out); else pnp_staged<double>(c, E, stages, state, act, obs, rew, done, succ, stage_out);
 }
 void xh_coop_step(int f32, CFGARGS, int64_t E, double *state, const double *act, double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ) {
     auto c = mkcfg(seed, off, igr, ggr, gs, rt);

@@ -61,7 +61,7 @@ def test_an_env_does_not_depend_on_its_batch(env_id, A):
 
 
 def test_fast_pipeline_at_ragged_sizes():
-    """k_step_fast + the hand-off (what large PickAndPlace batches step on) at env counts that leave a ragged last
+    """k_step_fast_stage + the hand-off (what large PickAndPlace batches step on) at env counts that leave a ragged last
     workgroup in the fast kernel and a ragged last row group in the hand-off kernel, with auto-reset on: every env equals,
     bit for bit, the same global env id in a larger batch of the same pipeline - whichever wavefront its hand-off shares"""
     import torch

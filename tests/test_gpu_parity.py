@@ -27,7 +27,7 @@ class _Maker:
     """gx.make with the PickAndPlace kernel family pinned: 'lane' = one env per lane for step and reset (k_step /
     k_reset), 'coop' = the 16-lanes-per-env kernels (k_step_coop / k_reset_coop, the default for the batch sizes of
     these tests), 'fast' = what a 65 536-env batch steps on by default: the pad-free fast kernel with the hand-off of the
-    envs that have an active finger-pad row to the cooperative kernel (k_step_fast + k_step_coop_list), resets on k_reset"""
+    envs that have an active finger-pad row to the cooperative kernel (k_step_fast_stage + k_step_coop_list_stage), resets on k_reset"""
 
     def __init__(self, gx, family):
         self.gx, self.family, self.vec_env = gx, family, gx.vec_env
@@ -376,7 +376,7 @@ def test_a_captured_step_replays_like_eager_steps(gx, env_id, E, A):
 
 
 def test_overlapped_reset_changes_nothing_but_the_time(gx, monkeypatch):
-    """A pipelined PickAndPlace step resets the episodes that ended in k_step_fast on a side stream while the hand-off still
+    """A pipelined PickAndPlace step resets the episodes that ended in k_step_fast_stage on a side stream while the hand-off still
     runs, and those that ended in the hand-off after it (two lists, two launches, joined before the call's work ends on the
     caller's stream).  XARM_RESET_OVERLAP=0 runs both resets on the caller's stream: same bits, through several hundred
     resets per step."""
@@ -404,7 +404,7 @@ def test_overlapped_reset_changes_nothing_but_the_time(gx, monkeypatch):
 def test_staged_pipeline_against_the_unstaged_one(gx, monkeypatch):
     """The pipelined PickAndPlace step runs its fast kernel in three stages of five substeps (XARM_PNP_STAGES_DEFAULT), each stage's hand-off
     re-running the substeps from that stage's first one on the cooperative kernel beside the next stage - against XARM_PNP_STAGES=1 (one fast
-    launch, one hand-off: round 3's pipeline) from identical states: an env that finishes on the fast path or is handed off in the first
+    launch, one hand-off: the single stage {0, 15} of the same kernels) from identical states: an env that finishes on the fast path or is handed off in the first
     stage runs the same code over the same substeps - the same bits; an env whose pads come alive later has its first substeps on the
     lane core instead of the cooperative one - float32-close.  Run to run the staged step is bitwise reproducible (three streams), with
     auto-reset as without."""
@@ -452,8 +452,8 @@ def test_staged_pipeline_against_the_unstaged_one(gx, monkeypatch):
 
 
 def test_fast_pipeline_against_the_plain_step_kernel(gx, monkeypatch):
-    """What a large PickAndPlace batch steps on by default - k_step_fast (the pad-free substep) with the hand-off of the
-    envs that have an active finger-pad row to k_step_coop_list - against the plain k_step.  The fast substep is the plain
+    """What a large PickAndPlace batch steps on by default - k_step_fast_stage (the pad-free substep) with the hand-off of the
+    envs that have an active finger-pad row to k_step_coop_list_stage - against the plain k_step.  The fast substep is the plain
     one minus blocks that are no-ops for an env without pad rows: the same bits in the host build (tests/test_hostcore.py)
     and in a device build with -ffp-contract=on (measured: 71 of 4 096 envs differ after a step, the handed-off ones); the
     default device build lets LLVM contract the two instantiations differently, so here an env that is never handed off

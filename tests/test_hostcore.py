@@ -2,6 +2,8 @@
 space block PGS, lane-masked execution) compiled for the host and compared with the oracle.  In
 float64 the two must agree to rounding - they are the same Gauss-Seidel sweep in exact arithmetic -
 which is what licenses the float32 tolerance used on the GPU."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -104,7 +106,7 @@ def test_dense_reward_f64_matches_oracle(oracle, hostcore, golden_rollout):
 
 
 def test_fast_step_is_the_plain_step_for_every_env_it_accepts(hostcore, golden_rollout):
-    """xk::env_step_fast (the pad-free substep behind k_step_fast): on every env it accepts the result is the plain
+    """xk::env_step_fast (the pad-free substep behind k_step_fast_stage, as its one stage [0, 15)): on every env it accepts the result is the plain
     env_step's bit for bit - state, observation, reward, done - in float32 and in float64; an env it rejects (a finger-pad
     row became active) comes back untouched; and no env that ends the step with a pad impulse is ever accepted"""
     g = golden_rollout
@@ -124,3 +126,62 @@ def test_fast_step_is_the_plain_step_for_every_env_it_accepts(hostcore, golden_r
             n_ok += ok.sum()
             n_all += ok.size
         assert (0.85 < n_ok / n_all <= 1.0) if key == "rand" else (0.4 < n_ok / n_all < 0.9)   # the grasp script lives in contact
+
+
+def _pnp_staged(hostcore, state, actions, stages, f32):
+    """xh_pnp_staged (tests/hostbuild/xarm_host.cpp): the staged pipeline of xarm_step; stage 0 = finished on the fast path,
+    1 + c = handed off to the cooperative rows in stage c"""
+    E = state.shape[0]
+    st = np.array(state, dtype=np.float64, copy=True)
+    a = np.ascontiguousarray(actions, dtype=np.float64)
+    obs, rew = np.zeros((E, 24)), np.zeros(E)
+    done, succ, stage = np.zeros(E, np.uint8), np.zeros(E, np.uint8), np.zeros(E, np.uint8)
+    hostcore.L.xh_pnp_staged(C.c_int(f32), *hostcore._cfg(), C.c_int64(E), C.c_int(stages), hostcore._p(st), hostcore._p(a), hostcore._p(obs),
+                             hostcore._p(rew), hostcore._u8(done), hostcore._u8(succ), hostcore._u8(stage))
+    return st, obs, rew, done, succ, stage
+
+
+def test_staged_pipeline_f64_equals_oracle_and_hands_off_late_contacts_late(hostcore, golden_rollout):
+    """PickAndPlace's staged step (fast stages of xk::env_step_fast_range on a copy; the stage that sees a pad row is dropped and
+    xc::env_step_from finishes the step from its first substep) - the host counterpart of the Handover test of the same name.
+    Three stages in float64 == the oracle's next state within the bound of test_step_f64_equals_oracle_on_golden_rollout; one stage
+    is step_fast on the envs that accepts and coop_step on the others, bit for bit; three stages are one stage bit for bit on every
+    env that finishes fast or is handed off in stage 0; over the random rollout the fast path and a hand-off in each of the three
+    stages all occur (a contact that begins late in the step is handed off late)."""
+    g = golden_rollout
+    for key in ("rand", "grasp"):
+        S, A = g[key + "_states"], g[key + "_actions"]
+        seen = np.zeros(4, np.int64)
+        worst, n_ok = 0.0, 0
+        for t in range(A.shape[0]):
+            st, obs, rew, done, succ, stage = _pnp_staged(hostcore, S[t], A[t], 3, f32=0)
+            sens = g[key + "_sens"][t]
+            err = np.abs(st - S[t + 1]).max(axis=1)
+            ok = sens < 1e-2
+            print(key, t, "worst non-exempt err", err[ok].max(), "stages", np.bincount(stage, minlength=4))
+            assert (err[ok] <= 1e-9 + 1e-4 * sens[ok]).all(), (t, err[ok].max())
+            n_ok += ok.sum()
+            np.testing.assert_allclose(obs[ok], g[key + "_obs"][t][ok], atol=1e-8)
+            assert np.array_equal(rew[ok], g[key + "_rew"][t][ok])
+            assert np.array_equal(done[ok], g[key + "_done"][t][ok])
+            worst = max(worst, err[ok].max())
+            seen += np.bincount(stage, minlength=4)
+            for f32 in (0, 1):
+                three = st, obs, rew, done, succ, stage
+                if f32:
+                    three = _pnp_staged(hostcore, S[t], A[t], 3, f32=1)
+                one = _pnp_staged(hostcore, S[t], A[t], 1, f32=f32)
+                fast = hostcore.step_fast(S[t], A[t], f32=f32)
+                acc = fast[7]
+                coop = hostcore.coop_step(S[t][~acc], A[t][~acc], f32=f32)     # only the envs the fast step refused
+                assert np.array_equal(one[5] == 0, acc)
+                same = three[5] <= 1
+                assert np.array_equal(three[5][same], one[5][same])
+                for k, j in enumerate((0, 1, 4, 5, 6)):      # state, obs, reward, done, success
+                    assert np.array_equal(one[k][acc], fast[j][acc]) and np.array_equal(one[k][~acc], coop[j]), (key, t, f32, k)
+                    assert np.array_equal(three[k][same], one[k][same]), (key, t, f32, k)
+        print(key, "stage census", seen, "worst", worst, "non-exempt share", n_ok / (A.shape[0] * A.shape[1]))
+        assert worst < 1e-9
+        assert n_ok >= 0.85 * A.shape[0] * A.shape[1]
+        if key == "rand":
+            assert (seen > 0).all(), seen        # fast path, and a hand-off in each of the three stages

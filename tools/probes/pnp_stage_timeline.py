@@ -2,7 +2,7 @@
 
   python tools/probes/pnp_stage_timeline.py <rocprofv3 output dir> <fast stages per call> [calls to average, default 10]
 
-A call starts at every n-th launch of the fast kernel (k_step_fast_stage, or k_step_fast when unstaged).  Every kernel of the
+A call starts at every n-th launch of the fast kernel (k_step_fast_stage; n = 1 for the unstaged pipeline, XARM_PNP_STAGES=1).  Every kernel of the
 library that starts before the next call's first fast launch belongs to it.  Printed: start and end of each launch relative
 to the call's first launch, the median over the last calls of the trace (keyed by kernel name and its ordinal within the
 call), then the span of the call and when its last reset launch began."""
@@ -28,7 +28,7 @@ def main():
         if n and (n.startswith("k_step") or n.startswith("k_reset")):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n, r.get("Grid_Size_X", r.get("Grid_Size", "?"))))
     rows.sort()
-    fast = [i for i, r in enumerate(rows) if r[2] in ("k_step_fast_stage", "k_step_fast")]
+    fast = [i for i, r in enumerate(rows) if r[2] == "k_step_fast_stage"]
     heads = fast[::nst]
     heads = heads[-(ncall + 1):]           # the last one only closes the call before it
     per_key, order, spans, last_reset = {}, [], [], []

@@ -9,7 +9,9 @@ import os
 import sys
 
 # candidates per role, the first one present in the summary with counters wins (the fast pipeline's first kernel, the plain
-# kernel when the pipeline is off, the cooperative family at small batch sizes)
+# kernel when the pipeline is off, the cooperative family at small batch sizes).  k_step_fast / k_step_coop_list are HISTORIC names:
+# the unstaged pipeline's own kernels until it became the one stage {0, 15} of the *_stage kernels; kept so that the summaries
+# under profiles/ from before (r03j_*, r04b_*) still merge
 STEP_KERNEL = {"pnp": ["k_step_fast_stage", "k_step_fast", "k_step", "k_step_coop"], "reach": ["k_reach_step", "k_reach_step_coop"],
                "handover": ["k_ho_step_fast", "k_ho_step"], "stack": ["k_st_step"], "handover2": ["k_ho2_step"]}
 RESET_KERNEL = {"pnp": ["k_reset_coop", "k_reset"], "reach": ["k_reach_reset", "k_reach_reset_coop"],
