@@ -1,11 +1,11 @@
-// xarm_k_rearrange.hip - XarmRearrange-v0 (two arms, four cubes, a goal per cube; core: xarm_rearrange_core.h).
-// Part of libxarm_hip.so (gfx950); shared declarations: xarm_dev.h, C ABI: xarm_hip.hip.
-#include "xarm_dev.h"
+// xarm_k_rearrange.hip - XarmRearrange-v0 (two arms, four cubes, a goal per cube; scene: xra::Rearrange4 in xarm_rearrange_core.h).
+// Part of libxarm_hip.so (gfx950); shared declarations: xarm_dev.h, shared kernel parts: xarm_cubes_dev.h, C ABI: xarm_hip.hip.
+#include "xarm_cubes_dev.h"
 
 namespace xd {
 
 // --------------------------------------------------------------------- LDS: one copy of the object columns per env
-// The core addresses 929 floats per lane (xra::LDS_FLOATS).  The first 117 (the arm's S | T | A_hh columns) are the lane's own,
+// The core addresses 929 floats per lane (Rearrange4::LDS_FLOATS).  The first 117 (the arm's S | T | A_hh columns) are the lane's own,
 // at stride WG; the other 812 (16 table slots, 6 cube/cube pairs, the clipping scratch) hold the same numbers in both lanes of an
 // env - each lane computes the object rows redundantly and bit-identically, in lockstep - and are ONE copy per env at stride
 // WG / 2: same-address reads broadcast, the two lanes' writes carry the same value.  117 x 64 + 812 x 32 floats = 130.75 KiB per
@@ -15,126 +15,31 @@ struct RaLds {
     float *obj;   // + lane / 2, column stride WG / 2
     __device__ __forceinline__ float &operator[](int i) const { return i < xk::LDS_TBL ? arm[i * WG] : obj[(i - xk::LDS_TBL) * (WG / 2)]; }
 };
-constexpr int RA_LDS_FLOATS = xk::LDS_TBL * WG + xra::LDS_SHARED * (WG / 2);
+constexpr int RA_LDS_FLOATS = xk::LDS_TBL * WG + xra::Rearrange4::LDS_SHARED * (WG / 2);
 static_assert(RA_LDS_FLOATS * 4 <= 160 * 1024, "one wavefront must fit a CU's LDS");
 __device__ __forceinline__ RaLds ra_lds(float *smem) { return RaLds{smem + threadIdx.x, smem + xk::LDS_TBL * WG + (threadIdx.x >> 1)}; }
 
-__device__ __forceinline__ void ra_load(const KParams &P, int64_t e, int arm, xra::Lane<float> &L) {
-    const float *S = P.state + e;
-    const int64_t n = P.stride;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        L.q[i] = S[(xra::K_Q + 9 * arm + i) * n]; L.qd[i] = S[(xra::K_QD + 9 * arm + i) * n]; L.qt[i] = S[(xra::K_QT + 9 * arm + i) * n];
-    }
-#pragma unroll
-    for (int o = 0; o < xra::NOBJ; o++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            L.bp[o][k] = S[(xra::K_BP + 3 * o + k) * n]; L.bv[o][k] = S[(xra::K_BV + 3 * o + k) * n];
-            L.bw[o][k] = S[(xra::K_BW + 3 * o + k) * n]; L.goal[o][k] = S[(xra::K_GOAL + 3 * o + k) * n];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) L.bq[o][k] = S[(xra::K_BQ + 4 * o + k) * n];
-#pragma unroll
-        for (int k = 0; k < 8; k++) L.lam_t[o][k] = S[(xra::K_LT + 8 * o + k) * n];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) L.lam_p[k] = S[(xra::K_LP + 4 * arm + k) * n];
-    L.steps = S[xra::K_STEPS * n]; L.episode = S[xra::K_EPISODE * n];
-    L.cls = 0;
-}
-
-__device__ __forceinline__ void ra_store(const KParams &P, int64_t e, int arm, const xra::Lane<float> &L) {
-    float *S = P.state + e;
-    const int64_t n = P.stride;
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        S[(xra::K_Q + 9 * arm + i) * n] = L.q[i]; S[(xra::K_QD + 9 * arm + i) * n] = L.qd[i]; S[(xra::K_QT + 9 * arm + i) * n] = L.qt[i];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) S[(xra::K_LP + 4 * arm + k) * n] = L.lam_p[k];
-    if (arm == 0) { // shared fields are bit-identical in both lanes
-#pragma unroll
-        for (int o = 0; o < xra::NOBJ; o++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                S[(xra::K_BP + 3 * o + k) * n] = L.bp[o][k]; S[(xra::K_BV + 3 * o + k) * n] = L.bv[o][k];
-                S[(xra::K_BW + 3 * o + k) * n] = L.bw[o][k]; S[(xra::K_GOAL + 3 * o + k) * n] = L.goal[o][k];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) S[(xra::K_BQ + 4 * o + k) * n] = L.bq[o][k];
-#pragma unroll
-            for (int k = 0; k < 8; k++) S[(xra::K_LT + 8 * o + k) * n] = L.lam_t[o][k];
-        }
-        S[xra::K_STEPS * n] = L.steps; S[xra::K_EPISODE * n] = L.episode;
-    }
-}
-
-// observation (xarm_rearrange.py :190-199): cube pos 12, quat 16, v 12, w 12, then per arm hand COM pos 3, vel 3, finger q, qd
-__device__ __forceinline__ void ra_write_obs(const xra::Lane<float> &L, int64_t e, int arm, float *obs_out, float *ag_out, float *dg_out) {
-    float o8[8];
-    xra::arm_obs(L, arm, o8);
-    float *o = obs_out + e * xra::OBS_DIM;
-#pragma unroll
-    for (int k = 0; k < 8; k++) o[52 + 8 * arm + k] = o8[k];
-    if (arm == 0) {
-#pragma unroll
-        for (int ob = 0; ob < xra::NOBJ; ob++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                o[3 * ob + k] = L.bp[ob][k]; o[28 + 3 * ob + k] = L.bv[ob][k]; o[40 + 3 * ob + k] = L.bw[ob][k];
-                if (ag_out) { ag_out[e * 12 + 3 * ob + k] = L.bp[ob][k]; dg_out[e * 12 + 3 * ob + k] = L.goal[ob][k]; }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) o[12 + 4 * ob + k] = L.bq[ob][k];
-        }
-    }
-}
+using Sc = xra::Rearrange4;
 
 __global__ __launch_bounds__(WG) void k_ra_init(KParams P) {
     const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x, e = t >> 1;
     const int arm = (int)(t & 1);
     if (e >= P.num_envs) return;
-    xra::Lane<float> L;
-    xra::lane_init<float>(P.cfg, e, L);
-    ra_store(P, e, arm, L);
+    xs::Lane<float, Sc> L;
+    xs::lane_init<float>(P.cfg, e, L);
+    cubes_store(P, e, arm, L);
 }
 
-// class-homogeneous wavefronts over the 256 row-set classes of this scene (xra::class_layout; as k_class_hist / k_class_place
-// do for StackTower's 32): histogram of the per-env class keys, then every env takes the next slot of its class.
 __global__ void k_ra_class_hist(const uint8_t *__restrict__ key, int64_t n, int *__restrict__ hist) {
-    __shared__ int h[xra::NCLS];
-    for (int c = threadIdx.x; c < xra::NCLS; c += blockDim.x) h[c] = 0;
-    __syncthreads();
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) atomicAdd(&h[key[e]], 1);
-    __syncthreads();
-    for (int c = threadIdx.x; c < xra::NCLS; c += blockDim.x)
-        if (h[c]) atomicAdd(&hist[c], h[c]);
+    __shared__ int h[Sc::NCLS];
+    class_hist<Sc::NCLS>(key, n, hist, h);
 }
 
 __global__ void k_ra_class_place(const uint8_t *__restrict__ key, int64_t n, const int *__restrict__ hist, int *__restrict__ cursor,
                                  int *__restrict__ order, int group) {
-    __shared__ xra::ClassLayout Y;
-    __shared__ int cnt[xra::NCLS], base[xra::NCLS];
-    for (int c = threadIdx.x; c < xra::NCLS; c += blockDim.x) { cnt[c] = 0; base[c] = 0; }
-    if (threadIdx.x == 0) {
-        int hh[xra::NCLS];
-        for (int c = 0; c < xra::NCLS; c++) hh[c] = hist[c];
-        xra::class_layout(hh, group, Y);
-    }
-    __syncthreads();
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = e < n ? (int)key[e] : 0;
-    // arrival number inside the class: rank inside the block (LDS counter), one global atomic per block and class
-    const int local = e < n ? atomicAdd(&cnt[c], 1) : 0;
-    __syncthreads();
-    for (int k = threadIdx.x; k < xra::NCLS; k += blockDim.x)
-        if (cnt[k]) base[k] = atomicAdd(&cursor[k], cnt[k]);
-    __syncthreads();
-    if (e >= n) return;
-    const int slot = xra::class_slot(Y, c, base[c] + local);
-    if (slot >= 0 && slot < n) order[slot] = (int)e;   // always true for a histogram of these keys; never write outside
+    __shared__ xs::ClassLayoutN<Sc::NCLS> Y;
+    __shared__ int cnt[Sc::NCLS], base[Sc::NCLS];
+    class_place<Sc::NCLS>(key, n, hist, cursor, order, group, Y, cnt, base);
 }
 
 __global__ __launch_bounds__(WG) void k_ra_step(KParams P, const float *__restrict__ actions, float *__restrict__ obs_out,
@@ -149,17 +54,17 @@ __global__ __launch_bounds__(WG) void k_ra_step(KParams P, const float *__restri
     if (slot >= P.num_envs) return;
     const int64_t e_in = order ? (int64_t)order[slot] : slot;
     const RaLds lds = ra_lds(smem);
-    xra::Lane<float> L;
-    ra_load(P, e_in, arm, L);
+    xs::Lane<float, Sc> L;
+    cubes_load(P, e_in, arm, L);
     const float4 a4 = reinterpret_cast<const float4 *>(actions)[e_in * 2 + arm];
     const float act[4] = {a4.x, a4.y, a4.z, a4.w};
     float reward;
     bool done, success;
-    xra::lane_step<float, RaLds, DppXchg>(P.cfg, L, arm, act, reward, done, success, lds, DppXchg());
+    xs::lane_step<float, RaLds, DppXchg>(P.cfg, L, arm, act, reward, done, success, lds, DppXchg());
     const int64_t e = late_index(e_in);
-    ra_store(P, e, arm, L);
-    ra_write_obs(L, e, arm, obs_out, ag_out, dg_out);
-    if (done && P.auto_reset && term_obs) ra_write_obs(L, e, arm, term_obs, nullptr, nullptr);
+    cubes_store(P, e, arm, L);
+    cubes_write_obs(L, e, arm, obs_out, ag_out, dg_out);
+    if (done && P.auto_reset && term_obs) cubes_write_obs(L, e, arm, term_obs, nullptr, nullptr);
     if (arm == 0) {
         if (key) key[e] = (uint8_t)L.cls;
         rew_out[e] = reward;
@@ -182,24 +87,17 @@ __global__ __launch_bounds__(WG) void k_ra_reset(KParams P, const int *__restric
     if (i >= n) return;
     const int64_t e_in = list ? (int64_t)list[i] : i;
     const RaLds lds = ra_lds(smem);
-    xra::Lane<float> L;
-    ra_load(P, e_in, arm, L);
-    xra::lane_reset<float, RaLds, DppXchg>(P.cfg, e_in, L, arm, lds, DppXchg());
+    xs::Lane<float, Sc> L;
+    cubes_load(P, e_in, arm, L);
+    xs::lane_reset<float, RaLds, DppXchg>(P.cfg, e_in, L, arm, lds, DppXchg());
     const int64_t e = late_index(e_in);
-    ra_store(P, e, arm, L);
+    cubes_store(P, e, arm, L);
     if (key && arm == 0) key[e] = (uint8_t)L.cls;
-    if (obs_out) ra_write_obs(L, e, arm, obs_out, ag_out, dg_out);
+    if (obs_out) cubes_write_obs(L, e, arm, obs_out, ag_out, dg_out);
 }
 
-// xarm_rearrange.py:124-129 over n rows of 12
 __global__ void k_ra_compute_reward(int reward_type, const float *__restrict__ ag, const float *__restrict__ g, int64_t n, float *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float d2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 12; k++) { const float d = ag[i * 12 + k] - g[i * 12 + k]; d2 += d * d; }
-    const float d = sqrtf(d2);
-    out[i] = reward_type == 0 ? (d > (float)xm::RA_DISTANCE_THRESHOLD ? -1.f : 0.f) : -d;
+    cubes_compute_reward<Sc>(reward_type, ag, g, n, out);
 }
 
 } // namespace xd

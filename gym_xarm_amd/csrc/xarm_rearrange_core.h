@@ -3,873 +3,41 @@
 // Reference: gym_xarm/envs/xarm_rearrange.py (XarmRearrangeEnv; xarm_bimanual_base.py XarmPDBimanualEnv is the
 // same file but for the class name).  It differs from xarm_stack_tower.py in num_obj = 4 (:20, so distance_threshold 0.12) and
 // _sample_goal (:213-218: an independent goal_space xy per cube at z = 0.025) only.  Arms, clip boxes, gripper range, cubes,
-// the reset (one tick, no rejection), done = False, 50 steps and the contact model are StackTower's (xarm_stack_core.h): this
-// core is xs::substep with four cubes and six cube pairs, and reuses xs::StackScene and xs::box_box.
-//
-// State (SoA, STATE_DIM = 160 floats per env, StackTower's field order):
-//   q 0-17, qd 18-35, qt 36-53 (arm a: 9 a .. 9 a + 8), cube positions 54-65, quaternions (x y z w) 66-81, linear velocities
-//   82-93, angular velocities 94-105, goals 106-117, table warm starts lam_t[4][8] 118-149, pad warm starts lam_p[2][4]
-//   150-157, steps 158, episode 159.
-// Observation (68, xarm_rearrange.py _get_obs :164-199): cube pos 12, quat 16, v 12, w 12, then per arm hand COM pos 3, vel 3,
-//   finger q, finger qd.  Achieved goal = the 12 cube coordinates, desired goal = 4 x (xy, 0.025).
-// Row order of a substep (projected Gauss-Seidel): T cubes 0-3; BB pairs 01 02 03 12 13 23; M L G of this lane's arm; F arm 0,
-//   F arm 1.  With one cube parked away from everything the rows left over are StackTower's, in StackTower's order.
-// Reset: both arms to joint_init_pos, 4 cubes uniform in obj_space (identity orientation, no rejection), ONE tick with the
-//   previous motor targets, then the 4 goals.  Draws (Philox keyed by seed, global env id, episode; block b gives 4 uniforms):
-//   blocks 0-1 = u[0..7] = cube i xy (u[2i], u[2i+1]) - cubes 0-2 spawn where StackTower's do; blocks 2-3 = u[8..15] = goal i xy
-//   (u[8+2i], u[9+2i]).
-//
-// Data placement: 929 LDS floats per lane if laid out as StackTower's (117 arm columns, 16 table slots x 11, 6 pairs x 94,
-// 72 clip) - 232 KiB per 64-lane wavefront, over a CU's 160 KiB.  The object-contact columns (812 of the 929) hold the same
-// numbers in both lanes of an env (each lane computes the object rows redundantly and bit-identically, in lockstep), so the
-// kernel keeps ONE copy per env (RaLds in xarm_k_rearrange.hip, as two-stick Handover's Ho2Lds): 117 x 64 + 812 x 32 floats
-// = 130.75 KiB per wavefront of 32 envs, one wavefront per CU as StackTower.  This core is written against the accessor only.
+// the reset (one tick, no rejection), done = False, 50 steps and the contact model are StackTower's: the scene is the cube
+// core of xarm_stack_core.h (state and observation layout, row order, class key, LDS columns: its header comment) with
+// N = 4 - six cube pairs, 256 row-set classes, STATE_DIM 160, OBS_DIM 68 - plus the goal sampling below.
+// Draws: blocks 0-1 = u[0..7] = cube i xy - cubes 0-2 spawn where StackTower's do; blocks 2-3 = u[8..15] = goal i xy
+// (u[8+2i], u[9+2i]).
 #pragma once
 #include "xarm_stack_core.h"
 
 namespace xra {
-using xk::V3; using xk::mk; using xk::dot; using xk::cross; using xk::clampT; using xk::Frame; using xk::PadPoint;
-using xk::tri; using xk::symi; using xk::LDS_S; using xk::LDS_T; using xk::LDS_AHH; using xk::EnvCfg;
-using xs::StackScene; using xs::selv; using xs::ldv;
 
-constexpr int NOBJ = 4, NPAIR = 6;
-constexpr int STATE_DIM = 160, OBS_DIM = 68, ACT_DIM = 8, GOAL_DIM = 12;
-enum { K_Q = 0, K_QD = 18, K_QT = 36, K_BP = 54, K_BQ = 66, K_BV = 82, K_BW = 94, K_GOAL = 106, K_LT = 118, K_LP = 150,
-       K_STEPS = 158, K_EPISODE = 159 };
-static_assert(K_EPISODE + 1 == STATE_DIM, "state layout");
-static_assert(xm::RA_NUM_OBJ == NOBJ, "model JSON rearrange.num_obj");
-// LDS columns behind the arm's S | T | A_hh, as StackTower's (xs::TP_W / BB_W / BB_PAIR)
-constexpr int TP_W = xs::TP_W, BB_W = xs::BB_W, BB_PAIR = xs::BB_PAIR;
-constexpr int LDS_TP = xk::LDS_TBL;                     // 16 table slots
-constexpr int LDS_BB = LDS_TP + NOBJ * 4 * TP_W;        // 6 cube/cube pairs
-constexpr int LDS_CLIP = LDS_BB + NPAIR * BB_PAIR;      // 72 floats of box_box clipping scratch
-constexpr int LDS_FLOATS = LDS_CLIP + 72;               // 929 floats per lane as addressed by the core
-constexpr int LDS_SHARED = LDS_FLOATS - xk::LDS_TBL;    // 812 of them: object columns, one copy per env on the device
-static_assert(LDS_FLOATS == 929 && LDS_SHARED == 812, "DESIGN.md 17 LDS arithmetic");
-
-// pair p = (pair_a(p), pair_b(p)): 01 02 03 12 13 23
-XARM_HD constexpr int pair_a(int p) { return p < 3 ? 0 : (p < 5 ? 1 : 2); }
-XARM_HD constexpr int pair_b(int p) { return p < 3 ? p + 1 : (p < 5 ? p - 1 : 3); }
-
-template <typename T> struct Lane {
-    T q[9], qd[9], qt[9];
-    T bp[NOBJ][3], bq[NOBJ][4], bv[NOBJ][3], bw[NOBJ][3];
-    T goal[NOBJ][3];
-    T lam_t[NOBJ][8];
-    T lam_p[4];
-    T steps, episode;
-    int cls;   // row-set class of the last substep (below); scheduling hint, not part of the state
+struct Rearrange4 : xs::Cubes<4> {
+    static constexpr double OBJ_LOW[2] = {xm::RA_OBJ_LOW[0], xm::RA_OBJ_LOW[1]}, OBJ_HIGH[2] = {xm::RA_OBJ_HIGH[0], xm::RA_OBJ_HIGH[1]};
+    static constexpr double DISTANCE_THRESHOLD = xm::RA_DISTANCE_THRESHOLD;
+    static constexpr int MAX_EPISODE_STEPS = xm::RA_MAX_EPISODE_STEPS;
+    static constexpr int NDRAW = 16;
+    template <typename T> static XARM_HD void sample_goal(const T (&u)[NDRAW], xs::Lane<T, Rearrange4> &L) {
+#pragma unroll
+        for (int o = 0; o < NOBJ; o++) {   // :213-218: one goal_space xy per cube, on the table
+            L.goal[o][0] = (T)xm::RA_GOAL_LOW[0] + u[8 + 2 * o] * (T)(xm::RA_GOAL_HIGH[0] - xm::RA_GOAL_LOW[0]);
+            L.goal[o][1] = (T)xm::RA_GOAL_LOW[1] + u[9 + 2 * o] * (T)(xm::RA_GOAL_HIGH[1] - xm::RA_GOAL_LOW[1]);
+            L.goal[o][2] = (T)xm::ST_HEIGHT_OFFSET;
+        }
+    }
 };
+static_assert(xm::RA_NUM_OBJ == Rearrange4::NOBJ, "model JSON rearrange.num_obj");
+static_assert(Rearrange4::K_BQ == 66 && Rearrange4::K_BV == 82 && Rearrange4::K_BW == 94 && Rearrange4::K_GOAL == 106 && Rearrange4::K_LT == 118 &&
+              Rearrange4::K_LP == 150 && Rearrange4::K_STEPS == 158 && Rearrange4::K_EPISODE == 159, "Rearrange state layout");
+static_assert(Rearrange4::STATE_DIM == 160 && Rearrange4::OBS_DIM == 68 && Rearrange4::GOAL_DIM == 12 && Rearrange4::NCLS == 256, "Rearrange sizes");
+static_assert(Rearrange4::LDS_FLOATS == 929 && Rearrange4::LDS_SHARED == 812, "DESIGN.md 17 LDS arithmetic");
+static_assert(Rearrange4::pair_a(2) == 0 && Rearrange4::pair_b(2) == 3 && Rearrange4::pair_a(3) == 1 && Rearrange4::pair_b(3) == 2 &&
+              Rearrange4::pair_a(4) == 1 && Rearrange4::pair_b(4) == 3 && Rearrange4::pair_a(5) == 2 && Rearrange4::pair_b(5) == 3, "pairs 01 02 03 12 13 23");
 
-// ---- class-homogeneous wavefronts (xarm_stack_core.h): the step kernel visits the envs grouped by the row sets their last
-// substep used.  Key: bits 0-5 cube pairs 01 02 03 12 13 23 in contact, bit 6 / 7 a finger pad of arm 0 / 1 active - every
-// row set of this scene is one of 256 classes (StackTower's 5-bit key has three pair bits).  Same layout rule as
-// xs::class_layout over NCLS classes.
-constexpr int NCLS = 256;
-struct ClassLayout { int start[NCLS], hole_start[NCLS], hole_len[NCLS], tail_start; bool aligned; };
-XARM_HD void class_layout(const int (&hist)[NCLS], int group, ClassLayout &Y) {
-    int pos = 0, holes = 0;
-    for (int c = 1; c < NCLS; c++) {
-        Y.start[c] = pos;
-        const int end = pos + hist[c];
-        const int al = hist[c] > 0 ? (end + group - 1) / group * group : end;
-        Y.hole_start[c] = end; Y.hole_len[c] = al - end;
-        holes += al - end;
-        pos = al;
-    }
-    Y.aligned = holes <= hist[0];
-    if (!Y.aligned) {
-        pos = 0;
-        for (int c = 1; c < NCLS; c++) { Y.start[c] = pos; pos += hist[c]; Y.hole_start[c] = pos; Y.hole_len[c] = 0; }
-    }
-    Y.start[0] = 0; Y.hole_start[0] = 0; Y.hole_len[0] = 0;
-    Y.tail_start = pos;
-}
-XARM_HD int class_slot(const ClassLayout &Y, int c, int k) {
-    if (c != 0) return Y.start[c] + k;
-    for (int j = 1; j < NCLS; j++) {
-        if (k < Y.hole_len[j]) return Y.hole_start[j] + k;
-        k -= Y.hole_len[j];
-    }
-    return Y.tail_start + k;
-}
-
-template <typename T> XARM_HD T sel4(int i, T a, T b, T c, T d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
-template <typename T> XARM_HD V3<T> sel4v(int i, V3<T> a, V3<T> b, V3<T> c, V3<T> d) {
-    return mk<T>(sel4(i, a.x, b.x, c.x, d.x), sel4(i, a.y, b.y, c.y, d.y), sel4(i, a.z, b.z, c.z, d.z));
-}
-template <typename T, typename Lds>
-XARM_HD int cube_cube(V3<T> pA, const V3<T> (&A)[3], V3<T> pB, const V3<T> (&B)[3], T h, T margin, V3<T> (&pts)[4], V3<T> &nrm, T (&dist)[4], Lds lds) {
-    const T hh[3] = {h, h, h};
-    return xs::box_box<T, Lds, LDS_CLIP>(pA, A, hh, pB, B, hh, margin, pts, nrm, dist, lds);
-}
-
-// ---------------------------------------------------------------------------------------------
-// one internal substep of the two-arm / four-cube scene (dt = timeStep / numSubSteps): xs::substep with four cubes and six pairs
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg xchg) {
-    const T idt = (T)1 / dt;
-    xk::ArmDyn<T> AD;
-    xk::arm_dynamics<T, Lds, StackScene>(L.q, L.qd, dt, lds, arm, AD);
-    T (&Minv)[45] = AD.Minv;
-    T (&dq)[9] = AD.dq;
-    const V3<T> hc0 = AD.hc0, hc1 = AD.hc1, hc2 = AD.hc2;
-
-    // ---------------- cubes: frames, unconstrained motion (isotropic inertia: no gyroscopic term)
-    const T h = (T)xm::ST_CUBE_HALF;
-    const T imb = (T)(1.0 / xm::ST_CUBE_MASS), ii = (T)(1.0 / (xm::ST_CUBE_MASS * 2.0 / 3.0 * xm::ST_CUBE_HALF * xm::ST_CUBE_HALF));
-    V3<T> cb[NOBJ], Rb[NOBJ][3], vb[NOBJ], wb[NOBJ];
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-        const T x = L.bq[o][0], y = L.bq[o][1], z = L.bq[o][2], w = L.bq[o][3];
-        Rb[o][0] = mk<T>((T)1 - (T)2 * (y * y + z * z), (T)2 * (x * y + z * w), (T)2 * (x * z - y * w));
-        Rb[o][1] = mk<T>((T)2 * (x * y - z * w), (T)1 - (T)2 * (x * x + z * z), (T)2 * (y * z + x * w));
-        Rb[o][2] = mk<T>((T)2 * (x * z + y * w), (T)2 * (y * z - x * w), (T)1 - (T)2 * (x * x + y * y));
-        cb[o] = ldv(L.bp[o]);
-        vb[o] = ldv(L.bv[o]); wb[o] = ldv(L.bw[o]);
-        vb[o].z -= dt * (T)xm::GRAVITY;
-        vb[o] = vb[o] * (T)xm::LIN_DAMP_FACTOR;
-        wb[o] = wb[o] * (T)xm::ANG_DAMP_FACTOR;
-    }
-
-    // ---------------- (T) cube corners against the table top: first <= 4 active corners per cube -> LDS slots
-    const T mu_t = (T)(xm::MU_OBJECT * xm::MU_TABLE);
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-        int cnt = 0;
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-#pragma unroll
-            for (int k = 0; k < TP_W; k++) lds[LDS_TP + (o * 4 + s) * TP_W + k] = k == TP_W - 1 ? (T)-1 : (T)0;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const V3<T> r = Rb[o][0] * ((i & 1) ? h : -h) + Rb[o][1] * ((i & 2) ? h : -h) + Rb[o][2] * ((i & 4) ? h : -h);
-            const V3<T> p = cb[o] + r;
-            const bool on_table = xk::xabs(p.x) <= (T)xm::TABLE_HALF_X && xk::xabs(p.y) <= (T)xm::TABLE_HALF_Y;
-            const T dist = p.z - (T)xm::TABLE_TOP_Z;
-            const bool act = on_table && dist < (T)xm::SOLVER_MARGIN && cnt < 4;
-            if (act) {
-                const int base = LDS_TP + (o * 4 + cnt) * TP_W;
-                const T l0 = (T)xm::WARMSTART * L.lam_t[o][i];
-                const T rr = dot(r, r);
-                lds[base + 0] = r.x; lds[base + 1] = r.y; lds[base + 2] = r.z;
-                lds[base + 3] = l0; lds[base + 4] = (T)0; lds[base + 5] = (T)0;
-                lds[base + 6] = dist < (T)0 ? -(T)xm::CONTACT_ERP * dist * idt : -dist * idt;
-                lds[base + 7] = (T)1 / (imb + ii * (rr - r.z * r.z));   // n = +z
-                lds[base + 8] = (T)1 / (imb + ii * (rr - r.y * r.y));   // t1 = -y
-                lds[base + 9] = (T)1 / (imb + ii * (rr - r.x * r.x));   // t2 = +x
-                lds[base + 10] = (T)i;
-                // warm start
-                vb[o].z += imb * l0;
-                wb[o] = wb[o] + cross(r, mk<T>((T)0, (T)0, l0)) * ii;
-                cnt++;
-            }
-        }
-    }
-
-    // ---------------- (BB) cube / cube manifolds -> LDS
-    const T mu_bb = (T)(xm::MU_OBJECT * xm::MU_OBJECT);
-    bool bb_any = false, pair_act[NPAIR] = {false, false, false, false, false, false};
-#pragma unroll
-    for (int pr = 0; pr < NPAIR; pr++) {
-        const int a = pair_a(pr), b = pair_b(pr);
-        const int base = LDS_BB + pr * BB_PAIR;
-#pragma unroll
-        for (int k = 0; k < BB_PAIR; k++) lds[base + k] = (T)0;
-        const V3<T> d = cb[a] - cb[b];
-        // bounding spheres: 2 * sqrt(3) * h + margin
-        const T reach = (T)(2.0 * 1.7320508075688772 * xm::ST_CUBE_HALF + xm::SOLVER_MARGIN);
-        const bool near = dot(d, d) < reach * reach;
-        if (XARM_ANY(near)) {
-            V3<T> pts[4], nrm = mk<T>(0, 0, 1);
-            T dist[4];
-            const int np = near ? cube_cube<T, Lds>(cb[a], Rb[a], cb[b], Rb[b], h, (T)xm::SOLVER_MARGIN, pts, nrm, dist, lds) : 0;
-            if (np > 0) {
-                bb_any = true; pair_act[pr] = true;
-                const V3<T> t1 = xk::plane_space(nrm), t2 = cross(nrm, t1);
-                lds[base + 0] = nrm.x; lds[base + 1] = nrm.y; lds[base + 2] = nrm.z;
-                lds[base + 3] = t1.x; lds[base + 4] = t1.y; lds[base + 5] = t1.z;
-                for (int q = 0; q < np; q++) {
-                    const int pb = base + 6 + q * BB_W;
-                    const V3<T> rA = pts[q] - cb[a], rB = pts[q] - cb[b];
-                    const T ra2 = dot(rA, rA), rb2 = dot(rB, rB);
-                    lds[pb + 0] = rA.x; lds[pb + 1] = rA.y; lds[pb + 2] = rA.z;
-                    lds[pb + 3] = rB.x; lds[pb + 4] = rB.y; lds[pb + 5] = rB.z;
-                    lds[pb + 9] = dist[q] < (T)0 ? -(T)xm::CONTACT_ERP * dist[q] * idt : -dist[q] * idt;
-                    // point Delassus block K = (2/m + (|rA|^2 + |rB|^2)/I) 1 - (rA rA^T + rB rB^T)/I; K d for the three rows
-                    const T kd = (T)2 * imb + ii * (ra2 + rb2);
-                    const V3<T> dirs[3] = {nrm, t1, t2};
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const V3<T> Kd = dirs[k] * kd - (rA * dot(rA, dirs[k]) + rB * dot(rB, dirs[k])) * ii;
-                        lds[pb + 10 + k] = (T)1 / dot(dirs[k], Kd);
-                        lds[pb + 13 + 3 * k] = Kd.x; lds[pb + 14 + 3 * k] = Kd.y; lds[pb + 15 + 3 * k] = Kd.z;
-                    }
-                }
-            }
-        }
-    }
-
-    // ---------------- (M) motors, (L) limits, (G) gear: row constants (as PickAndPlace)
-    T m_vt[9], m_invd[9], m_lam[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        m_vt[i] = (T)xm::MOTOR_KP * (L.qt[i] - L.q[i]) * idt + (T)(1.0 - xm::MOTOR_KD) * dq[i];
-        m_invd[i] = (T)1 / Minv[tri(i, i)];
-        m_lam[i] = (T)0;
-    }
-    const T m_hi_arm = (T)(xm::ARM_MOTOR_FORCE * StackScene::TIME_STEP), m_hi_fin = (T)(StackScene::FINGER_MOTOR_FORCE * StackScene::TIME_STEP);
-    T la_vt[7], la_sg[7], la_lam[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        const T g0 = L.q[i] - (T)xm::LOWER[i], g1 = (T)xm::UPPER[i] - L.q[i];
-        const bool lo = g0 < (T)xm::LIMIT_WINDOW, hi = g1 < (T)xm::LIMIT_WINDOW;
-        const T g = lo ? g0 : g1;
-        la_sg[i] = lo ? (T)1 : (hi ? (T)-1 : (T)0);
-        la_vt[i] = g < (T)0 ? -(T)xm::GLOBAL_ERP * g * idt : -g * idt;
-        la_lam[i] = (T)0;
-    }
-    T lf_vt[2][2], lf_lam[2][2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const T g0 = L.q[7 + k] - (T)xm::LOWER[7 + k], g1 = (T)xm::UPPER[7 + k] - L.q[7 + k];
-        lf_vt[k][0] = g0 < (T)0 ? -(T)xm::GLOBAL_ERP * g0 * idt : -g0 * idt;
-        lf_vt[k][1] = g1 < (T)0 ? -(T)xm::GLOBAL_ERP * g1 * idt : -g1 * idt;
-        lf_lam[k][0] = lf_lam[k][1] = (T)0;
-    }
-    const T g_vt = -(T)(xm::GEAR_ERP * xm::GLOBAL_ERP) * (L.q[7] - L.q[8]) * idt;
-    const T g_hi = (T)(xm::GEAR_MAX_FORCE * StackScene::TIME_STEP);
-    const T g_invd = (T)1 / (Minv[tri(7, 7)] - (T)2 * Minv[tri(8, 7)] + Minv[tri(8, 8)]);
-    T g_lam = (T)0;
-
-    // ---------------- (F) finger pad spheres, each against its nearest cube
-    constexpr int NP = xk::NP;
-    static_assert(xm::NPAD == 2, "the finger block of the sweep fuses exactly two pad points per finger");
-    PadPoint<T> pp[NP];
-    int pc[NP];
-    T K21[2][9];
-#pragma unroll
-    for (int k = 0; k < 2; k++)
-#pragma unroll
-        for (int e = 0; e < 9; e++) K21[k][e] = (T)0;
-    bool pad_any = false;
-    const T pad_denom = dt * (T)xm::FINGER_CONTACT_STIFFNESS + (T)(xm::FINGER_CONTACT_DAMPING + xm::OBJECT_CONTACT_DAMPING);
-    const T pad_cfm = ((T)1 / pad_denom) * idt, pad_erp = dt * (T)xm::FINGER_CONTACT_STIFFNESS / pad_denom;
-    {
-        T wtot[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) wtot[k] = (T)0;
-        V3<T> vb_pre[NOBJ], wb_pre[NOBJ];
-#pragma unroll
-        for (int o = 0; o < NOBJ; o++) { vb_pre[o] = vb[o]; wb_pre[o] = wb[o]; }
-#pragma unroll
-        for (int idx = 0; idx < NP; idx++) {
-            const int fk = idx / xm::NPAD, j = idx % xm::NPAD;
-            const T sg = fk == 0 ? (T)1 : (T)-1;
-            PadPoint<T> &P = pp[idx];
-            const V3<T> c = AD.fo[fk] + hc0 * (T)xm::PAD_C[j][0] + hc1 * (sg * (T)xm::PAD_C[j][1]) + hc2 * (T)xm::PAD_C[j][2];
-            T dist = (T)1e30;
-            V3<T> nw = mk<T>(0, 0, 1), pw = mk<T>(0, 0, 0);
-            int co = 0;
-#pragma unroll
-            for (int o = 0; o < NOBJ; o++) {
-                // sphere against cube o, in the cube's axes
-                const V3<T> d = c - cb[o];
-                const V3<T> cl = mk<T>(dot(Rb[o][0], d), dot(Rb[o][1], d), dot(Rb[o][2], d));
-                const V3<T> ql = mk<T>(clampT(cl.x, -h, h), clampT(cl.y, -h, h), clampT(cl.z, -h, h));
-                const V3<T> dl = cl - ql;
-                const T d2 = dot(dl, dl);
-                V3<T> nl, pl;
-                T di;
-                if (d2 > (T)1e-12) {
-                    const T len = xk::xsqrt(d2);
-                    nl = dl * ((T)1 / len);
-                    di = len - (T)xm::PAD_RADIUS;
-                    pl = ql;
-                } else {
-                    const T px = h - xk::xabs(cl.x), py = h - xk::xabs(cl.y), pz = h - xk::xabs(cl.z);
-                    int k = 0;
-                    T bestp = px;
-                    if (py < bestp) { bestp = py; k = 1; }
-                    if (pz < bestp) { bestp = pz; k = 2; }
-                    const T clk = k == 0 ? cl.x : (k == 1 ? cl.y : cl.z);
-                    const T s1 = clk < (T)0 ? (T)-1 : (T)1;
-                    nl = mk<T>(k == 0 ? s1 : (T)0, k == 1 ? s1 : (T)0, k == 2 ? s1 : (T)0);
-                    di = -bestp - (T)xm::PAD_RADIUS;
-                    pl = mk<T>(k == 0 ? s1 * h : cl.x, k == 1 ? s1 * h : cl.y, k == 2 ? s1 * h : cl.z);
-                }
-                if (di < dist) {
-                    dist = di; co = o;
-                    nw = Rb[o][0] * nl.x + Rb[o][1] * nl.y + Rb[o][2] * nl.z;
-                    pw = cb[o] + Rb[o][0] * pl.x + Rb[o][1] * pl.y + Rb[o][2] * pl.z;
-                }
-            }
-            const bool act = dist < (T)xm::SOLVER_MARGIN;
-            pad_any = pad_any || act;
-            pc[idx] = co;
-            P.n = nw; P.p = pw;
-            P.t1 = xk::plane_space(P.n);
-            P.vt = dist < (T)0 ? -pad_erp * dist * idt : -dist * idt;
-            P.lam[0] = act ? (T)xm::WARMSTART * L.lam_p[idx] : (T)0;
-            P.lam[1] = P.lam[2] = (T)0;
-            P.invd[0] = P.invd[1] = P.invd[2] = (T)0;
-            P.Kn = P.Kt1 = P.Kt2 = mk<T>(0, 0, 0);
-            if (XARM_ANY(act)) {
-                const V3<T> af = hc1 * sg;
-                const V3<T> cc = sel4v(co, cb[0], cb[1], cb[2], cb[3]);
-                const V3<T> r = P.p - cc;
-                T K[3][3];
-#pragma unroll
-                for (int e = 0; e < 3; e++) {
-                    const V3<T> ej = mk<T>(e == 0 ? (T)1 : (T)0, e == 1 ? (T)1 : (T)0, e == 2 ? (T)1 : (T)0);
-                    const V3<T> mo = cross(P.p, ej);
-                    const T W[6] = {mo.x, mo.y, mo.z, ej.x, ej.y, ej.z};
-                    const T wf = xk::comp(af, e);
-                    T Y[6];
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-                        T s = lds[LDS_T + (7 + fk) * 6 + a] * wf;
-#pragma unroll
-                        for (int b = 0; b < 6; b++) s += lds[LDS_AHH + symi(a, b)] * W[b];
-                        Y[a] = s;
-                    }
-                    T yf = Minv[tri(7 + fk, 7 + fk)] * wf;
-#pragma unroll
-                    for (int b = 0; b < 6; b++) yf += lds[LDS_T + (7 + fk) * 6 + b] * W[b];
-                    const V3<T> va = mk<T>(Y[3], Y[4], Y[5]) + cross(mk<T>(Y[0], Y[1], Y[2]), P.p) + af * yf;
-                    const V3<T> vbj = ej * imb - cross(r, cross(r, ej)) * ii;
-                    K[0][e] = va.x + vbj.x; K[1][e] = va.y + vbj.y; K[2][e] = va.z + vbj.z;
-                }
-                const V3<T> t2 = cross(P.n, P.t1);
-                P.Kn = mk<T>(K[0][0] * P.n.x + K[0][1] * P.n.y + K[0][2] * P.n.z, K[1][0] * P.n.x + K[1][1] * P.n.y + K[1][2] * P.n.z,
-                             K[2][0] * P.n.x + K[2][1] * P.n.y + K[2][2] * P.n.z);
-                P.Kt1 = mk<T>(K[0][0] * P.t1.x + K[0][1] * P.t1.y + K[0][2] * P.t1.z, K[1][0] * P.t1.x + K[1][1] * P.t1.y + K[1][2] * P.t1.z,
-                              K[2][0] * P.t1.x + K[2][1] * P.t1.y + K[2][2] * P.t1.z);
-                P.Kt2 = mk<T>(K[0][0] * t2.x + K[0][1] * t2.y + K[0][2] * t2.z, K[1][0] * t2.x + K[1][1] * t2.y + K[1][2] * t2.z,
-                              K[2][0] * t2.x + K[2][1] * t2.y + K[2][2] * t2.z);
-                P.invd[0] = act ? (T)1 / (dot(P.n, P.Kn) + pad_cfm) : (T)0;
-                P.invd[1] = act ? (T)1 / dot(P.t1, P.Kt1) : (T)0;
-                P.invd[2] = act ? (T)1 / dot(t2, P.Kt2) : (T)0;
-                // warm start: +lam0 n on the finger, -lam0 n on the cube
-                const V3<T> fi = P.n * P.lam[0];
-                const V3<T> mo = cross(P.p, fi);
-                wtot[0] += mo.x; wtot[1] += mo.y; wtot[2] += mo.z;
-                wtot[3] += fi.x; wtot[4] += fi.y; wtot[5] += fi.z;
-                wtot[6 + fk] += dot(af, fi);
-                const V3<T> dv = fi * imb, dw = cross(r, fi) * ii;
-#pragma unroll
-                for (int o = 0; o < NOBJ; o++) {
-                    vb[o] = co == o ? vb[o] - dv : vb[o];
-                    wb[o] = co == o ? wb[o] - dw : wb[o];
-                }
-            }
-        }
-        if (XARM_ANY(pad_any)) {
-#pragma unroll
-            for (int r = 0; r < 9; r++) {
-                T s = Minv[symi(r, 7)] * wtot[6] + Minv[symi(r, 8)] * wtot[7];
-#pragma unroll
-                for (int k = 0; k < 6; k++) s += lds[LDS_T + r * 6 + k] * wtot[k];
-                dq[r] += s;
-            }
-            // arm-side coupling of the two pad points of each finger: velocity of the finger at its second point per unit
-            // impulse at its first one (3x3, row-major) - lets both points be swept before ONE operational-space update
-            // (as xk::substep; the cube side is applied to the cube velocities point by point)
-#pragma unroll
-            for (int fk = 0; fk < 2; fk++) {
-                const PadPoint<T> &P1 = pp[2 * fk], &P2 = pp[2 * fk + 1];
-                if (!XARM_ANY(P1.invd[0] != (T)0 && P2.invd[0] != (T)0)) continue;
-                const V3<T> af = hc1 * (fk == 0 ? (T)1 : (T)-1);
-#pragma unroll
-                for (int e = 0; e < 3; e++) {
-                    const V3<T> ej = mk<T>(e == 0 ? (T)1 : (T)0, e == 1 ? (T)1 : (T)0, e == 2 ? (T)1 : (T)0);
-                    const V3<T> mo = cross(P1.p, ej);
-                    const T W[6] = {mo.x, mo.y, mo.z, ej.x, ej.y, ej.z};
-                    const T wf = xk::comp(af, e);
-                    T Y[6];
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-                        T s = lds[LDS_T + (7 + fk) * 6 + a] * wf;
-#pragma unroll
-                        for (int b = 0; b < 6; b++) s += lds[LDS_AHH + symi(a, b)] * W[b];
-                        Y[a] = s;
-                    }
-                    T yf = Minv[tri(7 + fk, 7 + fk)] * wf;
-#pragma unroll
-                    for (int b = 0; b < 6; b++) yf += lds[LDS_T + (7 + fk) * 6 + b] * W[b];
-                    const V3<T> va = mk<T>(Y[3], Y[4], Y[5]) + cross(mk<T>(Y[0], Y[1], Y[2]), P2.p) + af * yf;
-                    K21[fk][0 * 3 + e] = va.x; K21[fk][1 * 3 + e] = va.y; K21[fk][2 * 3 + e] = va.z;
-                }
-            }
-        }
-        // the cubes also receive the warm-start impulses of the other arm's pads; afterwards both lanes must hold
-        // bit-identical cube velocities: take arm 0's sums
-#pragma unroll
-        for (int o = 0; o < NOBJ; o++) {
-            const V3<T> dv = vb[o] - vb_pre[o], dw = wb[o] - wb_pre[o];
-            vb[o] = vb[o] + mk<T>(xchg.partner(dv.x), xchg.partner(dv.y), xchg.partner(dv.z));
-            wb[o] = wb[o] + mk<T>(xchg.partner(dw.x), xchg.partner(dw.y), xchg.partner(dw.z));
-            vb[o] = mk<T>(xchg.from0(vb[o].x), xchg.from0(vb[o].y), xchg.from0(vb[o].z));
-            wb[o] = mk<T>(xchg.from0(wb[o].x), xchg.from0(wb[o].y), xchg.from0(wb[o].z));
-        }
-    }
-    // cubes touched by this arm's active pads / by the partner arm's; `seq` is wave-uniform
-    int mymask = 0;
-#pragma unroll
-    for (int idx = 0; idx < NP; idx++) mymask |= pp[idx].invd[0] != (T)0 ? (1 << pc[idx]) : 0;
-    const int othermask = (int)xchg.partner((T)mymask);
-    const bool seq = XARM_ANY_X((mymask & othermask) != 0);
-    L.cls = (pair_act[0] ? 1 : 0) | (pair_act[1] ? 2 : 0) | (pair_act[2] ? 4 : 0) | (pair_act[3] ? 8 : 0) | (pair_act[4] ? 16 : 0) |
-            (pair_act[5] ? 32 : 0) | ((arm == 0 ? mymask : othermask) != 0 ? 64 : 0) | ((arm == 1 ? mymask : othermask) != 0 ? 128 : 0);
-    XARM_LDS_FENCE();
-
-    bool la_lane = false;
-#pragma unroll
-    for (int i = 0; i < 7; i++) la_lane = la_lane || la_sg[i] != (T)0;
-    const bool la_wave = XARM_ANY(la_lane);
-    // ... and which of the seven: at 65 536 envs a handful always have ONE joint near a limit, and the launch lasts as
-    // long as its slowest wavefront - that wavefront now sweeps the one row, not all seven
-    bool la_row[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) la_row[i] = la_wave && XARM_ANY(la_sg[i] != (T)0);
-    // packed working set of the sweep (as PickAndPlace): joint velocities as 4 pairs + dq[8], full Minv columns as pairs
-    xk::Pk<T> dqp[4], MC[9][4];
-    T dq8 = dq[8], ML[9];
-#pragma unroll
-    for (int k = 0; k < 4; k++) dqp[k] = xk::mkpk<T>(dq[2 * k], dq[2 * k + 1]);
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) MC[i][k] = xk::mkpk<T>(Minv[symi(2 * k, i)], Minv[symi(2 * k + 1, i)]);
-        ML[i] = Minv[symi(8, i)];
-    }
-#define XARM_DQ(i) ((i) == 8 ? dq8 : (((i) & 1) ? xk::pkhi(dqp[(i) >> 1]) : xk::pklo(dqp[(i) >> 1])))
-#define XARM_DQ_AXPY(col, dl_) do { _Pragma("unroll") for (int k_ = 0; k_ < 4; k_++) dqp[k_] = xk::pkfma(MC[col][k_], (dl_), dqp[k_]); dq8 += ML[col] * (dl_); } while (0)
-    // ---------------- projected Gauss-Seidel: T, BB, (M L G) of this lane's arm, F arm 0, F arm 1
-    const T mu_p = (T)(xm::MU_OBJECT * xm::MU_FINGER);
-#pragma unroll 1
-    for (int it = 0; it < XK_SWEEP_ITERS; it++) {
-        XARM_LDS_FENCE();
-        // (T) n = +z, t1 = -y, t2 = +x
-#pragma unroll
-        for (int o = 0; o < NOBJ; o++)
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                // no wave-level skip (1/diag = 0 makes an empty slot a no-op): the slots of different cubes and the arm
-                // rows are independent chains, and in one basic block they fill each other's dependency stalls
-                const int base = LDS_TP + (o * 4 + s) * TP_W;
-                const T e0 = lds[base + 7];
-                const V3<T> r = mk<T>(lds[base + 0], lds[base + 1], lds[base + 2]);
-                const T e1 = lds[base + 8], e2 = lds[base + 9];
-                T l0 = lds[base + 3], l1 = lds[base + 4], l2 = lds[base + 5];
-                V3<T> v = vb[o], w = wb[o];
-                T dl = (lds[base + 6] - (v.z + w.x * r.y - w.y * r.x)) * e0;
-                T nl = l0 + dl;
-                nl = xk::smax0(nl);
-                dl = nl - l0; l0 = nl;
-                v.z += imb * dl;
-                w.x += ii * r.y * dl; w.y -= ii * r.x * dl;
-                const T lim = mu_t * l0;
-                dl = (v.y + w.z * r.x - w.x * r.z) * e1;        // jv = -u.y, target 0
-                nl = xk::sclamp(l1 + dl, -lim, lim);
-                dl = nl - l1; l1 = nl;
-                v.y -= imb * dl;
-                w.x += ii * r.z * dl; w.z -= ii * r.x * dl;
-                dl = -(v.x + w.y * r.z - w.z * r.y) * e2;
-                nl = xk::sclamp(l2 + dl, -lim, lim);
-                dl = nl - l2; l2 = nl;
-                v.x += imb * dl;
-                w.y += ii * r.z * dl; w.z -= ii * r.y * dl;
-                vb[o] = v; wb[o] = w;
-                lds[base + 3] = l0; lds[base + 4] = l1; lds[base + 5] = l2;
-            }
-        // the arm rows (M L G) only touch this lane's joints and the T / BB rows only the cubes: issued next to the table
-        // slots (one basic block) they fill each other's dependency stalls; the result is the oracle's T, BB, MLG order
-        // (M) velocity-level PD motors
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            const T hi = i < 7 ? m_hi_arm : m_hi_fin;
-            T dl = (m_vt[i] - XARM_DQ(i)) * m_invd[i];
-            const T nl = xk::sclamp(m_lam[i] + dl, -hi, hi);
-            dl = nl - m_lam[i];
-            m_lam[i] = nl;
-            XARM_DQ_AXPY(i, dl);
-        }
-        // (L) joint limits
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            if (!la_row[i]) continue;   // wave-uniform, decided once per substep
-            const T sg = la_sg[i];
-            T dl = (la_vt[i] - sg * XARM_DQ(i)) * (sg != (T)0 ? m_invd[i] : (T)0);
-            T nl = la_lam[i] + dl;
-            nl = xk::smax0(nl);
-            dl = (nl - la_lam[i]) * sg;
-            la_lam[i] = nl;
-            XARM_DQ_AXPY(i, dl);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; k++)
-#pragma unroll
-            for (int side = 0; side < 2; side++) {
-                const T sg = side == 0 ? (T)1 : (T)-1;
-                T dl = (lf_vt[k][side] - sg * XARM_DQ(7 + k)) * m_invd[7 + k];
-                T nl = lf_lam[k][side] + dl;
-                nl = xk::smax0(nl);
-                dl = (nl - lf_lam[k][side]) * sg;
-                lf_lam[k][side] = nl;
-                XARM_DQ_AXPY(7 + k, dl);
-            }
-        // (G) gear row
-        {
-            T dl = (g_vt - (XARM_DQ(7) - dq8)) * g_invd;
-            const T nl = xk::sclamp(g_lam + dl, -g_hi, g_hi);
-            dl = nl - g_lam;
-            g_lam = nl;
-            XARM_DQ_AXPY(7, dl);
-            XARM_DQ_AXPY(8, -dl);
-        }
-        // (BB) cube / cube points
-        if (XARM_ANY(bb_any)) {
-#pragma unroll
-            for (int pr = 0; pr < NPAIR; pr++) {
-                const int a = pair_a(pr), b = pair_b(pr);
-                const int base = LDS_BB + pr * BB_PAIR;
-                if (!XARM_ANY(pair_act[pr])) continue;
-                const V3<T> n = mk<T>(lds[base + 0], lds[base + 1], lds[base + 2]), t1 = mk<T>(lds[base + 3], lds[base + 4], lds[base + 5]);
-                const V3<T> t2 = cross(n, t1);
-                // all four slots of an active pair, unrolled and unconditional (an empty slot is a no-op): the LDS reads
-                // of the next point are issued while the current one is solved
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int pb = base + 6 + q * BB_W;
-                    const T e0 = lds[pb + 10];
-                    const V3<T> rA = mk<T>(lds[pb + 0], lds[pb + 1], lds[pb + 2]), rB = mk<T>(lds[pb + 3], lds[pb + 4], lds[pb + 5]);
-                    T lam[3] = {lds[pb + 6], lds[pb + 7], lds[pb + 8]};
-                    const T ed[3] = {e0, lds[pb + 11], lds[pb + 12]};
-                    const T vt = lds[pb + 9];
-                    // relative velocity at the point once, then kept current through K d per row; one impulse at the end
-                    V3<T> u = vb[a] + cross(wb[a], rA) - vb[b] - cross(wb[b], rB);
-                    V3<T> f = mk<T>(0, 0, 0);
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const V3<T> d = k == 0 ? n : (k == 1 ? t1 : t2);
-                        const V3<T> Kd = mk<T>(lds[pb + 13 + 3 * k], lds[pb + 14 + 3 * k], lds[pb + 15 + 3 * k]);
-                        T dl = ((k == 0 ? vt : (T)0) - dot(d, u)) * ed[k];
-                        const T lim = mu_bb * lam[0];
-                        const T nl = k == 0 ? xk::smax0(lam[0] + dl) : xk::sclamp(lam[k] + dl, -lim, lim);
-                        dl = nl - lam[k];
-                        lam[k] = nl;
-                        u = u + Kd * dl;
-                        f = f + d * dl;
-                    }
-                    vb[a] = vb[a] + f * imb; wb[a] = wb[a] + cross(rA, f) * ii;
-                    vb[b] = vb[b] - f * imb; wb[b] = wb[b] - cross(rB, f) * ii;
-                    lds[pb + 6] = lam[0]; lds[pb + 7] = lam[1]; lds[pb + 8] = lam[2];
-                }
-            }
-        }
-        // (F) pad points.  Sequential form: arm 0's pads, hand the cube velocities over, arm 1's pads.  When no cube
-        // of any environment in the wavefront is touched by both arms the two sweeps act on disjoint variables and
-        // commute, so both lanes sweep at once (phase 0) and each cube is then taken from the lane that touched it.
-        // One instruction stream serves both forms (a second copy of the sweep pushes the cube velocities to scratch).
-#pragma unroll
-        for (int ph = 0; ph < 2; ph++) {
-            // sequential: phase 0 = arm 0, phase 1 = arm 1; concurrent: every lane sweeps in phase 0, phase 1 is empty
-            const bool mine = seq ? arm == ph : ph == 0;
-            if (XARM_ANY(pad_any && mine)) {
-                T y[6], yf[2], wtot[8];
-#pragma unroll
-                for (int k = 0; k < 6; k++) {
-                    T s = (T)0;
-#pragma unroll
-                    for (int i = 0; i < 7; i++) s += lds[LDS_S + i * 6 + k] * XARM_DQ(i);
-                    y[k] = s;
-                }
-                yf[0] = XARM_DQ(7); yf[1] = dq8;
-#pragma unroll
-                for (int k = 0; k < 8; k++) wtot[k] = (T)0;
-#pragma unroll
-                for (int fk = 0; fk < 2; fk++) {
-                    if (!XARM_ANY((pp[2 * fk].invd[0] != (T)0 || pp[2 * fk + 1].invd[0] != (T)0) && mine)) continue;
-                    const V3<T> af = hc1 * (fk == 0 ? (T)1 : (T)-1);
-                    const V3<T> yw = mk<T>(y[0], y[1], y[2]);
-                    const V3<T> base = mk<T>(y[3], y[4], y[5]) + af * yf[fk];
-                    V3<T> fsum = mk<T>(0, 0, 0), msum = mk<T>(0, 0, 0), f1 = mk<T>(0, 0, 0);   // sum f, sum p x f, the first point's impulse
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        PadPoint<T> &P = pp[2 * fk + j];
-                        const int co = pc[2 * fk + j];
-                        const T e0 = mine ? P.invd[0] : (T)0, e1 = mine ? P.invd[1] : (T)0, e2 = mine ? P.invd[2] : (T)0;
-                        const V3<T> r = P.p - sel4v(co, cb[0], cb[1], cb[2], cb[3]);
-                        const V3<T> vc = sel4v(co, vb[0], vb[1], vb[2], vb[3]), wc = sel4v(co, wb[0], wb[1], wb[2], wb[3]);
-                        const V3<T> t2 = cross(P.n, P.t1);
-                        V3<T> u = base + cross(yw, P.p) - vc - cross(wc, r);
-                        if (j == 1) // effect on the finger of the impulse just applied at its first point (the cube side went into vb / wb)
-                            u = u + mk<T>(K21[fk][0] * f1.x + K21[fk][1] * f1.y + K21[fk][2] * f1.z,
-                                          K21[fk][3] * f1.x + K21[fk][4] * f1.y + K21[fk][5] * f1.z,
-                                          K21[fk][6] * f1.x + K21[fk][7] * f1.y + K21[fk][8] * f1.z);
-                        T dl = (P.vt - pad_cfm * P.lam[0] - dot(P.n, u)) * e0;
-                        T nl = P.lam[0] + dl;
-                        nl = xk::smax0(nl);
-                        dl = nl - P.lam[0];
-                        P.lam[0] = nl;
-                        V3<T> fi = P.n * dl;
-                        u = u + P.Kn * dl;
-                        const T lim = mu_p * P.lam[0];
-                        dl = -dot(P.t1, u) * e1;
-                        nl = xk::sclamp(P.lam[1] + dl, -lim, lim);
-                        dl = nl - P.lam[1];
-                        P.lam[1] = nl;
-                        fi = fi + P.t1 * dl;
-                        u = u + P.Kt1 * dl;
-                        dl = -dot(t2, u) * e2;
-                        nl = xk::sclamp(P.lam[2] + dl, -lim, lim);
-                        dl = nl - P.lam[2];
-                        P.lam[2] = nl;
-                        fi = fi + t2 * dl;
-                        if (j == 0) f1 = fi;
-                        fsum = fsum + fi;
-                        msum = msum + cross(P.p, fi);
-                        // -fi on the cube, at once: the finger's second point may press on the same cube
-                        const V3<T> dv = fi * imb, dw = cross(r, fi) * ii;
-#pragma unroll
-                        for (int o = 0; o < NOBJ; o++) {
-                            vb[o] = co == o ? vb[o] - dv : vb[o];
-                            wb[o] = co == o ? wb[o] - dw : wb[o];
-                        }
-                    }
-                    // ONE operational-space update for the finger: +fsum on finger fk, moment msum about the world origin
-                    const T W[6] = {msum.x, msum.y, msum.z, fsum.x, fsum.y, fsum.z};
-                    const T wf = dot(af, fsum);
-#pragma unroll
-                    for (int a = 0; a < 6; a++) {
-                        T s = lds[LDS_T + (7 + fk) * 6 + a] * wf;
-#pragma unroll
-                        for (int b = 0; b < 6; b++) s += lds[LDS_AHH + symi(a, b)] * W[b];
-                        y[a] += s;
-                    }
-#pragma unroll
-                    for (int k2 = 0; k2 < 2; k2++) {
-                        T s = Minv[symi(7 + k2, 7 + fk)] * wf;
-#pragma unroll
-                        for (int b = 0; b < 6; b++) s += lds[LDS_T + (7 + k2) * 6 + b] * W[b];
-                        yf[k2] += s;
-                    }
-#pragma unroll
-                    for (int b = 0; b < 6; b++) wtot[b] += W[b];
-                    wtot[6 + fk] += wf;
-                }
-                XARM_DQ_AXPY(7, wtot[6]);
-                XARM_DQ_AXPY(8, wtot[7]);
-#pragma unroll
-                for (int k = 0; k < 6; k++) {
-#pragma unroll
-                    for (int r2 = 0; r2 < 4; r2++)
-                        dqp[r2] = xk::pkfma(xk::mkpk<T>(lds[LDS_T + (2 * r2) * 6 + k], lds[LDS_T + (2 * r2 + 1) * 6 + k]), wtot[k], dqp[r2]);
-                    dq8 += lds[LDS_T + 8 * 6 + k] * wtot[k];
-                }
-            }
-            // hand the cube velocities over.  Three wave-uniform cases, the same values as one select cascade over all of them (which cost
-            // 36 instructions per cube and sweep in every wavefront, pads or not): sequential - take arm 0's after phase 0, arm 1's after
-            // phase 1; concurrent with a pad somewhere in the wavefront - take the partner's where only it touched; no pad at all - nothing
-            if (ph == 0) {
-                if (seq) {
-#pragma unroll
-                    for (int o = 0; o < NOBJ; o++) {
-                        vb[o] = mk<T>(xchg.from0(vb[o].x), xchg.from0(vb[o].y), xchg.from0(vb[o].z));
-                        wb[o] = mk<T>(xchg.from0(wb[o].x), xchg.from0(wb[o].y), xchg.from0(wb[o].z));
-                    }
-                } else if (XARM_ANY(mymask != 0 || othermask != 0)) {
-#pragma unroll
-                    for (int o = 0; o < NOBJ; o++) {
-                        const bool take = ((othermask >> o) & 1) != 0;   // the partner lane touched cube o, this one did not
-                        const V3<T> pv = mk<T>(xchg.partner(vb[o].x), xchg.partner(vb[o].y), xchg.partner(vb[o].z));
-                        const V3<T> pw = mk<T>(xchg.partner(wb[o].x), xchg.partner(wb[o].y), xchg.partner(wb[o].z));
-                        vb[o] = selv(take, pv, vb[o]);
-                        wb[o] = selv(take, pw, wb[o]);
-                    }
-                }
-            } else if (seq) {
-#pragma unroll
-                for (int o = 0; o < NOBJ; o++) {
-                    vb[o] = mk<T>(xchg.from1(vb[o].x), xchg.from1(vb[o].y), xchg.from1(vb[o].z));
-                    wb[o] = mk<T>(xchg.from1(wb[o].x), xchg.from1(wb[o].y), xchg.from1(wb[o].z));
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) { dq[2 * k] = xk::pklo(dqp[k]); dq[2 * k + 1] = xk::pkhi(dqp[k]); }
-    dq[8] = dq8;
-#undef XARM_DQ
-#undef XARM_DQ_AXPY
-    XARM_LDS_FENCE();
-
-    // ---------------- store warm-start impulses, integrate (semi-implicit Euler)
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) L.lam_t[o][i] = (T)0;
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            const int base = LDS_TP + (o * 4 + s) * TP_W;
-            const int id = (int)lds[base + 10];
-            const T l0 = lds[base + 3];
-#pragma unroll
-            for (int i = 0; i < 8; i++) L.lam_t[o][i] = id == i ? l0 : L.lam_t[o][i];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NP; i++) L.lam_p[i] = pp[i].invd[0] != (T)0 ? pp[i].lam[0] : (T)0;
-#pragma unroll
-    for (int i = 0; i < 9; i++) { L.qd[i] = dq[i]; L.q[i] += dt * dq[i]; }
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-        L.bp[o][0] += dt * vb[o].x; L.bp[o][1] += dt * vb[o].y; L.bp[o][2] += dt * vb[o].z;
-        T ang = xk::xsqrt(dot(wb[o], wb[o]));
-        if (ang * dt > (T)0.7853981633974483) ang = (T)0.7853981633974483 * idt;
-        T sw, cw;
-        xk::xsincos((T)0.5 * ang * dt, sw, cw);
-        const T k = ang < (T)0.001 ? (T)0.5 * dt - dt * dt * dt * (T)0.020833333333 * ang * ang : sw / ang;
-        const V3<T> ax = wb[o] * k;
-        const T x = L.bq[o][0], y = L.bq[o][1], z = L.bq[o][2], w0 = L.bq[o][3];
-        const T nx = cw * x + ax.x * w0 + ax.y * z - ax.z * y;
-        const T ny = cw * y + ax.y * w0 + ax.z * x - ax.x * z;
-        const T nz = cw * z + ax.z * w0 + ax.x * y - ax.y * x;
-        const T nw = cw * w0 - ax.x * x - ax.y * y - ax.z * z;
-        const T inv = (T)1 / xk::xsqrt(nx * nx + ny * ny + nz * nz + nw * nw);
-        L.bq[o][0] = nx * inv; L.bq[o][1] = ny * inv; L.bq[o][2] = nz * inv; L.bq[o][3] = nw * inv;
-        L.bv[o][0] = vb[o].x; L.bv[o][1] = vb[o].y; L.bv[o][2] = vb[o].z;
-        L.bw[o][0] = wb[o].x; L.bw[o][1] = wb[o].y; L.bw[o][2] = wb[o].z;
-    }
-}
-
-// p.stepSimulation() with numSubSteps = 15
-template <typename T, typename Lds, typename Xchg> XARM_HD void tick(Lane<T> &L, Lds lds, int arm, Xchg x) {
-    const T dt = (T)(xm::ST_TIME_STEP / xm::ST_N_SUBSTEPS);
-#pragma unroll 1
-    for (int k = 0; k < xm::ST_N_SUBSTEPS; k++) substep<T, Lds, Xchg>(L, dt, lds, arm, x);
-}
-
-// the 8 per-arm observation entries (:170-181): hand COM position and velocity, finger q, qd (as xs::arm_obs)
-template <typename T> XARM_HD void arm_obs(const Lane<T> &L, int arm, T (&o)[8]) {
-    Frame<T> f = StackScene::base_frame<T>(arm);
-    V3<T> w = mk<T>(0, 0, 0), v = mk<T>(0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        xk::fk_advance(f, i, L.q[i]);
-        w = w + f.c2 * L.qd[i];
-        v = v + cross(f.o, f.c2) * L.qd[i];
-    }
-    const V3<T> hp = f.o + f.c0 * (T)xm::HAND_COM[0] + f.c1 * (T)xm::HAND_COM[1] + f.c2 * (T)xm::HAND_COM[2];
-    const V3<T> hv = v + cross(w, hp);
-    o[0] = hp.x; o[1] = hp.y; o[2] = hp.z;
-    o[3] = hv.x; o[4] = hv.y; o[5] = hv.z;
-    o[6] = L.q[7]; o[7] = L.qd[7];
-}
-
-// draws 0-7: cube xy (cube i: 2i, 2i+1), 8-15: goal xy (goal i: 8 + 2i, 9 + 2i)
-template <typename T> XARM_HD void draws(const EnvCfg &cfg, int64_t env, int64_t episode, T (&u)[16]) {
-    const uint64_t gid = (uint64_t)(cfg.env_id_offset + env);
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        uint32_t o[4];
-        xk::philox(cfg.seed, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)episode, (uint32_t)b, o);
-#pragma unroll
-        for (int k = 0; k < 4; k++) u[b * 4 + k] = xk::u01<T>(o[k]);
-    }
-}
-template <typename T> XARM_HD void sample_objects(const T (&u)[16], Lane<T> &L) {
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-        L.bp[o][0] = (T)xm::RA_OBJ_LOW[0] + u[2 * o] * (T)(xm::RA_OBJ_HIGH[0] - xm::RA_OBJ_LOW[0]);
-        L.bp[o][1] = (T)xm::RA_OBJ_LOW[1] + u[2 * o + 1] * (T)(xm::RA_OBJ_HIGH[1] - xm::RA_OBJ_LOW[1]);
-        L.bp[o][2] = (T)xm::ST_HEIGHT_OFFSET;
-        L.bq[o][0] = L.bq[o][1] = L.bq[o][2] = (T)0; L.bq[o][3] = (T)1;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { L.bv[o][k] = (T)0; L.bw[o][k] = (T)0; }
-#pragma unroll
-        for (int k = 0; k < 8; k++) L.lam_t[o][k] = (T)0;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) L.lam_p[k] = (T)0;
-}
-template <typename T> XARM_HD void sample_goal(const T (&u)[16], Lane<T> &L) {
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {   // :213-218: one goal_space xy per cube, on the table
-        L.goal[o][0] = (T)xm::RA_GOAL_LOW[0] + u[8 + 2 * o] * (T)(xm::RA_GOAL_HIGH[0] - xm::RA_GOAL_LOW[0]);
-        L.goal[o][1] = (T)xm::RA_GOAL_LOW[1] + u[9 + 2 * o] * (T)(xm::RA_GOAL_HIGH[1] - xm::RA_GOAL_LOW[1]);
-        L.goal[o][2] = (T)xm::ST_HEIGHT_OFFSET;
-    }
-}
-template <typename T> XARM_HD void teleport_arm(Lane<T> &L) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) { L.q[i] = (T)xm::ST_JOINT_INIT_POS[i]; L.qd[i] = (T)0; }
-}
-template <typename T> XARM_HD void lane_init(const EnvCfg &cfg, int64_t env, Lane<T> &L) {
-    teleport_arm(L);
-#pragma unroll
-    for (int i = 0; i < 9; i++) L.qt[i] = L.q[i];   // no motor command yet: hold the init pose
-    L.steps = L.episode = (T)0;
-    L.cls = 0;
-    T u[16];
-    draws(cfg, env, 0, u);
-    sample_objects(u, L);
-    sample_goal(u, L);
-}
-// _reset_sim + _sample_goal (:201-218)
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void lane_reset(const EnvCfg &cfg, int64_t env, Lane<T> &L, int arm, Lds lds, Xchg x) {
-    const int64_t episode = (int64_t)L.episode + 1;
-    T u[16];
-    teleport_arm(L);
-    draws(cfg, env, episode, u);
-    sample_objects(u, L);
-    tick<T, Lds, Xchg>(L, lds, arm, x);   // with the motor targets of the last step still set (:210)
-    sample_goal(u, L);
-    L.steps = (T)0;
-    L.episode = (T)episode;
-}
-// |ag - g| over the whole 12-vector (:124-127)
-template <typename T> XARM_HD T goal_distance(const Lane<T> &L) {
-    T d2 = (T)0;
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { const T d = L.bp[o][k] - L.goal[o][k]; d2 += d * d; }
-    return xk::xsqrt(d2);
-}
-// act = this arm's 4 action entries (:142-162, as StackTower)
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void lane_step(const EnvCfg &cfg, Lane<T> &L, int arm, const T (&act)[4], T &reward, bool &done, bool &success, Lds lds, Xchg x) {
-    L.steps += (T)1;
-    T a[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) a[k] = clampT(act[k], (T)-1, (T)1);
-    Frame<T> f = StackScene::base_frame<T>(arm);
-#pragma unroll
-    for (int i = 0; i < 7; i++) xk::fk_advance(f, i, L.q[i]);
-    const V3<T> cur = f.o;
-    const T sc = (T)(xm::ST_MAX_VEL * xm::ST_ACTION_DT);
-    const V3<T> lo = arm == 0 ? mk<T>((T)xm::ST_POS_LOW[0][0], (T)xm::ST_POS_LOW[0][1], (T)xm::ST_POS_LOW[0][2])
-                              : mk<T>((T)xm::ST_POS_LOW[1][0], (T)xm::ST_POS_LOW[1][1], (T)xm::ST_POS_LOW[1][2]);
-    const V3<T> hi = arm == 0 ? mk<T>((T)xm::ST_POS_HIGH[0][0], (T)xm::ST_POS_HIGH[0][1], (T)xm::ST_POS_HIGH[0][2])
-                              : mk<T>((T)xm::ST_POS_HIGH[1][0], (T)xm::ST_POS_HIGH[1][1], (T)xm::ST_POS_HIGH[1][2]);
-    const V3<T> target = mk<T>(clampT(cur.x + a[0] * sc, lo.x, hi.x), clampT(cur.y + a[1] * sc, lo.y, hi.y), clampT(cur.z + a[2] * sc, lo.z, hi.z));
-    const T g = clampT(L.q[7] + a[3] * (T)(xm::ST_ACTION_DT * xm::ST_MAX_GRIPPER_VEL), (T)xm::ST_GRIPPER_LOW, (T)xm::ST_GRIPPER_HIGH);
-    T qa[7], qo[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) qa[i] = L.q[i];
-    xk::ik_arm<T, xm::ST_N_SUBSTEPS>(qa, target, qo, StackScene::base_frame<T>(arm));   // maxNumIterations = n_substeps (:154-155)
-#pragma unroll
-    for (int i = 0; i < 7; i++) L.qt[i] = qo[i];
-    L.qt[7] = L.qt[8] = g;
-    tick<T, Lds, Xchg>(L, lds, arm, x);
-    const T dist = goal_distance(L);
-    success = dist < (T)xm::RA_DISTANCE_THRESHOLD;                                   // :220-222
-    reward = cfg.reward_type == 0 ? (dist > (T)xm::RA_DISTANCE_THRESHOLD ? (T)-1 : (T)0) : -dist;   // :124-129
-    done = (int)L.steps == xm::RA_MAX_EPISODE_STEPS;                                // step() itself never ends (:111)
-}
+// the namespace-level names, and the core's entry points under this namespace (the scene is deduced from the Lane)
+XARM_CUBE_SCENE_NAMES(Rearrange4);
+template <typename T> using Lane = xs::Lane<T, Rearrange4>;
+using xs::lane_init; using xs::lane_step; using xs::lane_reset; using xs::arm_obs; using xs::class_layout; using xs::class_slot;
 
 } // namespace xra

@@ -1,33 +1,66 @@
-// XarmPDStackTower-v0 on the device: two xarm7_pd arms (one lane each, as in the Handover scene) and three cubes.
+// The two-arm cube scenes on the device: two xarm7_pd arms (one lane each, as in the Handover scene) and N cubes.  One core,
+// templated on a scene description: XarmPDStackTower-v0 is xs::Tower3 (below), XarmRearrange-v0 is xra::Rearrange4
+// (xarm_rearrange_core.h: N = 4 plus its goal sampling).
 //
-// Reference: /root/reference/gym_xarm/envs/xarm_stack_tower.py (step :101-113, _set_action :142-162, _get_obs
+// Reference: gym_xarm/envs/xarm_stack_tower.py (step :101-113, _set_action :142-162, _get_obs
 // :164-199, _reset_sim :201-210, _sample_goal :212-219, compute_reward :124-129).  The contact model is the one the
 // CPU oracle states (oracle/xarm_oracle_stack.inc.c, model JSON "stack_tower"._contact_model): cube corners against
 // the table top, cube/cube by SAT + face clipping or one edge/edge point, each pad sphere against its nearest cube.
 //
-// Data placement: the arm part (arm_dynamics) is the PickAndPlace code and uses the same LDS columns; the object
-// contact data (12 table slots, 3 x 4 cube/cube points) lives in further lane-private LDS columns - this scene's
-// BASELINE size is 8192 envs per GPU = one wavefront per CU, so a wavefront may take ~151 KB of the CU's 160 KB.
-// Both lanes of an env compute the object-only rows redundantly (bit-identical); the cube velocities are handed from
-// lane to lane between the two finger phases of a sweep exactly as the Handover scene hands over its stick.
+// Everything that depends on the cube count N is derived in Cubes<N> below:
+//   State (SoA, one float per field and env): q 0-17, qd 18-35, qt 36-53 (arm a: 9 a .. 9 a + 8), then from 54 cube positions
+//     3N, quaternions (x y z w) 4N, linear velocities 3N, angular velocities 3N, goals 3N, table warm starts lam_t[N][8], pad
+//     warm starts lam_p[2][4], steps, episode.
+//   Observation (_get_obs :164-199): cube pos 3N, quat 4N, v 3N, w 3N, then per arm hand COM pos 3, vel 3, finger q, finger qd.
+//     Achieved goal = the 3N cube coordinates, desired goal = the 3N goal coordinates.
+//   Row order of a substep (projected Gauss-Seidel): T cubes 0..N-1; BB pairs in lexicographic order (N = 3: 01 02 12, N = 4:
+//     01 02 03 12 13 23); M L G of this lane's arm; F arm 0, F arm 1.  With one of four cubes parked away from everything the
+//     rows left over are the three-cube scene's, in its order.
+//   Reset: both arms to joint_init_pos, N cubes uniform in the object box (identity orientation, no rejection), ONE tick with
+//     the previous motor targets, then the goals.  Draws (Philox keyed by seed, global env id, episode; block b gives 4
+//     uniforms): u[2i], u[2i+1] = cube i xy; what follows is the scene's (Sc::sample_goal).
+//
+// Data placement: the arm part (arm_dynamics) is the PickAndPlace code and uses the same LDS columns; the object contact
+// data (4N table slots, N(N-1)/2 x 4 cube/cube points, 72 floats of clipping scratch) lives in further columns behind them,
+// LDS_FLOATS = 117 + 44 N + 94 N(N-1)/2 + 72 per lane as the core addresses them: 603 for N = 3, 929 for N = 4.  Both lanes
+// of an env compute the object-only rows redundantly (bit-identical); the cube velocities are handed from lane to lane
+// between the two finger phases of a sweep exactly as the Handover scene hands over its stick.  The core is written against
+// an accessor only.  StackTower's kernels give every lane its private copy (DevLds: 603 x 64 floats = 151 KB per wavefront;
+// its BASELINE size is 8192 envs per GPU = one wavefront per CU, so a wavefront may take that much of the CU's 160 KB).
+// 929 x 64 floats = 232 KiB would not fit, so Rearrange's kernels keep ONE copy per env of the LDS_SHARED = 812 object
+// columns, which hold the same numbers in both lanes (RaLds in xarm_k_rearrange.hip, as two-stick Handover's Ho2Lds):
+// 117 x 64 + 812 x 32 floats = 130.75 KiB per wavefront of 32 envs, one wavefront per CU again.
 #pragma once
+#include <utility>
 #include "xarm_core.h"
 
 namespace xs {
 using xk::V3; using xk::mk; using xk::dot; using xk::cross; using xk::clampT; using xk::Frame; using xk::PadPoint;
 using xk::tri; using xk::symi; using xk::LDS_S; using xk::LDS_T; using xk::LDS_AHH; using xk::EnvCfg;
 
-constexpr int NOBJ = 3, NPAIR = 3;
-constexpr int STATE_DIM = 136, OBS_DIM = 55, ACT_DIM = 8, GOAL_DIM = 9;
-enum { K_Q = 0, K_QD = 18, K_QT = 36, K_BP = 54, K_BQ = 63, K_BV = 75, K_BW = 84, K_GOAL = 93, K_LT = 102, K_LP = 126,
-       K_STEPS = 134, K_EPISODE = 135 };
 // extra LDS columns behind the arm's S | T | A_hh (the arm's table-slot columns are reused)
 constexpr int TP_W = 11;                      // r3 lam3 vt invd3 id
-constexpr int LDS_TP = xk::LDS_TBL;           // 12 table slots
 constexpr int BB_W = 22, BB_PAIR = 6 + 4 * BB_W; // per pair: n3 t1_3, then 4 x (rA3 rB3 lam3 vt invd3 Kn3 Kt1_3 Kt2_3)
-constexpr int LDS_BB = LDS_TP + NOBJ * 4 * TP_W;
-constexpr int LDS_CLIP = LDS_BB + NPAIR * BB_PAIR;     // 3 x 8 x 3 floats: polygon ping-pong + kept points of cube_cube
-constexpr int LDS_FLOATS = LDS_CLIP + 72;              // 603 floats = 2412 B per lane, 151 KB per wavefront
+
+// layout of a scene with N cubes; a scene description (Tower3 below) derives from it and adds what is its own: the object and
+// goal boxes, the success threshold, the episode length, NDRAW uniforms per reset and sample_goal
+template <int N> struct Cubes {
+    static constexpr int NOBJ = N, NPAIR = N * (N - 1) / 2;
+    static constexpr int NCLS = 1 << (NPAIR + 2);   // row-set classes: pair bits 0..NPAIR-1, pad bits NPAIR and NPAIR+1 (class_layout)
+    enum { K_Q = 0, K_QD = 18, K_QT = 36, K_BP = 54, K_BQ = K_BP + 3 * N, K_BV = K_BQ + 4 * N, K_BW = K_BV + 3 * N, K_GOAL = K_BW + 3 * N,
+           K_LT = K_GOAL + 3 * N, K_LP = K_LT + 8 * N, K_STEPS = K_LP + 8, K_EPISODE = K_STEPS + 1 };
+    static constexpr int STATE_DIM = K_EPISODE + 1, OBS_DIM = 13 * N + 16, ACT_DIM = 8, GOAL_DIM = 3 * N;
+    enum { O_BP = 0, O_BQ = 3 * N, O_BV = 7 * N, O_BW = 10 * N, O_ARM = 13 * N };   // observation offsets
+    static constexpr int LDS_TP = xk::LDS_TBL;                  // 4N table slots
+    static constexpr int LDS_BB = LDS_TP + N * 4 * TP_W;        // NPAIR cube/cube pairs
+    static constexpr int LDS_CLIP = LDS_BB + NPAIR * BB_PAIR;   // 3 x 8 x 3 floats: polygon ping-pong + kept points of box_box
+    static constexpr int LDS_FLOATS = LDS_CLIP + 72;            // per lane as addressed by the core
+    static constexpr int LDS_SHARED = LDS_FLOATS - xk::LDS_TBL; // the object columns among them
+    // pair p = cubes (pair_a(p), pair_b(p)), lexicographic
+    // (conditionals, no loop: in the unrolled pair loops they fold as soon as p is a constant)
+    template <int A = 0> static XARM_HD constexpr int pair_a(int p) { if constexpr (A == N - 2) return A; else return p < N - 1 - A ? A : pair_a<A + 1>(p - (N - 1 - A)); }
+    template <int A = 0> static XARM_HD constexpr int pair_b(int p) { if constexpr (A == N - 2) return A + 1 + p; else return p < N - 1 - A ? A + 1 + p : pair_b<A + 1>(p - (N - 1 - A)); }
+};
 
 struct StackScene {
     static constexpr int NARMS = 2;
@@ -45,33 +78,57 @@ struct StackScene {
 };
 
 // one lane = one arm: q/qd/qt/lam_p are the arm's, everything else is the lane's copy of the shared state
-template <typename T> struct Lane {
+struct Tower3;
+template <typename T, typename Sc = Tower3> struct Lane {
+    static constexpr int NOBJ = Sc::NOBJ;
     T q[9], qd[9], qt[9];
     T bp[NOBJ][3], bq[NOBJ][4], bv[NOBJ][3], bw[NOBJ][3];
     T goal[NOBJ][3];
     T lam_t[NOBJ][8];
     T lam_p[4];
     T steps, episode;
-    int cls;   // row-set class of the last substep (class_key below); scheduling hint, not part of the state
+    int cls;   // row-set class of the last substep (class_layout below); scheduling hint, not part of the state
 };
+
+// XarmPDStackTower-v0: three cubes, one goal xy for the tower (draws 6-7), cube o's goal at height (2 o + 1) * 0.025
+struct Tower3 : Cubes<3> {
+    static constexpr double OBJ_LOW[2] = {xm::ST_OBJ_LOW[0], xm::ST_OBJ_LOW[1]}, OBJ_HIGH[2] = {xm::ST_OBJ_HIGH[0], xm::ST_OBJ_HIGH[1]};
+    static constexpr double DISTANCE_THRESHOLD = xm::ST_DISTANCE_THRESHOLD;
+    static constexpr int MAX_EPISODE_STEPS = xm::ST_MAX_EPISODE_STEPS;
+    static constexpr int NDRAW = 8;
+    template <typename T> static XARM_HD void sample_goal(const T (&u)[NDRAW], Lane<T, Tower3> &L) {
+        const T x = (T)xm::ST_GOAL_LOW[0] + u[6] * (T)(xm::ST_GOAL_HIGH[0] - xm::ST_GOAL_LOW[0]);
+        const T y = (T)xm::ST_GOAL_LOW[1] + u[7] * (T)(xm::ST_GOAL_HIGH[1] - xm::ST_GOAL_LOW[1]);
+#pragma unroll
+        for (int o = 0; o < NOBJ; o++) {   // :212-219
+            L.goal[o][0] = x; L.goal[o][1] = y;
+            L.goal[o][2] = (T)(xm::ST_HEIGHT_OFFSET * (2 * o + 1));
+        }
+    }
+};
+static_assert(xm::ST_NUM_OBJ == Tower3::NOBJ, "model JSON stack_tower.num_obj");
+static_assert(Tower3::K_BQ == 63 && Tower3::K_BV == 75 && Tower3::K_BW == 84 && Tower3::K_GOAL == 93 && Tower3::K_LT == 102 && Tower3::K_LP == 126 &&
+              Tower3::K_STEPS == 134 && Tower3::K_EPISODE == 135, "StackTower state layout");
+static_assert(Tower3::STATE_DIM == 136 && Tower3::OBS_DIM == 55 && Tower3::GOAL_DIM == 9 && Tower3::NCLS == 32 && Tower3::LDS_FLOATS == 603, "StackTower sizes");
+static_assert(Tower3::pair_a(0) == 0 && Tower3::pair_b(0) == 1 && Tower3::pair_a(1) == 0 && Tower3::pair_b(1) == 2 && Tower3::pair_a(2) == 1 && Tower3::pair_b(2) == 2, "pairs 01 02 12");
 
 // ---- class-homogeneous wavefronts.  A wavefront sweeps the UNION of the row sets its 32 environments need (each
 // wave-uniform skip is a ballot over the lanes), and the launch lasts as long as its slowest wavefront: with the envs in
-// arrival order nearly every wavefront holds some env with cube/cube contact in each of the three pairs and some env with
-// a finger contact, so all pay for everything (k_st_step 5.6 ms), although 88 % of the envs have no cube/cube contact
-// at all and ~0.05 % have two pairs (tools/st_pairs.py).  An env's result does not depend on its neighbours (bitwise,
+// arrival order nearly every wavefront holds some env with cube/cube contact in each of the pairs and some env with
+// a finger contact, so all pay for everything (StackTower: k_st_step 5.6 ms), although 88 % of the envs have no cube/cube
+// contact at all and ~0.05 % have two pairs (tools/st_pairs.py).  An env's result does not depend on its neighbours (bitwise,
 // tests/test_edge_cases.py), so the step kernel may visit the envs in any order: they are grouped by the row sets their
-// last substep used - class key: bits 0-2 cube pairs (0,1) (0,2) (1,2) in contact, bit 3 / 4 a finger pad of arm 0 / 1
-// active - and every non-empty class other than 0 starts on a wavefront boundary, topped up with class-0 envs (which
-// add nothing to a union).  A stale key (the contact set changed during the step) only makes that wavefront slower.
+// last substep used - class key: bit p cube pair p in contact (N = 3: bits 0-2 = 01 02 12, N = 4: bits 0-5 = 01 02 03 12 13
+// 23), then one bit each for a finger pad of arm 0 / 1 active - and every non-empty class other than 0 starts on a wavefront
+// boundary, topped up with class-0 envs (which add nothing to a union).  A stale key (the contact set changed during the
+// step) only makes that wavefront slower.
 // (Also keying on "manifold wider than two points" and skipping point slots 2-3 per wavefront was measured: no gain, the
 // contacts of these axis-aligned cubes are face against face.)
-constexpr int NCLS = 32;
-struct ClassLayout { int start[NCLS], hole_start[NCLS], hole_len[NCLS], tail_start; bool aligned; };
+template <int NCLS> struct ClassLayoutN { int start[NCLS], hole_start[NCLS], hole_len[NCLS], tail_start; bool aligned; };
 // slots [0, n) for the envs of each class, from the class histogram; `group` = envs per wavefront.  Class c > 0 occupies
 // [start[c], start[c] + hist[c]); the hole up to the next multiple of `group` and the tail after the last class are
 // filled by class 0 in order.  Without enough class-0 envs to fill the holes: plain contiguous order (aligned = false).
-XARM_HD void class_layout(const int (&hist)[NCLS], int group, ClassLayout &Y) {
+template <int NCLS> XARM_HD void class_layout(const int (&hist)[NCLS], int group, ClassLayoutN<NCLS> &Y) {
     int pos = 0, holes = 0;
     for (int c = 1; c < NCLS; c++) {
         Y.start[c] = pos;
@@ -90,7 +147,7 @@ XARM_HD void class_layout(const int (&hist)[NCLS], int group, ClassLayout &Y) {
     Y.tail_start = pos;
 }
 // slot of the k-th env (arrival order) of class c
-XARM_HD int class_slot(const ClassLayout &Y, int c, int k) {
+template <int NCLS> XARM_HD int class_slot(const ClassLayoutN<NCLS> &Y, int c, int k) {
     if (c != 0) return Y.start[c] + k;
     for (int j = 1; j < NCLS; j++) {
         if (k < Y.hole_len[j]) return Y.hole_start[j] + k;
@@ -99,8 +156,21 @@ XARM_HD int class_slot(const ClassLayout &Y, int c, int k) {
     return Y.tail_start + k;
 }
 
-template <typename T> XARM_HD T sel3(int i, T a, T b, T c) { return i == 0 ? a : (i == 1 ? b : c); }
-template <typename T> XARM_HD V3<T> sel3v(int i, V3<T> a, V3<T> b, V3<T> c) { return mk<T>(sel3(i, a.x, b.x, c.x), sel3(i, a.y, b.y, c.y), sel3(i, a.z, b.z, c.z)); }
+// the i-th of the values listed, as a chain of conditionals: expanded at compile time, never a run-time index into a register
+// array.  One overload per count in use, each ONE expression: a variadic form that recurses (i == K ? a : pick<K + 1>(i, b, ...))
+// means the same but is compiled to plain selects, where the compiler turns the nested conditionals of four values into a
+// branch per value - other code for every pad row of k_ra_step / k_ra_reset (about 5 % fewer instructions; a speed change, to
+// be measured on its own).
+template <typename T> XARM_HD T pick(int i, T a, T b, T c) { return i == 0 ? a : (i == 1 ? b : c); }
+template <typename T> XARM_HD T pick(int i, T a, T b, T c, T d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
+template <typename T, typename... R> XARM_HD V3<T> pickv(int i, V3<T> a, R... r) { return mk<T>(pick(i, a.x, r.x...), pick(i, a.y, r.y...), pick(i, a.z, r.z...)); }
+// a[i] of a length-N array of vectors (the cubes)
+template <typename T, int N, int... K> XARM_HD V3<T> pickv(int i, const V3<T> (&a)[N], std::integer_sequence<int, K...>) { return pickv(i, a[K]...); }
+template <typename T, int N> XARM_HD V3<T> pickv(int i, const V3<T> (&a)[N]) { return pickv(i, a, std::make_integer_sequence<int, N>()); }
+// bit p set where act[p]: (act[0] ? 1 : 0) | (act[1] ? 2 : 0) | ... as ONE expression (a run-time loop over the array that is then
+// unrolled leaves the compiler another order of operations, and the whole substep is scheduled differently)
+template <int N, int... P> XARM_HD int bits(const bool (&act)[N], std::integer_sequence<int, P...>) { return (... | (act[P] ? 1 << P : 0)); }
+template <int N> XARM_HD int bits(const bool (&act)[N]) { return bits(act, std::make_integer_sequence<int, N>()); }
 using xk::selv;
 template <typename T> XARM_HD V3<T> ldv(const T (&a)[3]) { return mk<T>(a[0], a[1], a[2]); }
 
@@ -108,7 +178,7 @@ template <typename T> XARM_HD V3<T> ldv(const T (&a)[3]) { return mk<T>(a[0], a[
 // A[k], B[k]: box axes in the world; both boxes are cubes of half edge h.  Returns the number of points (<= 4),
 // normal from B to A.  Everything with a compile-time index stays in registers (all fixed loops are unrolled, the
 // run-time axis choices are selects); the clipped polygon, whose vertex count is data dependent, lives in the
-// lane's LDS columns [LDS_CLIP, LDS_CLIP + 72) - private (scratch) arrays cost ~2 us per dependent access here.
+// lane's LDS columns [CLIP, CLIP + 72) - private (scratch) arrays cost ~2 us per dependent access here.
 template <typename T, typename Lds> XARM_HD int clip_axis(Lds lds, int in, int n, int out, int axis, T sgn, T h) {
     int m = 0;
     for (int i = 0; i < n; i++) {
@@ -200,9 +270,9 @@ XARM_HD int box_box(V3<T> pA, const V3<T> (&A)[3], const T (&hA)[3], V3<T> pB, c
 #pragma unroll
     for (int k = 0; k < 3; k++) { Rx[k] = selv(refA, A[k], B[k]); Ix[k] = selv(refA, B[k], A[k]); }
     const V3<T> pR = selv(refA, pA, pB), pI = selv(refA, pB, pA);
-    const T tAr = sel3(ri, tA[0], tA[1], tA[2]), tBr = sel3(ri, tB[0], tB[1], tB[2]);
+    const T tAr = pick(ri, tA[0], tA[1], tA[2]), tBr = pick(ri, tB[0], tB[1], tB[2]);
     const T sgR = refA ? (tAr < (T)0 ? (T)-1 : (T)1) : (tBr > (T)0 ? (T)-1 : (T)1);
-    const V3<T> Rri = sel3v(ri, Rx[0], Rx[1], Rx[2]);
+    const V3<T> Rri = pickv(ri, Rx[0], Rx[1], Rx[2]);
     const V3<T> dR = Rri * sgR;
     int jj = 0;
     T bestdot = (T)-1;
@@ -211,16 +281,16 @@ XARM_HD int box_box(V3<T> pA, const V3<T> (&A)[3], const T (&hA)[3], V3<T> pB, c
         const T d = xk::xabs(dot(Ix[j], dR));
         if (d > bestdot) { bestdot = d; jj = j; }
     }
-    const V3<T> Ijj = sel3v(jj, Ix[0], Ix[1], Ix[2]), Ij1 = sel3v(jj, Ix[1], Ix[2], Ix[0]), Ij2 = sel3v(jj, Ix[2], Ix[0], Ix[1]);
-    const V3<T> Rr1 = sel3v(ri, Rx[1], Rx[2], Rx[0]), Rr2 = sel3v(ri, Rx[2], Rx[0], Rx[1]);
+    const V3<T> Ijj = pickv(jj, Ix[0], Ix[1], Ix[2]), Ij1 = pickv(jj, Ix[1], Ix[2], Ix[0]), Ij2 = pickv(jj, Ix[2], Ix[0], Ix[1]);
+    const V3<T> Rr1 = pickv(ri, Rx[1], Rx[2], Rx[0]), Rr2 = pickv(ri, Rx[2], Rx[0], Rx[1]);
     const T sj = dot(Ijj, dR) > (T)0 ? (T)-1 : (T)1;
     // half extents of the reference / incident box along the selected axes
-    const T hRi = refA ? sel3(ri, hA[0], hA[1], hA[2]) : sel3(ri, hB[0], hB[1], hB[2]);
-    const T hR1 = refA ? sel3(ri, hA[1], hA[2], hA[0]) : sel3(ri, hB[1], hB[2], hB[0]);
-    const T hR2 = refA ? sel3(ri, hA[2], hA[0], hA[1]) : sel3(ri, hB[2], hB[0], hB[1]);
-    const T hIj = refA ? sel3(jj, hB[0], hB[1], hB[2]) : sel3(jj, hA[0], hA[1], hA[2]);
-    const T hI1 = refA ? sel3(jj, hB[1], hB[2], hB[0]) : sel3(jj, hA[1], hA[2], hA[0]);
-    const T hI2 = refA ? sel3(jj, hB[2], hB[0], hB[1]) : sel3(jj, hA[2], hA[0], hA[1]);
+    const T hRi = refA ? pick(ri, hA[0], hA[1], hA[2]) : pick(ri, hB[0], hB[1], hB[2]);
+    const T hR1 = refA ? pick(ri, hA[1], hA[2], hA[0]) : pick(ri, hB[1], hB[2], hB[0]);
+    const T hR2 = refA ? pick(ri, hA[2], hA[0], hA[1]) : pick(ri, hB[2], hB[0], hB[1]);
+    const T hIj = refA ? pick(jj, hB[0], hB[1], hB[2]) : pick(jj, hA[0], hA[1], hA[2]);
+    const T hI1 = refA ? pick(jj, hB[1], hB[2], hB[0]) : pick(jj, hA[1], hA[2], hA[0]);
+    const T hI2 = refA ? pick(jj, hB[2], hB[0], hB[1]) : pick(jj, hA[2], hA[0], hA[1]);
     constexpr int P0 = CLIP, P1 = CLIP + 24, KP = CLIP + 48;
     int n = 4;
 #pragma unroll
@@ -278,16 +348,17 @@ XARM_HD int box_box(V3<T> pA, const V3<T> (&A)[3], const T (&hA)[3], V3<T> pB, c
     nrm = refA ? dR * (T)-1 : dR;
     return ns;
 }
-template <typename T, typename Lds>
+template <typename T, typename Lds, typename Sc = Tower3>
 XARM_HD int cube_cube(V3<T> pA, const V3<T> (&A)[3], V3<T> pB, const V3<T> (&B)[3], T h, T margin, V3<T> (&pts)[4], V3<T> &nrm, T (&dist)[4], Lds lds) {
     const T hh[3] = {h, h, h};
-    return box_box<T, Lds, LDS_CLIP>(pA, A, hh, pB, B, hh, margin, pts, nrm, dist, lds);
+    return box_box<T, Lds, Sc::LDS_CLIP>(pA, A, hh, pB, B, hh, margin, pts, nrm, dist, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
-// one internal substep of the two-arm / three-cube scene (dt = timeStep / numSubSteps)
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg xchg) {
+// one internal substep of the two-arm / N-cube scene (dt = timeStep / numSubSteps)
+template <typename T, typename Lds, typename Xchg, typename Sc>
+XARM_HD void substep(Lane<T, Sc> &L, const T dt, Lds lds, const int arm, const Xchg xchg) {
+    constexpr int NOBJ = Sc::NOBJ, NPAIR = Sc::NPAIR, LDS_TP = Sc::LDS_TP, LDS_BB = Sc::LDS_BB;
     const T idt = (T)1 / dt;
     xk::ArmDyn<T> AD;
     xk::arm_dynamics<T, Lds, StackScene>(L.q, L.qd, dt, lds, arm, AD);
@@ -350,10 +421,10 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
 
     // ---------------- (BB) cube / cube manifolds -> LDS
     const T mu_bb = (T)(xm::MU_OBJECT * xm::MU_OBJECT);
-    bool bb_any = false, pair_act[NPAIR] = {false, false, false};
+    bool bb_any = false, pair_act[NPAIR] = {};
 #pragma unroll
     for (int pr = 0; pr < NPAIR; pr++) {
-        const int a = pr == 2 ? 1 : 0, b = pr == 0 ? 1 : 2;
+        const int a = Sc::pair_a(pr), b = Sc::pair_b(pr);
         const int base = LDS_BB + pr * BB_PAIR;
 #pragma unroll
         for (int k = 0; k < BB_PAIR; k++) lds[base + k] = (T)0;
@@ -364,7 +435,7 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
         if (XARM_ANY(near)) {
             V3<T> pts[4], nrm = mk<T>(0, 0, 1);
             T dist[4];
-            const int np = near ? cube_cube<T, Lds>(cb[a], Rb[a], cb[b], Rb[b], h, (T)xm::SOLVER_MARGIN, pts, nrm, dist, lds) : 0;
+            const int np = near ? cube_cube<T, Lds, Sc>(cb[a], Rb[a], cb[b], Rb[b], h, (T)xm::SOLVER_MARGIN, pts, nrm, dist, lds) : 0;
             if (np > 0) {
                 bb_any = true; pair_act[pr] = true;
                 const V3<T> t1 = xk::plane_space(nrm), t2 = cross(nrm, t1);
@@ -497,7 +568,7 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
             P.Kn = P.Kt1 = P.Kt2 = mk<T>(0, 0, 0);
             if (XARM_ANY(act)) {
                 const V3<T> af = hc1 * sg;
-                const V3<T> cc = sel3v(co, cb[0], cb[1], cb[2]);
+                const V3<T> cc = pickv(co, cb);
                 const V3<T> r = P.p - cc;
                 T K[3][3];
 #pragma unroll
@@ -600,8 +671,7 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
     for (int idx = 0; idx < NP; idx++) mymask |= pp[idx].invd[0] != (T)0 ? (1 << pc[idx]) : 0;
     const int othermask = (int)xchg.partner((T)mymask);
     const bool seq = XARM_ANY_X((mymask & othermask) != 0);
-    L.cls = (pair_act[0] ? 1 : 0) | (pair_act[1] ? 2 : 0) | (pair_act[2] ? 4 : 0) |
-            ((arm == 0 ? mymask : othermask) != 0 ? 8 : 0) | ((arm == 1 ? mymask : othermask) != 0 ? 16 : 0);
+    L.cls = bits(pair_act) | ((arm == 0 ? mymask : othermask) != 0 ? 1 << NPAIR : 0) | ((arm == 1 ? mymask : othermask) != 0 ? 2 << NPAIR : 0);
     XARM_LDS_FENCE();
 
     bool la_lane = false;
@@ -713,7 +783,7 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
         if (XARM_ANY(bb_any)) {
 #pragma unroll
             for (int pr = 0; pr < NPAIR; pr++) {
-                const int a = pr == 2 ? 1 : 0, b = pr == 0 ? 1 : 2;
+                const int a = Sc::pair_a(pr), b = Sc::pair_b(pr);
                 const int base = LDS_BB + pr * BB_PAIR;
                 if (!XARM_ANY(pair_act[pr])) continue;
                 const V3<T> n = mk<T>(lds[base + 0], lds[base + 1], lds[base + 2]), t1 = mk<T>(lds[base + 3], lds[base + 4], lds[base + 5]);
@@ -781,8 +851,8 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
                         PadPoint<T> &P = pp[2 * fk + j];
                         const int co = pc[2 * fk + j];
                         const T e0 = mine ? P.invd[0] : (T)0, e1 = mine ? P.invd[1] : (T)0, e2 = mine ? P.invd[2] : (T)0;
-                        const V3<T> r = P.p - sel3v(co, cb[0], cb[1], cb[2]);
-                        const V3<T> vc = sel3v(co, vb[0], vb[1], vb[2]), wc = sel3v(co, wb[0], wb[1], wb[2]);
+                        const V3<T> r = P.p - pickv(co, cb);
+                        const V3<T> vc = pickv(co, vb), wc = pickv(co, wb);
                         const V3<T> t2 = cross(P.n, P.t1);
                         V3<T> u = base + cross(yw, P.p) - vc - cross(wc, r);
                         if (j == 1) // effect on the finger of the impulse just applied at its first point (the cube side went into vb / wb)
@@ -926,14 +996,14 @@ XARM_HD void substep(Lane<T> &L, const T dt, Lds lds, const int arm, const Xchg 
 }
 
 // p.stepSimulation() with numSubSteps = 15
-template <typename T, typename Lds, typename Xchg> XARM_HD void tick(Lane<T> &L, Lds lds, int arm, Xchg x) {
+template <typename T, typename Lds, typename Xchg, typename Sc> XARM_HD void tick(Lane<T, Sc> &L, Lds lds, int arm, Xchg x) {
     const T dt = (T)(xm::ST_TIME_STEP / xm::ST_N_SUBSTEPS);
 #pragma unroll 1
     for (int k = 0; k < xm::ST_N_SUBSTEPS; k++) substep<T, Lds, Xchg>(L, dt, lds, arm, x);
 }
 
 // the 8 per-arm observation entries (:170-181): hand COM position and velocity, finger q, qd
-template <typename T> XARM_HD void arm_obs(const Lane<T> &L, int arm, T (&o)[8]) {
+template <typename T, typename Sc> XARM_HD void arm_obs(const Lane<T, Sc> &L, int arm, T (&o)[8]) {
     Frame<T> f = StackScene::base_frame<T>(arm);
     V3<T> w = mk<T>(0, 0, 0), v = mk<T>(0, 0, 0);
 #pragma unroll
@@ -949,22 +1019,23 @@ template <typename T> XARM_HD void arm_obs(const Lane<T> &L, int arm, T (&o)[8])
     o[6] = L.q[7]; o[7] = L.qd[7];
 }
 
-// draws 0-5: cube xy (cube i: 2i, 2i+1), 6-7: tower xy
-template <typename T> XARM_HD void draws(const EnvCfg &cfg, int64_t env, int64_t episode, T (&u)[8]) {
+// the NDRAW uniforms of a reset, ceil(NDRAW / 4) Philox blocks: 0 .. 2N-1 cube xy (cube i: 2i, 2i+1), then the scene's
+template <typename T, int NDRAW> XARM_HD void draws(const EnvCfg &cfg, int64_t env, int64_t episode, T (&u)[NDRAW]) {
+    static_assert(NDRAW % 4 == 0, "whole Philox blocks");
     const uint64_t gid = (uint64_t)(cfg.env_id_offset + env);
 #pragma unroll
-    for (int b = 0; b < 2; b++) {
+    for (int b = 0; b < NDRAW / 4; b++) {
         uint32_t o[4];
         xk::philox(cfg.seed, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)episode, (uint32_t)b, o);
 #pragma unroll
         for (int k = 0; k < 4; k++) u[b * 4 + k] = xk::u01<T>(o[k]);
     }
 }
-template <typename T> XARM_HD void sample_objects(const T (&u)[8], Lane<T> &L) {
+template <typename T, typename Sc> XARM_HD void sample_objects(const T (&u)[Sc::NDRAW], Lane<T, Sc> &L) {
 #pragma unroll
-    for (int o = 0; o < NOBJ; o++) {
-        L.bp[o][0] = (T)xm::ST_OBJ_LOW[0] + u[2 * o] * (T)(xm::ST_OBJ_HIGH[0] - xm::ST_OBJ_LOW[0]);
-        L.bp[o][1] = (T)xm::ST_OBJ_LOW[1] + u[2 * o + 1] * (T)(xm::ST_OBJ_HIGH[1] - xm::ST_OBJ_LOW[1]);
+    for (int o = 0; o < Sc::NOBJ; o++) {
+        L.bp[o][0] = (T)Sc::OBJ_LOW[0] + u[2 * o] * (T)(Sc::OBJ_HIGH[0] - Sc::OBJ_LOW[0]);
+        L.bp[o][1] = (T)Sc::OBJ_LOW[1] + u[2 * o + 1] * (T)(Sc::OBJ_HIGH[1] - Sc::OBJ_LOW[1]);
         L.bp[o][2] = (T)xm::ST_HEIGHT_OFFSET;
         L.bq[o][0] = L.bq[o][1] = L.bq[o][2] = (T)0; L.bq[o][3] = (T)1;
 #pragma unroll
@@ -975,54 +1046,46 @@ template <typename T> XARM_HD void sample_objects(const T (&u)[8], Lane<T> &L) {
 #pragma unroll
     for (int k = 0; k < 4; k++) L.lam_p[k] = (T)0;
 }
-template <typename T> XARM_HD void sample_goal(const T (&u)[8], Lane<T> &L) {
-    const T x = (T)xm::ST_GOAL_LOW[0] + u[6] * (T)(xm::ST_GOAL_HIGH[0] - xm::ST_GOAL_LOW[0]);
-    const T y = (T)xm::ST_GOAL_LOW[1] + u[7] * (T)(xm::ST_GOAL_HIGH[1] - xm::ST_GOAL_LOW[1]);
-#pragma unroll
-    for (int o = 0; o < NOBJ; o++) {   // :212-219
-        L.goal[o][0] = x; L.goal[o][1] = y;
-        L.goal[o][2] = (T)(xm::ST_HEIGHT_OFFSET * (2 * o + 1));
-    }
-}
-template <typename T> XARM_HD void teleport_arm(Lane<T> &L) {
+template <typename T, typename Sc> XARM_HD void teleport_arm(Lane<T, Sc> &L) {
 #pragma unroll
     for (int i = 0; i < 9; i++) { L.q[i] = (T)xm::ST_JOINT_INIT_POS[i]; L.qd[i] = (T)0; }
 }
-template <typename T> XARM_HD void lane_init(const EnvCfg &cfg, int64_t env, Lane<T> &L) {
+template <typename T, typename Sc> XARM_HD void lane_init(const EnvCfg &cfg, int64_t env, Lane<T, Sc> &L) {
     teleport_arm(L);
 #pragma unroll
     for (int i = 0; i < 9; i++) L.qt[i] = L.q[i];   // no motor command yet: hold the init pose
     L.steps = L.episode = (T)0;
     L.cls = 0;
-    T u[8];
+    T u[Sc::NDRAW];
     draws(cfg, env, 0, u);
     sample_objects(u, L);
-    sample_goal(u, L);
+    Sc::sample_goal(u, L);
 }
 // _reset_sim + _sample_goal (:201-219)
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void lane_reset(const EnvCfg &cfg, int64_t env, Lane<T> &L, int arm, Lds lds, Xchg x) {
+template <typename T, typename Lds, typename Xchg, typename Sc>
+XARM_HD void lane_reset(const EnvCfg &cfg, int64_t env, Lane<T, Sc> &L, int arm, Lds lds, Xchg x) {
     const int64_t episode = (int64_t)L.episode + 1;
-    T u[8];
+    T u[Sc::NDRAW];
     teleport_arm(L);
     draws(cfg, env, episode, u);
     sample_objects(u, L);
     tick<T, Lds, Xchg>(L, lds, arm, x);   // with the motor targets of the last step still set (:210)
-    sample_goal(u, L);
+    Sc::sample_goal(u, L);
     L.steps = (T)0;
     L.episode = (T)episode;
 }
-template <typename T> XARM_HD T goal_distance(const Lane<T> &L) {
+// |ag - g| over the whole 3N-vector (:124-127)
+template <typename T, typename Sc> XARM_HD T goal_distance(const Lane<T, Sc> &L) {
     T d2 = (T)0;
 #pragma unroll
-    for (int o = 0; o < NOBJ; o++)
+    for (int o = 0; o < Sc::NOBJ; o++)
 #pragma unroll
         for (int k = 0; k < 3; k++) { const T d = L.bp[o][k] - L.goal[o][k]; d2 += d * d; }
     return xk::xsqrt(d2);
 }
 // act = this arm's 4 action entries (:142-162)
-template <typename T, typename Lds, typename Xchg>
-XARM_HD void lane_step(const EnvCfg &cfg, Lane<T> &L, int arm, const T (&act)[4], T &reward, bool &done, bool &success, Lds lds, Xchg x) {
+template <typename T, typename Lds, typename Xchg, typename Sc>
+XARM_HD void lane_step(const EnvCfg &cfg, Lane<T, Sc> &L, int arm, const T (&act)[4], T &reward, bool &done, bool &success, Lds lds, Xchg x) {
     L.steps += (T)1;
     T a[4];
 #pragma unroll
@@ -1047,9 +1110,19 @@ XARM_HD void lane_step(const EnvCfg &cfg, Lane<T> &L, int arm, const T (&act)[4]
     L.qt[7] = L.qt[8] = g;
     tick<T, Lds, Xchg>(L, lds, arm, x);
     const T dist = goal_distance(L);
-    success = dist < (T)xm::ST_DISTANCE_THRESHOLD;                                   // :221-223
-    reward = cfg.reward_type == 0 ? (dist > (T)xm::ST_DISTANCE_THRESHOLD ? (T)-1 : (T)0) : -dist;   // :124-129
-    done = (int)L.steps == xm::ST_MAX_EPISODE_STEPS;                                // step() itself never ends (:111)
+    success = dist < (T)Sc::DISTANCE_THRESHOLD;                                     // :221-223
+    reward = cfg.reward_type == 0 ? (dist > (T)Sc::DISTANCE_THRESHOLD ? (T)-1 : (T)0) : -dist;   // :124-129
+    done = (int)L.steps == Sc::MAX_EPISODE_STEPS;                                   // step() itself never ends (:111)
 }
+
+// ---- namespace-level names of a scene's layout (what the C ABI unit, the render core and the host builds say: xs::K_BP,
+// xs::STATE_DIM, xs::ClassLayout; the same list in namespace xra for Rearrange4)
+#define XARM_CUBE_SCENE_NAMES(Sc)                                                                                                       \
+    constexpr int NOBJ = Sc::NOBJ, NPAIR = Sc::NPAIR, NCLS = Sc::NCLS, STATE_DIM = Sc::STATE_DIM, OBS_DIM = Sc::OBS_DIM,              \
+                  ACT_DIM = Sc::ACT_DIM, GOAL_DIM = Sc::GOAL_DIM, LDS_FLOATS = Sc::LDS_FLOATS, LDS_SHARED = Sc::LDS_SHARED;            \
+    enum { K_Q = Sc::K_Q, K_QD = Sc::K_QD, K_QT = Sc::K_QT, K_BP = Sc::K_BP, K_BQ = Sc::K_BQ, K_BV = Sc::K_BV, K_BW = Sc::K_BW,        \
+           K_GOAL = Sc::K_GOAL, K_LT = Sc::K_LT, K_LP = Sc::K_LP, K_STEPS = Sc::K_STEPS, K_EPISODE = Sc::K_EPISODE };                   \
+    using ClassLayout = xs::ClassLayoutN<Sc::NCLS>
+XARM_CUBE_SCENE_NAMES(Tower3);
 
 } // namespace xs

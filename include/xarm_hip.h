@@ -216,7 +216,7 @@ int xarm_debug_counts(xarm_handle *h, int32_t *finished, int32_t *handed_off, vo
  * envs' (csrc/xarm_stack_core.h "class-homogeneous wavefronts"); an env's result does not depend on the order.
  * XARM_ST_CLASS_ORDER=0 in the environment at xarm_create keeps the arrival order (then, and for the other env kinds,
  * this call fails with XARM_E_INVALID).  Rearrange: the same with bits 0-5 cube pairs 01 02 03 12 13 23, bit 6 / 7 a finger
- * pad of arm 0 / 1 (csrc/xarm_rearrange_core.h), switched off by XARM_RA_CLASS_ORDER=0.  Introspection only - nothing in
+ * pad of arm 0 / 1 (the same core with four cubes), switched off by XARM_RA_CLASS_ORDER=0.  Introspection only - nothing in
  * the reference corresponds to it. */
 int xarm_class_keys(xarm_handle *h, uint8_t *keys_dev, void *stream);
 

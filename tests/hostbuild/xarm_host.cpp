@@ -7,22 +7,15 @@
 #define XARM_HOST_BUILD 1
 #include "../../gym_xarm_amd/csrc/xarm_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_reach_core.h"
-#include <atomic>
-#include <sched.h>
 #include "../../gym_xarm_amd/csrc/xarm_handover_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_handover2_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_stack_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_coop_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_handover_coop_core.h"
 #include "../../gym_xarm_amd/csrc/xarm_reach_coop_core.h"
-#include <pthread.h>
-#include <string.h>
+#include "cube_pair_host.h"   // HostLds, SpinBarrier / PairShared / PairXchg, the cube scenes' runner
 
 namespace {
-template <typename T> struct HostLds {
-    T *base;
-    T &operator[](int i) const { return base[i]; }
-};
 template <typename T> void load(const double *row, xk::EnvState<T> &s) {
     for (int i = 0; i < 9; i++) { s.q[i] = (T)row[xk::S_Q + i]; s.qd[i] = (T)row[xk::S_QD + i]; }
     for (int i = 0; i < 3; i++) { s.bp[i] = (T)row[xk::S_BP + i]; s.bv[i] = (T)row[xk::S_BV + i]; s.bw[i] = (T)row[xk::S_BW + i]; s.goal[i] = (T)row[xk::S_GOAL + i]; }
@@ -251,36 +244,6 @@ template <typename T> void reach_init(const xr::EnvCfg &c, int64_t E, double *st
 
 // ---- Handover: the two lanes of an environment run as two host threads, the lane-pair exchange is a slot + barrier
 namespace {
-// two-party sense-reversing spin barrier: the lane pair exchanges thousands of values per tick, and a futex-based
-// pthread barrier made the emulation ~50x slower than the arithmetic it synchronises
-struct SpinBarrier {
-    std::atomic<int> count{0}, gen{0};
-    void wait() {
-        const int g = gen.load(std::memory_order_acquire);
-        if (count.fetch_add(1, std::memory_order_acq_rel) + 1 == 2) {
-            count.store(0, std::memory_order_relaxed);
-            gen.store(g + 1, std::memory_order_release);
-        } else {
-            int spins = 0;
-            while (gen.load(std::memory_order_acquire) == g)
-                if (++spins > 4096) { sched_yield(); spins = 0; }
-        }
-    }
-};
-struct PairShared { SpinBarrier bar; double slot[2]; };
-struct PairXchg {
-    PairShared *sh; int arm;
-    template <typename T> T get(int src, T v) const {
-        sh->slot[arm] = (double)v;
-        sh->bar.wait();
-        T r = (T)sh->slot[src];
-        sh->bar.wait();
-        return r;
-    }
-    template <typename T> T from0(T v) const { return get(0, v); }
-    template <typename T> T from1(T v) const { return get(1, v); }
-    template <typename T> T partner(T v) const { return get(1 - arm, v); }
-};
 template <typename T> void hload(const double *r, int arm, xh::Lane<T> &L) {
     for (int i = 0; i < 9; i++) { L.st.q[i] = (T)r[xh::H_Q + 9 * arm + i]; L.st.qd[i] = (T)r[xh::H_QD + 9 * arm + i]; }
     L.ft = (T)r[xh::H_FT + arm];
@@ -526,119 +489,33 @@ void xh_ik(int f32, const double *q, const double *target, double *out) { if (f3
 }
 
 
-// ---- StackTower: same two-thread lane-pair emulation as Handover
-namespace {
-template <typename T> void sload(const double *r, int arm, xs::Lane<T> &L) {
-    for (int i = 0; i < 9; i++) { L.q[i] = (T)r[xs::K_Q + 9 * arm + i]; L.qd[i] = (T)r[xs::K_QD + 9 * arm + i]; L.qt[i] = (T)r[xs::K_QT + 9 * arm + i]; }
-    for (int o = 0; o < 3; o++) {
-        for (int k = 0; k < 3; k++) { L.bp[o][k] = (T)r[xs::K_BP + 3 * o + k]; L.bv[o][k] = (T)r[xs::K_BV + 3 * o + k]; L.bw[o][k] = (T)r[xs::K_BW + 3 * o + k]; L.goal[o][k] = (T)r[xs::K_GOAL + 3 * o + k]; }
-        for (int k = 0; k < 4; k++) L.bq[o][k] = (T)r[xs::K_BQ + 4 * o + k];
-        for (int k = 0; k < 8; k++) L.lam_t[o][k] = (T)r[xs::K_LT + 8 * o + k];
-    }
-    for (int k = 0; k < 4; k++) L.lam_p[k] = (T)r[xs::K_LP + 4 * arm + k];
-    L.steps = (T)r[xs::K_STEPS]; L.episode = (T)r[xs::K_EPISODE];
-}
-template <typename T> void sstore(const xs::Lane<T> &L, int arm, double *r) {
-    for (int i = 0; i < 9; i++) { r[xs::K_Q + 9 * arm + i] = L.q[i]; r[xs::K_QD + 9 * arm + i] = L.qd[i]; r[xs::K_QT + 9 * arm + i] = L.qt[i]; }
-    for (int k = 0; k < 4; k++) r[xs::K_LP + 4 * arm + k] = L.lam_p[k];
-    if (arm == 0) {
-        for (int o = 0; o < 3; o++) {
-            for (int k = 0; k < 3; k++) { r[xs::K_BP + 3 * o + k] = L.bp[o][k]; r[xs::K_BV + 3 * o + k] = L.bv[o][k]; r[xs::K_BW + 3 * o + k] = L.bw[o][k]; r[xs::K_GOAL + 3 * o + k] = L.goal[o][k]; }
-            for (int k = 0; k < 4; k++) r[xs::K_BQ + 4 * o + k] = L.bq[o][k];
-            for (int k = 0; k < 8; k++) r[xs::K_LT + 8 * o + k] = L.lam_t[o][k];
-        }
-        r[xs::K_STEPS] = L.steps; r[xs::K_EPISODE] = L.episode;
-    }
-}
-template <typename T> struct StJob {
-    int mode; xk::EnvCfg cfg; int64_t E; double *state; const double *act; const uint8_t *mask;
-    double *obs, *ag, *dg, *rew; uint8_t *done, *succ; PairShared *sh; int arm;
-};
-template <typename T> void *st_thread(void *p) {
-    StJob<T> &J = *(StJob<T> *)p;
-    PairXchg x{J.sh, J.arm};
-    for (int64_t e = 0; e < J.E; e++) {
-        if (J.mode == 1 && J.mask && !J.mask[e]) continue;
-        xs::Lane<T> L; T lds[xs::LDS_FLOATS]; HostLds<T> hl{lds};
-        sload(J.state + e * xs::STATE_DIM, J.arm, L);
-        T r = 0; bool d = false, su = false;
-        if (J.mode == 0) {
-            T a[4]; for (int k = 0; k < 4; k++) a[k] = (T)J.act[e * 8 + 4 * J.arm + k];
-            xs::lane_step<T>(J.cfg, L, J.arm, a, r, d, su, hl, x);
-        } else xs::lane_reset<T>(J.cfg, e, L, J.arm, hl, x);
-        T o8[8];
-        xs::arm_obs(L, J.arm, o8);
-        J.sh->bar.wait();
-        sstore(L, J.arm, J.state + e * xs::STATE_DIM);
-        double *o = J.obs + e * xs::OBS_DIM;
-        for (int k = 0; k < 8; k++) o[39 + 8 * J.arm + k] = o8[k];
-        if (J.arm == 0) {
-            for (int ob = 0; ob < 3; ob++) {
-                for (int k = 0; k < 3; k++) {
-                    o[3 * ob + k] = L.bp[ob][k]; o[21 + 3 * ob + k] = L.bv[ob][k]; o[30 + 3 * ob + k] = L.bw[ob][k];
-                    J.ag[e * 9 + 3 * ob + k] = L.bp[ob][k]; J.dg[e * 9 + 3 * ob + k] = L.goal[ob][k];
-                }
-                for (int k = 0; k < 4; k++) o[9 + 4 * ob + k] = L.bq[ob][k];
-            }
-            if (J.mode == 0) { J.rew[e] = r; J.done[e] = d; J.succ[e] = su; }
-        }
-        J.sh->bar.wait();
-    }
-    return 0;
-}
-template <typename T> void st_run(int mode, const xk::EnvCfg &cfg, int64_t E, double *state, const double *act, const uint8_t *mask,
-                                  double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ) {
-    PairShared sh;
-    StJob<T> j[2];
-    pthread_t th[2];
-    for (int a = 0; a < 2; a++) { j[a] = StJob<T>{mode, cfg, E, state, act, mask, obs, ag, dg, rew, done, succ, &sh, a}; pthread_create(&th[a], 0, st_thread<T>, &j[a]); }
-    for (int a = 0; a < 2; a++) pthread_join(th[a], 0);
-}
-static xk::EnvCfg scfg(uint64_t seed, int64_t off, int rt) { xk::EnvCfg c; memset(&c, 0, sizeof c); c.seed = seed; c.env_id_offset = off; c.reward_type = rt; return c; }
-}
+// ---- StackTower: the cube scenes' lane-pair runner (cube_pair_host.h) on xs::Tower3
 extern "C" {
 void xh_st_init(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state) {
-    auto c = scfg(seed, off, rt);
-    for (int64_t e = 0; e < E; e++) for (int a = 1; a >= 0; a--) {
-        if (f32) { xs::Lane<float> L; xs::lane_init<float>(c, e, L); sstore(L, a, state + e * xs::STATE_DIM); }
-        else { xs::Lane<double> L; xs::lane_init<double>(c, e, L); sstore(L, a, state + e * xs::STATE_DIM); }
-    }
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::init<float, xs::Tower3>(c, E, state); else cubes::init<double, xs::Tower3>(c, E, state);
 }
 void xh_st_step(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state, const double *act, double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ) {
-    auto c = scfg(seed, off, rt);
-    if (f32) st_run<float>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ); else st_run<double>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ);
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::run<float, xs::Tower3>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, 0); else cubes::run<double, xs::Tower3>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, 0);
 }
 void xh_st_reset(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state, const uint8_t *mask, double *obs, double *ag, double *dg) {
-    auto c = scfg(seed, off, rt);
-    if (f32) st_run<float>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0); else st_run<double>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0);
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::run<float, xs::Tower3>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, 0); else cubes::run<double, xs::Tower3>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, 0);
 }
-// class-homogeneous visiting order of the StackTower step kernel (xs::class_layout / class_slot, as k_class_hist + k_class_place
-// run them, with the envs arriving in index order): order[slot] = env; returns 1 when the classes are wavefront-aligned
-int xh_class_order(const uint8_t *key, int64_t n, int group, int32_t *order) {
-    int hist[xs::NCLS] = {0}, cursor[xs::NCLS] = {0};
-    for (int64_t e = 0; e < n; e++) hist[key[e] & (xs::NCLS - 1)]++;
-    xs::ClassLayout Y;
-    xs::class_layout(hist, group, Y);
-    for (int64_t e = 0; e < n; e++) order[e] = -1;
-    for (int64_t e = 0; e < n; e++) {
-        const int c = key[e] & (xs::NCLS - 1);
-        const int slot = xs::class_slot(Y, c, cursor[c]++);
-        if (slot < 0 || slot >= n || order[slot] != -1) return -1;
-        order[slot] = (int32_t)e;
-    }
-    return Y.aligned ? 1 : 0;
-}
+// class-homogeneous visiting order of the StackTower step kernel, as k_class_hist + k_class_place run it
+int xh_class_order(const uint8_t *key, int64_t n, int group, int32_t *order) { return cubes::class_order<xs::Tower3>(key, n, group, order); }
 // cube/cube manifold alone (R row-major, column k = axis k, as the oracle's xo_box_box)
 int xh_cube_cube(int f32, const double *pA, const double *RA, const double *pB, const double *RB, double h, double margin, double *pts, double *nrm, double *dist) {
     int n;
     if (f32) {
-        xk::V3<float> A[3], B[3], P[4], N; float D[4]; float lds[xs::LDS_FLOATS]; HostLds<float> hl{lds};
+        xk::V3<float> A[3], B[3], P[4], N; float D[4]; float lds[xs::Tower3::LDS_FLOATS]; HostLds<float> hl{lds};
         for (int k = 0; k < 3; k++) { A[k] = xk::mk<float>((float)RA[k], (float)RA[3 + k], (float)RA[6 + k]); B[k] = xk::mk<float>((float)RB[k], (float)RB[3 + k], (float)RB[6 + k]); }
         n = xs::cube_cube<float, HostLds<float>>(xk::mk<float>((float)pA[0], (float)pA[1], (float)pA[2]), A, xk::mk<float>((float)pB[0], (float)pB[1], (float)pB[2]), B, (float)h, (float)margin, P, N, D, hl);
         for (int q = 0; q < n; q++) { pts[3 * q] = P[q].x; pts[3 * q + 1] = P[q].y; pts[3 * q + 2] = P[q].z; dist[q] = D[q]; }
         if (n) { nrm[0] = N.x; nrm[1] = N.y; nrm[2] = N.z; }
     } else {
-        xk::V3<double> A[3], B[3], P[4], N; double D[4]; double lds[xs::LDS_FLOATS]; HostLds<double> hl{lds};
+        xk::V3<double> A[3], B[3], P[4], N; double D[4]; double lds[xs::Tower3::LDS_FLOATS]; HostLds<double> hl{lds};
         for (int k = 0; k < 3; k++) { A[k] = xk::mk<double>(RA[k], RA[3 + k], RA[6 + k]); B[k] = xk::mk<double>(RB[k], RB[3 + k], RB[6 + k]); }
         n = xs::cube_cube<double, HostLds<double>>(xk::mk<double>(pA[0], pA[1], pA[2]), A, xk::mk<double>(pB[0], pB[1], pB[2]), B, h, margin, P, N, D, hl);
         for (int q = 0; q < n; q++) { pts[3 * q] = P[q].x; pts[3 * q + 1] = P[q].y; pts[3 * q + 2] = P[q].z; dist[q] = D[q]; }

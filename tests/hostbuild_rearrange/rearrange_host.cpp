@@ -1,137 +1,27 @@
-// Host (g++) instantiation of gym_xarm_amd/csrc/xarm_rearrange_core.h for the CPU-side tests ONLY (tests/rearrange_host.py).
-// It lives under tests/ and is never loaded by the product package.  The two lanes of an environment run as two host threads,
-// the lane-pair exchange is a slot + spin barrier (as tests/hostbuild/xarm_host.cpp does for StackTower); each lane keeps its own
-// copy of the object columns, which the device kernel shares between the two lanes of an env (they hold the same numbers).
+// Host (g++) instantiation of the cube core (gym_xarm_amd/csrc/xarm_stack_core.h) for the scene xra::Rearrange4
+// (xarm_rearrange_core.h), for the CPU-side tests ONLY (tests/rearrange_host.py).  It lives under tests/ and is never loaded by the
+// product package.  The lane-pair runner is tests/hostbuild/cube_pair_host.h, shared with StackTower's host build.
 #define XARM_HOST_BUILD 1
 #include "../../gym_xarm_amd/csrc/xarm_rearrange_core.h"
-#include <atomic>
-#include <pthread.h>
-#include <sched.h>
-#include <string.h>
+#include "../hostbuild/cube_pair_host.h"
 
-namespace {
-template <typename T> struct HostLds {
-    T *base;
-    T &operator[](int i) const { return base[i]; }
-};
-struct SpinBarrier {
-    std::atomic<int> count{0}, gen{0};
-    void wait() {
-        const int g = gen.load(std::memory_order_acquire);
-        if (count.fetch_add(1, std::memory_order_acq_rel) + 1 == 2) {
-            count.store(0, std::memory_order_relaxed);
-            gen.store(g + 1, std::memory_order_release);
-        } else {
-            int spins = 0;
-            while (gen.load(std::memory_order_acquire) == g)
-                if (++spins > 4096) { sched_yield(); spins = 0; }
-        }
-    }
-};
-struct PairShared { SpinBarrier bar; double slot[2]; };
-struct PairXchg {
-    PairShared *sh; int arm;
-    template <typename T> T get(int src, T v) const {
-        sh->slot[arm] = (double)v;
-        sh->bar.wait();
-        T r = (T)sh->slot[src];
-        sh->bar.wait();
-        return r;
-    }
-    template <typename T> T from0(T v) const { return get(0, v); }
-    template <typename T> T from1(T v) const { return get(1, v); }
-    template <typename T> T partner(T v) const { return get(1 - arm, v); }
-};
-
-template <typename T> void rload(const double *r, int arm, xra::Lane<T> &L) {
-    for (int i = 0; i < 9; i++) { L.q[i] = (T)r[xra::K_Q + 9 * arm + i]; L.qd[i] = (T)r[xra::K_QD + 9 * arm + i]; L.qt[i] = (T)r[xra::K_QT + 9 * arm + i]; }
-    for (int o = 0; o < xra::NOBJ; o++) {
-        for (int k = 0; k < 3; k++) { L.bp[o][k] = (T)r[xra::K_BP + 3 * o + k]; L.bv[o][k] = (T)r[xra::K_BV + 3 * o + k]; L.bw[o][k] = (T)r[xra::K_BW + 3 * o + k]; L.goal[o][k] = (T)r[xra::K_GOAL + 3 * o + k]; }
-        for (int k = 0; k < 4; k++) L.bq[o][k] = (T)r[xra::K_BQ + 4 * o + k];
-        for (int k = 0; k < 8; k++) L.lam_t[o][k] = (T)r[xra::K_LT + 8 * o + k];
-    }
-    for (int k = 0; k < 4; k++) L.lam_p[k] = (T)r[xra::K_LP + 4 * arm + k];
-    L.steps = (T)r[xra::K_STEPS]; L.episode = (T)r[xra::K_EPISODE];
-    L.cls = 0;
-}
-template <typename T> void rstore(const xra::Lane<T> &L, int arm, double *r) {
-    for (int i = 0; i < 9; i++) { r[xra::K_Q + 9 * arm + i] = L.q[i]; r[xra::K_QD + 9 * arm + i] = L.qd[i]; r[xra::K_QT + 9 * arm + i] = L.qt[i]; }
-    for (int k = 0; k < 4; k++) r[xra::K_LP + 4 * arm + k] = L.lam_p[k];
-    if (arm == 0) {
-        for (int o = 0; o < xra::NOBJ; o++) {
-            for (int k = 0; k < 3; k++) { r[xra::K_BP + 3 * o + k] = L.bp[o][k]; r[xra::K_BV + 3 * o + k] = L.bv[o][k]; r[xra::K_BW + 3 * o + k] = L.bw[o][k]; r[xra::K_GOAL + 3 * o + k] = L.goal[o][k]; }
-            for (int k = 0; k < 4; k++) r[xra::K_BQ + 4 * o + k] = L.bq[o][k];
-            for (int k = 0; k < 8; k++) r[xra::K_LT + 8 * o + k] = L.lam_t[o][k];
-        }
-        r[xra::K_STEPS] = L.steps; r[xra::K_EPISODE] = L.episode;
-    }
-}
-template <typename T> struct RaJob {
-    int mode; xk::EnvCfg cfg; int64_t E; double *state; const double *act; const uint8_t *mask;
-    double *obs, *ag, *dg, *rew; uint8_t *done, *succ, *key; PairShared *sh; int arm;
-};
-template <typename T> void *ra_thread(void *p) {
-    RaJob<T> &J = *(RaJob<T> *)p;
-    PairXchg x{J.sh, J.arm};
-    for (int64_t e = 0; e < J.E; e++) {
-        if (J.mode == 1 && J.mask && !J.mask[e]) continue;
-        xra::Lane<T> L; T lds[xra::LDS_FLOATS]; HostLds<T> hl{lds};
-        rload(J.state + e * xra::STATE_DIM, J.arm, L);
-        T r = 0; bool d = false, su = false;
-        if (J.mode == 0) {
-            T a[4]; for (int k = 0; k < 4; k++) a[k] = (T)J.act[e * 8 + 4 * J.arm + k];
-            xra::lane_step<T>(J.cfg, L, J.arm, a, r, d, su, hl, x);
-        } else xra::lane_reset<T>(J.cfg, e, L, J.arm, hl, x);
-        T o8[8];
-        xra::arm_obs(L, J.arm, o8);
-        J.sh->bar.wait();
-        rstore(L, J.arm, J.state + e * xra::STATE_DIM);
-        double *o = J.obs + e * xra::OBS_DIM;
-        for (int k = 0; k < 8; k++) o[52 + 8 * J.arm + k] = o8[k];
-        if (J.arm == 0) {
-            for (int ob = 0; ob < xra::NOBJ; ob++) {
-                for (int k = 0; k < 3; k++) {
-                    o[3 * ob + k] = L.bp[ob][k]; o[28 + 3 * ob + k] = L.bv[ob][k]; o[40 + 3 * ob + k] = L.bw[ob][k];
-                    J.ag[e * 12 + 3 * ob + k] = L.bp[ob][k]; J.dg[e * 12 + 3 * ob + k] = L.goal[ob][k];
-                }
-                for (int k = 0; k < 4; k++) o[12 + 4 * ob + k] = L.bq[ob][k];
-            }
-            if (J.mode == 0) { J.rew[e] = r; J.done[e] = d; J.succ[e] = su; }
-            if (J.key) J.key[e] = (uint8_t)L.cls;
-        }
-        J.sh->bar.wait();
-    }
-    return 0;
-}
-template <typename T> void ra_run(int mode, const xk::EnvCfg &cfg, int64_t E, double *state, const double *act, const uint8_t *mask,
-                                  double *obs, double *ag, double *dg, double *rew, uint8_t *done, uint8_t *succ, uint8_t *key) {
-    PairShared sh;
-    RaJob<T> j[2];
-    pthread_t th[2];
-    for (int a = 0; a < 2; a++) { j[a] = RaJob<T>{mode, cfg, E, state, act, mask, obs, ag, dg, rew, done, succ, key, &sh, a}; pthread_create(&th[a], 0, ra_thread<T>, &j[a]); }
-    for (int a = 0; a < 2; a++) pthread_join(th[a], 0);
-}
-xk::EnvCfg rcfg(uint64_t seed, int64_t off, int rt) { xk::EnvCfg c; memset(&c, 0, sizeof c); c.seed = seed; c.env_id_offset = off; c.reward_type = rt; return c; }
-}
+using Sc = xra::Rearrange4;
 
 extern "C" {
-int ra_dims(int32_t *d) { d[0] = xra::STATE_DIM; d[1] = xra::OBS_DIM; d[2] = xra::GOAL_DIM; d[3] = xra::LDS_FLOATS; d[4] = xra::NCLS; return 0; }
+int ra_dims(int32_t *d) { d[0] = Sc::STATE_DIM; d[1] = Sc::OBS_DIM; d[2] = Sc::GOAL_DIM; d[3] = Sc::LDS_FLOATS; d[4] = Sc::NCLS; return 0; }
 void ra_init(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state) {
-    auto c = rcfg(seed, off, rt);
-    for (int64_t e = 0; e < E; e++) for (int a = 1; a >= 0; a--) {
-        if (f32) { xra::Lane<float> L; xra::lane_init<float>(c, e, L); rstore(L, a, state + e * xra::STATE_DIM); }
-        else { xra::Lane<double> L; xra::lane_init<double>(c, e, L); rstore(L, a, state + e * xra::STATE_DIM); }
-    }
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::init<float, Sc>(c, E, state); else cubes::init<double, Sc>(c, E, state);
 }
 // key (optional): the row-set class of each env's last substep
 void ra_step(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state, const double *act, double *obs, double *ag, double *dg,
              double *rew, uint8_t *done, uint8_t *succ, uint8_t *key) {
-    auto c = rcfg(seed, off, rt);
-    if (f32) ra_run<float>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, key); else ra_run<double>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, key);
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::run<float, Sc>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, key); else cubes::run<double, Sc>(0, c, E, state, act, 0, obs, ag, dg, rew, done, succ, key);
 }
 void ra_reset(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *state, const uint8_t *mask, double *obs, double *ag, double *dg, uint8_t *key) {
-    auto c = rcfg(seed, off, rt);
-    if (f32) ra_run<float>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key); else ra_run<double>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key);
+    auto c = cubes::cfg(seed, off, rt);
+    if (f32) cubes::run<float, Sc>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key); else cubes::run<double, Sc>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key);
 }
 // the kernel's reward arithmetic (k_ra_compute_reward) over n rows of 12, in float32
 void ra_compute_reward(int rt, const float *ag, const float *g, int64_t n, float *out) {
@@ -142,21 +32,5 @@ void ra_compute_reward(int rt, const float *ag, const float *g, int64_t n, float
         out[i] = rt == 0 ? (d > (float)xm::RA_DISTANCE_THRESHOLD ? -1.f : 0.f) : -d;
     }
 }
-// class-homogeneous visiting order (xra::class_layout / class_slot as k_ra_class_hist + k_ra_class_place run them, envs in
-// index order): order[slot] = env; 1 when the classes are wavefront-aligned, 0 when not, -1 on an invalid permutation
-int ra_class_order(const uint8_t *key, int64_t n, int group, int32_t *order) {
-    static int hist[xra::NCLS], cursor[xra::NCLS];
-    static xra::ClassLayout Y;
-    memset(hist, 0, sizeof hist); memset(cursor, 0, sizeof cursor);
-    for (int64_t e = 0; e < n; e++) hist[key[e]]++;
-    xra::class_layout(hist, group, Y);
-    for (int64_t e = 0; e < n; e++) order[e] = -1;
-    for (int64_t e = 0; e < n; e++) {
-        const int c = key[e];
-        const int slot = xra::class_slot(Y, c, cursor[c]++);
-        if (slot < 0 || slot >= n || order[slot] != -1) return -1;
-        order[slot] = (int32_t)e;
-    }
-    return Y.aligned ? 1 : 0;
-}
+int ra_class_order(const uint8_t *key, int64_t n, int group, int32_t *order) { return cubes::class_order<Sc>(key, n, group, order); }
 }

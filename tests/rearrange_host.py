@@ -1,5 +1,6 @@
-"""ctypes view of tests/hostbuild_rearrange (g++ build of csrc/xarm_rearrange_core.h, float64 and float32) - CPU-side tests
-only.  Rows are float64 state rows [E, 160] in the layout of the header comment of xarm_rearrange_core.h."""
+"""ctypes view of tests/hostbuild_rearrange (g++ build of the cube core csrc/xarm_stack_core.h for the scene of
+csrc/xarm_rearrange_core.h, float64 and float32) - CPU-side tests only.  Rows are float64 state rows [E, 160] in the layout of
+the header comment of xarm_stack_core.h with N = 4."""
 import ctypes as C
 import os
 import subprocess
@@ -9,9 +10,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "hostbuild_rearrange")
 STATE_DIM, OBS_DIM, GOAL_DIM = 160, 68, 12
-# state fields (xra::K_*)
+# state fields (xra::Rearrange4::K_*)
 Q, QD, QT, BP, BQ, BV, BW, GOAL, LT, LP, STEPS, EPISODE = 0, 18, 36, 54, 66, 82, 94, 106, 118, 150, 158, 159
-# StackTower's (xs::K_*)
+# StackTower's (xs::Tower3::K_*)
 S_BP, S_BQ, S_BV, S_BW, S_GOAL, S_LT, S_LP, S_STEPS, S_EPISODE = 54, 63, 75, 84, 93, 102, 126, 134, 135
 _lib = None
 
@@ -22,7 +23,8 @@ def lib():
         return _lib
     so = os.path.join(DIR, "librearrange_host.so")
     csrc = os.path.join(ROOT, "gym_xarm_amd", "csrc")
-    srcs = [os.path.join(DIR, "rearrange_host.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    srcs = [os.path.join(DIR, "rearrange_host.cpp"), os.path.join(ROOT, "tests", "hostbuild", "cube_pair_host.h")] + [
+        os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
         tmp = so + ".%d.tmp" % os.getpid()
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-pthread", "-o", tmp, srcs[0]])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """XarmRearrange-v0 throughput: N envs (default 8 192, StackTower's per-GPU size), uniform random actions, auto-reset on.
-Prints env steps/s and ms per step() call, and the row-set class histogram (csrc/xarm_rearrange_core.h: bits 0-5 cube pairs
+Prints env steps/s and ms per step() call, and the row-set class histogram (csrc/xarm_stack_core.h with N = 4: bits 0-5 cube pairs
 01 02 03 12 13 23, bit 6 / 7 a pad of arm 0 / 1) after reset() and after the timed steps.  --class-order 0 builds the handle
 with XARM_RA_CLASS_ORDER=0 (the plain visiting order).  --json FILE also writes the numbers.  bench.py is not involved."""
 import argparse
