@@ -18,11 +18,12 @@ GOAL_SHAPES = {"air": 0, "ground": 1}
 RESET_COOP_LIMIT_DEFAULT = STEP_COOP_LIMIT_DEFAULT = 8192   # include/xarm_hip.h XARM_*_COOP_LIMIT_DEFAULT
 
 EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step", "xarm_compute_reward",
-           "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_class_keys", "xarm_last_error",
+           "xarm_get_state", "xarm_set_state", "xarm_episode_steps", "xarm_debug_substeps", "xarm_timing_enable", "xarm_timing_read", "xarm_timing_read_reset", "xarm_kernel_limits", "xarm_pipeline_info", "xarm_stage_info", "xarm_debug_counts", "xarm_debug_stage_counts", "xarm_class_keys", "xarm_last_error",
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
            "xarm_policy_act"]
+HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
 VIEW_FLOATS = 16            # XARM_VIEW_FLOATS: eye 0-2, target 3-5, up 6-8, fov_deg 9, near_z 10, far_z 11, mount 12
@@ -130,6 +131,7 @@ def load(path=None):
     L.xarm_pipeline_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.xarm_stage_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.xarm_debug_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+    L.xarm_debug_stage_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     L.xarm_class_keys.argtypes = [vp, vp, vp]
     L.xarm_default_camera.argtypes = [vp, C.POINTER(XarmCamera)]
     L.xarm_render.argtypes = [vp, C.POINTER(XarmCamera), vp, C.c_int32, vp, vp, vp, vp]

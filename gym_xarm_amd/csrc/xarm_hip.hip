@@ -53,10 +53,12 @@ struct xarm_handle {
     int *eject_list;     // [stages][E] envs handed off by the fast kernel, one list per stage
     // the two reset launches of a pipelined step (xarm_step): episodes that ended in the fast kernel are reset on `side`
     // while the hand-off still runs on the caller's stream, the few that end in the hand-off after it
-    int *done_list_b;    // [E] episodes that ended in the hand-off kernels
+    int *done_list_b;    // [E] episodes that ended in the hand-off kernels (reset_per_stage: [stages][E], one list per hand-off stage)
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
     int reset_overlap;   // PickAndPlace pipeline with auto-reset only (xarm_create)
+    int reset_per_stage; // reset_overlap and ho_stages > 1: every hand-off stage resets its own finished envs behind its hand-off
+                         // (XARM_RESET_PER_STAGE=0: one list B for all stages, reset after the last hand-off)
     // staged step (pipelined_step): the fast kernel runs the step's 15 ticks in ho_stages launches; the envs a stage hands off
     // re-run only the ticks from that stage's first one on the cooperative rows, on a side stream beside the next stage
     static constexpr int MAX_ST = XARM_HO_MAX_STAGES;
@@ -88,7 +90,9 @@ enum { CNT_DONE = 0,      // episodes that ended in this call (list A)
        CNT_DONE_B = 2,    // episodes that ended in the hand-off kernels (list B)
        CNT_REGION = 3 };
 static constexpr int cnt_stage(int c) { return c == 0 ? (int)CNT_EJECT : CNT_REGION + c; }   // hand-off count of stage c
-constexpr int CNT_STAGE_INTS = cnt_stage(xarm_handle::MAX_ST) + 1;   // what a staged step clears and xarm_debug_counts reads
+// episodes that ended in the hand-off of stage c (reset_per_stage; otherwise every stage counts in CNT_DONE_B)
+static constexpr int cnt_done_b(int c) { return c == 0 ? (int)CNT_DONE_B : cnt_stage(xarm_handle::MAX_ST) + c; }
+constexpr int CNT_STAGE_INTS = cnt_done_b(xarm_handle::MAX_ST) + 1;   // what a staged step clears and xarm_debug_counts reads
 constexpr int CNT_INTS = CNT_REGION + 2 * xra::NCLS;                 // the allocation
 static_assert(xra::NCLS >= xs::NCLS && CNT_STAGE_INTS <= CNT_INTS, "one counter block serves both class orders and the stage counters");
 
@@ -161,11 +165,14 @@ template <auto K> static void init_with(xarm_handle *h) { K<<<dim3(env_grid(h)),
 using ResetKernel = void (*)(KParams, const int *, const int *, float *, float *, float *);
 // the cooperative kernel takes counts up to kp.coop_limit, the one-env-per-lane (Handover: lane-pair) kernel the rest; both
 // are launched, the one out of its range exits at once (the count lives on the device)
+// lane_first: the lane kernel in front (the two are exclusive by count, so the order does not touch results) - for a short list at the
+// end of a latency chain, where the cooperative kernel does the work and the empty lane launch would otherwise end the chain
 static void split_reset(xarm_handle *h, ResetKernel coop, unsigned (*cgrid)(int64_t), ResetKernel lane, const int *list, const int *count,
-                        float *obs, float *ag, float *dg, hipStream_t st) {
+                        float *obs, float *ag, float *dg, hipStream_t st, bool lane_first = false) {
     const int64_t cap = capped(h, h->kp.coop_limit);
+    if (lane_first && h->kp.num_envs > cap) lane<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
     if (cap > 0) coop<<<dim3(cgrid(cap)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
-    if (h->kp.num_envs > cap) lane<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
+    if (!lane_first && h->kp.num_envs > cap) lane<<<dim3(env_grid(h)), dim3(WG), 0, st>>>(h->kp, list, count, obs, ag, dg);
 }
 static void pnp_reset(xarm_handle *h, const int *list, const int *count, float *obs, float *ag, float *dg, hipStream_t st) {
     split_reset(h, k_reset_coop, coop_grid, k_reset, list, count, obs, ag, dg, st);
@@ -199,11 +206,16 @@ template <auto K> static void sparse_reward(xarm_handle *h, const float *ag, con
 // beside the next fast stage (16 384 Handover envs are 512 of the 1 024 SIMDs); only the last stage's hand-off, a third of a step
 // long, is on the critical path: Handover's fast 0.73 + hand-off 0.69 ms became 0.77 + 0.27.
 //   fast        launches fast stage c on the caller's stream
-//   handoff     launches the hand-off of stage c on hs
+//   handoff     launches the hand-off of stage c on hs (and what belongs behind it on hs: PickAndPlace's per-stage reset)
 //   after_fast  hook, after the last fast stage and before its hand-off (null: none)
+// The side streams are joined here, or - reset_per_stage - by xarm_step behind the last stage's reset (join_stages).
+static int join_stages(xarm_handle *h, hipStream_t st) {
+    for (int c = 0; c + 1 < h->ho_stages; c++) HIPCHK(h, hipStreamWaitEvent(st, h->st_join[c], 0));
+    return XARM_OK;
+}
 static int pipelined_step(xarm_handle *h, const StepIO &io, hipStream_t st,
                           void (*fast)(xarm_handle *, const StepIO &, int *elist, int *ecnt, HoStage, hipStream_t),
-                          void (*handoff)(xarm_handle *, const StepIO &, int *elist, int *ecnt, HoStage rest, hipStream_t hs),
+                          void (*handoff)(xarm_handle *, const StepIO &, int c, int *elist, int *ecnt, HoStage rest, hipStream_t hs),
                           int (*after_fast)(xarm_handle *, const StepIO &, hipStream_t)) {
     static_assert(xm::HO_N_TICKS == xm::PNP_N_SUBSTEPS, "one stage table for both");
     const int nst = h->ho_stages;
@@ -220,13 +232,12 @@ static int pipelined_step(xarm_handle *h, const StepIO &io, hipStream_t st,
             const int rc = after_fast(h, io, st);
             if (rc != XARM_OK) return rc;
         }
-        // one done list for every kernel of the call (atomic appends), the reset after the last hand-off
+        // one done list for every kernel of the call (atomic appends), the reset after the last hand-off (PickAndPlace: pnp_handoff)
         const HoStage rest{sg.tick0, xm::HO_N_TICKS, h->ho_qt, h->ho_flag};
-        handoff(h, io, elist, ecnt, rest, hs);
+        handoff(h, io, c, elist, ecnt, rest, hs);
         if (c + 1 < nst) HIPCHK(h, hipEventRecord(h->st_join[c], hs));
     }
-    for (int c = 0; c + 1 < nst; c++) HIPCHK(h, hipStreamWaitEvent(st, h->st_join[c], 0));
-    return XARM_OK;
+    return h->reset_per_stage ? XARM_OK : join_stages(h, st);
 }
 
 // PickAndPlace.  The unstaged pipeline (XARM_PNP_STAGES=1) is the one stage {0, 15} of the same kernels, as for Handover.
@@ -236,20 +247,33 @@ static void pnp_fast(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, Ho
 // With the reset overlap the episodes that end in the hand-off go to a list of their own (done_list_b): the reset of the ~98 %
 // that ended on the fast path need not wait for it.  Without the side stream (XARM_RESET_OVERLAP=0): one list, one reset after
 // the hand-off.
-static void pnp_handoff(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
-    int *list_b = h->reset_overlap ? h->done_list_b : h->done_list, *cnt_b = slot(h, h->reset_overlap ? CNT_DONE_B : CNT_DONE);
+// reset_per_stage: the hand-off of stage c appends to a list of its own (b_stage(c)), and every stage but the last resets that list on its
+// side stream directly behind its hand-off - stream order is the dependency (terminal_obs / done / success / reward of an env are
+// written by its step kernel before its reset), and st_join[c], recorded by pipelined_step behind this, covers the reset.  A finished
+// stage-0 hand-off env starts its reset when ITS hand-off ends, not when the last stage's does, and shares reset wavefronts with envs of
+// its own stage only (DESIGN.md 4b "Resets per hand-off stage").  The last stage's list: xarm_step, on the caller's stream.
+static int b_stage(const xarm_handle *h, int c) { return h->reset_per_stage ? c : 0; }
+static int *b_list(const xarm_handle *h, int c) { return h->done_list_b + (int64_t)b_stage(h, c) * h->kp.stride; }
+static void pnp_reset_b(xarm_handle *h, const StepIO &io, int c, hipStream_t st) {
+    split_reset(h, k_reset_coop, coop_grid, k_reset, b_list(h, c), slot(h, cnt_done_b(b_stage(h, c))), io.obs, io.ag, io.dg, st, h->reset_per_stage != 0);
+}
+static void pnp_handoff(xarm_handle *h, const StepIO &io, int c, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
+    int *list_b = h->reset_overlap ? b_list(h, c) : h->done_list, *cnt_b = slot(h, h->reset_overlap ? cnt_done_b(b_stage(h, c)) : (int)CNT_DONE);
     const int64_t cap = capped(h, h->kp.eject_coop_cap);
     const unsigned cgrid = coop_grid(cap) < 1024u ? coop_grid(cap) : 1024u;
     launch_step(k_step_coop_list_stage, cgrid, hs, h, io, list_b, cnt_b, elist, ecnt, rest);
-    if (h->kp.num_envs <= cap) return;
-    // the long-list fall-back (lists above eject_coop_cap): k_step for an unstaged step, k_step_from_stage for a staged one
-    if (h->ho_stages > 1) launch_step(k_step_from_stage, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt, rest);
-    else launch_step(k_step, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt);
+    if (h->kp.num_envs > cap) {
+        // the long-list fall-back (lists above eject_coop_cap): k_step for an unstaged step, k_step_from_stage for a staged one
+        if (h->ho_stages > 1) launch_step(k_step_from_stage, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt, rest);
+        else launch_step(k_step, env_grid(h), hs, h, io, list_b, cnt_b, elist, ecnt);
+    }
+    if (h->reset_per_stage && c + 1 < h->ho_stages) pnp_reset_b(h, io, c, hs);
 }
 // a reset is six sequential ticks of latency on a few hundred wavefronts (2.9 ms), the hand-off 0.55 ms on a few hundred
 // others: started after the last fast stage on the side stream, the first reset overlaps the hand-off.  The call still waits
 // for the second one - a few dozen envs, but the ones with a finger contact, whose reset carries the pad rows through the
-// homing ticks (worth 0.16 ms per call at 16 384 envs, nothing at 65 536)
+// homing ticks (worth 0.16 ms per call at 16 384 envs, nothing at 65 536) - which is why the staged step resets them
+// per hand-off stage (pnp_handoff): the stage-0 envs, the ones that keep the pad rows, start 0.2 ms earlier
 static int pnp_overlapped_reset(xarm_handle *h, const StepIO &io, hipStream_t st) {
     if (!h->reset_overlap) return XARM_OK;
     HIPCHK(h, hipEventRecord(h->ev_fork, st));
@@ -276,7 +300,7 @@ static int reach_step(xarm_handle *h, const StepIO &io, hipStream_t st) {
 static void ho_fast(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage sg, hipStream_t st) {
     launch_step(HO_KERNEL(h, k_ho_step_fast), env_grid(h), st, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, sg);
 }
-static void ho_handoff(xarm_handle *h, const StepIO &io, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
+static void ho_handoff(xarm_handle *h, const StepIO &io, int, int *elist, int *ecnt, HoStage rest, hipStream_t hs) {
     const int64_t cap = capped(h, h->kp.eject_coop_cap);
     launch_step(HO_COOP_KERNEL(h, k_ho_step_coop_list), ho_coop_grid(cap), hs, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, rest);
     if (h->kp.num_envs > cap) launch_step(HO_KERNEL(h, k_ho_step), env_grid(h), hs, h, io, h->done_list, slot(h, CNT_DONE), elist, ecnt, rest);
@@ -344,7 +368,8 @@ static const KindOps KIND_REARRANGE = {
 static int step_counter_ints(const xarm_handle *h) {
     if (h->class_key) return CNT_REGION + 2 * h->ops->ncls;
     if (!h->fast_pipeline) return CNT_DONE + 1;
-    return h->ho_stages > 1 ? CNT_STAGE_INTS : (int)CNT_REGION;
+    if (h->ho_stages <= 1) return CNT_REGION;
+    return h->reset_per_stage ? CNT_STAGE_INTS : cnt_stage(xarm_handle::MAX_ST) + 1;   // with or without the per-stage list-B counts
 }
 
 // integer value of an environment variable that is set and not empty
@@ -505,7 +530,6 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
     hipError_t e4 = hipMalloc(&h->mask_count, sizeof(int));
     if (e4 == hipSuccess && h->fast_pipeline) {
         e4 = hipMalloc(&h->eject_list, sizeof(int) * stride * h->ho_stages);   // one list per stage
-        if (e4 == hipSuccess) e4 = hipMalloc(&h->done_list_b, sizeof(int) * stride);
         // the reset overlap is PickAndPlace's (Handover: see ho_fast)
         if (e4 == hipSuccess && cfg->auto_reset && !handover1 && !(env_int("XARM_RESET_OVERLAP", &v) && v == 0)) {
             e4 = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
@@ -513,6 +537,10 @@ int xarm_create(const xarm_config *cfg, xarm_handle **out) {
             if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming);
             h->reset_overlap = e4 == hipSuccess;
         }
+        // one list B per hand-off stage, reset behind that stage's hand-off (pnp_handoff); XARM_RESET_PER_STAGE=0: one list B, one reset
+        // after the last hand-off
+        h->reset_per_stage = h->reset_overlap && h->ho_stages > 1 && (env_int("XARM_RESET_PER_STAGE", &v) ? v != 0 : XARM_RESET_PER_STAGE_DEFAULT);
+        if (e4 == hipSuccess) e4 = hipMalloc(&h->done_list_b, sizeof(int) * stride * (h->reset_per_stage ? h->ho_stages : 1));
     }
     if (e4 == hipSuccess && h->fast_pipeline) {
         // the joint targets travel between stages only; the flags belong to every pipelined handle: k_step_fast_stage marks an env it
@@ -625,7 +653,10 @@ int xarm_step(xarm_handle *h, const float *actions_dev, float *obs_dev, float *a
     if (rc != XARM_OK) return rc;
     if (timed) HIPCHK(h, hipEventRecord(h->ev1[h->ev_n], st));
     if (h->reset_overlap && !small_batch(h)) {     // the PickAndPlace pipeline reset list A on `side` (pnp_overlapped_reset)
-        pnp_reset(h, h->done_list_b, slot(h, CNT_DONE_B), obs_dev, ag_dev, dg_dev, st);
+        // list B (reset_per_stage: the last stage's; the earlier stages reset theirs on their side streams, joined here, BEHIND the
+        // launch - the last reset waits for its own hand-off only, and the call still ends with every side stream joined)
+        pnp_reset_b(h, io, h->ho_stages - 1, st);
+        if (h->reset_per_stage) { const int jr = join_stages(h, st); if (jr != XARM_OK) return jr; }
         HIPCHK(h, hipStreamWaitEvent(st, h->ev_join, 0));
     } else if (h->kp.auto_reset)
         h->ops->reset(h, h->done_list, slot(h, CNT_DONE), obs_dev, ag_dev, dg_dev, st);
@@ -734,6 +765,19 @@ int xarm_debug_counts(xarm_handle *h, int32_t *finished, int32_t *handed_off, vo
     if (h->fast_pipeline) for (int k = 0; k < h->ho_stages; k++) *handed_off += c[cnt_stage(k)];   // staged step: one list per stage
     return XARM_OK;
 }
+int xarm_debug_stage_counts(xarm_handle *h, int32_t *handed_off, int32_t *finished_in_handoff, void *stream) {
+    if (!h || !handed_off || !finished_in_handoff) return XARM_E_INVALID;
+    DEVGUARD(h);
+    int c[CNT_STAGE_INTS] = {0};
+    HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(h, hipMemcpy(c, h->counters, sizeof c, hipMemcpyDeviceToHost));
+    for (int k = 0; k < XARM_HO_MAX_STAGES; k++) {
+        const bool live = h->fast_pipeline && k < h->ho_stages;
+        handed_off[k] = live ? c[cnt_stage(k)] : 0;
+        finished_in_handoff[k] = (live && h->reset_overlap && (k == 0 || h->reset_per_stage)) ? c[cnt_done_b(k)] : 0;
+    }
+    return XARM_OK;
+}
 int xarm_stage_info(const xarm_handle *h, int32_t *stages, int32_t *ticks) {
     if (!h || !stages || !ticks) return XARM_E_INVALID;
     const bool staged = h->fast_pipeline && h->ho_stages > 1 && !small_batch(h);
@@ -748,7 +792,7 @@ int xarm_pipeline_info(const xarm_handle *h, int32_t *fast_pipeline, int32_t *re
     if (!h || !fast_pipeline || !reset_overlap || !eject_coop_cap || !solver_iterations) return XARM_E_INVALID;
     // (the step limit is 0 for the env kinds without a cooperative step kernel)
     *fast_pipeline = (h->fast_pipeline && !small_batch(h)) ? 1 : 0;
-    *reset_overlap = (*fast_pipeline && h->reset_overlap) ? 1 : 0;
+    *reset_overlap = (*fast_pipeline && h->reset_overlap) ? (h->reset_per_stage ? 2 : 1) : 0;
     *eject_coop_cap = h->kp.eject_coop_cap;
 #if defined(XARM_SWEEP_VARIANT)
     *solver_iterations = XARM_SWEEP_VARIANT;

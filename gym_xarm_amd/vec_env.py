@@ -443,10 +443,11 @@ class XarmPickAndPlaceVecEnv:
 
     def pipeline_info(self):
         """which launches a step() call is made of and the solver constants the library was built with (include/xarm_hip.h
-        xarm_pipeline_info): dict(fast_pipeline, reset_overlap, eject_coop_cap, solver_iterations)"""
+        xarm_pipeline_info): dict(fast_pipeline, reset_overlap, reset_per_stage, eject_coop_cap, solver_iterations)"""
         v = [C.c_int32(0) for _ in range(4)]
         _native.check(self._L, self._h, self._L.xarm_pipeline_info(self._h, *[C.byref(x) for x in v]), "xarm_pipeline_info")
-        return dict(fast_pipeline=bool(v[0].value), reset_overlap=bool(v[1].value), eject_coop_cap=v[2].value, solver_iterations=v[3].value)
+        return dict(fast_pipeline=bool(v[0].value), reset_overlap=bool(v[1].value), reset_per_stage=v[1].value == 2,
+                    eject_coop_cap=v[2].value, solver_iterations=v[3].value)
 
     def stage_info(self):
         """the staged step of Handover (one stick) and PickAndPlace (include/xarm_hip.h xarm_stage_info): the first tick / substep of each
@@ -461,6 +462,14 @@ class XarmPickAndPlaceVecEnv:
         v = [C.c_int32(0) for _ in range(2)]
         _native.check(self._L, self._h, self._L.xarm_debug_counts(self._h, *[C.byref(x) for x in v], self._stream()), "xarm_debug_counts")
         return tuple(x.value for x in v)
+
+    def debug_stage_counts(self):
+        """(envs handed off, episodes that ended in the hand-off kernels) per stage of the last step() call, two lists of stage_info's
+        stage count (development hook, include/xarm_hip.h xarm_debug_stage_counts)"""
+        ho, fin = (C.c_int32 * _native.HO_MAX_STAGES)(), (C.c_int32 * _native.HO_MAX_STAGES)()
+        _native.check(self._L, self._h, self._L.xarm_debug_stage_counts(self._h, ho, fin, self._stream()), "xarm_debug_stage_counts")
+        n = len(self.stage_info()) - 1
+        return [int(x) for x in ho[:n]], [int(x) for x in fin[:n]]
 
     def library(self):
         """(xarm_version(), path of the loaded libxarm_hip.so)"""

@@ -105,7 +105,12 @@ typedef struct xarm_config {
 #define XARM_EJECT_COOP_CAP 32768
 /* A pipelined step with auto-reset resets the episodes that ended in the fast kernel on a side stream owned by the handle,
  * in parallel with the hand-off, and joins it (event wait) before its work on the caller's stream ends: the caller sees one
- * stream-ordered call.  XARM_RESET_OVERLAP=0 in the environment at xarm_create keeps everything on the caller's stream. */
+ * stream-ordered call.  XARM_RESET_OVERLAP=0 in the environment at xarm_create keeps everything on the caller's stream.
+ * The episodes that end in a hand-off kernel: with XARM_RESET_PER_STAGE_DEFAULT (env XARM_RESET_PER_STAGE = 0 / 1 at xarm_create)
+ * every hand-off stage of a staged step keeps a list of its own and resets it directly behind its hand-off, on that stage's side
+ * stream (the last stage's on the caller's stream); without, one list for all stages is reset after the last hand-off.  Same
+ * results either way: an env's reset does not depend on the envs it shares a wavefront with. */
+#define XARM_RESET_PER_STAGE_DEFAULT 1
 /* PickAndPlace handles of at most this many envs step on the cooperative kernel as well (env XARM_STEP_COOP_LIMIT) */
 #define XARM_STEP_COOP_LIMIT_DEFAULT 8192
 /* XarmHandover with one stick steps the same way at every batch size (unless step_coop_limit < 0 or XARM_STEP_PIPELINE=0 select
@@ -191,7 +196,8 @@ int xarm_kernel_limits(const xarm_handle *h, int32_t *reset_coop_limit, int32_t 
  *                    0: one step kernel (the cooperative one for batches of at most step_coop_limit envs).  Only
  *                    step_coop_limit < 0 or XARM_STEP_PIPELINE=0 turn the pipeline off - XARM_STEP_COOP_LIMIT=0 turns off
  *                    the cooperative STEP kernel of small batches, not the pipeline of large ones
- *   reset_overlap    1: PickAndPlace pipeline with the first reset launch on the handle's side stream (XARM_RESET_OVERLAP)
+ *   reset_overlap    non-zero: PickAndPlace pipeline with the first reset launch on the handle's side stream (XARM_RESET_OVERLAP);
+ *                    2: and a reset per hand-off stage behind that stage's hand-off (XARM_RESET_PER_STAGE), 1: one after the last
  *   eject_coop_cap   hand-off lists of at most this many envs step on the cooperative kernel, longer ones on the
  *                    one-env-per-lane kernel; INT32_MAX when step_coop_limit == 1 (the pin of
  *                    gym_xarm_amd.distributed.reproducible_limits('fast'): the choice is then a function of the config alone)
@@ -209,6 +215,10 @@ int xarm_stage_info(const xarm_handle *h, int32_t *stages, int32_t *ticks);
  * ended in the step kernels (a pipelined PickAndPlace call counts the ones that ended in the hand-off apart: not included) and
  * envs handed off by the fast kernel to the cooperative one (0 for a handle without the pipeline; the staged Handover step: all stages) */
 int xarm_debug_counts(xarm_handle *h, int32_t *finished, int32_t *handed_off, void *stream);
+/* the same counters per stage of a pipelined step, arrays of XARM_HO_MAX_STAGES entries: handed_off[c] = envs handed off by fast
+ * stage c, finished_in_handoff[c] = episodes that ended in the hand-off kernels of stage c (PickAndPlace with the side-stream reset;
+ * without XARM_RESET_PER_STAGE entry 0 holds the count of all stages).  Zero for stages the handle does not have. */
+int xarm_debug_stage_counts(xarm_handle *h, int32_t *handed_off, int32_t *finished_in_handoff, void *stream);
 
 /* StackTower: the row-set class each env's last substep fell into, uint8 [E] (bits 0-2 cube pairs (0,1) (0,2) (1,2) in
  * contact, bit 3 / 4 a finger pad of arm 0 / 1 active).  The step
