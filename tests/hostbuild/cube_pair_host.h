@@ -77,7 +77,8 @@ inline xk::EnvCfg cfg(uint64_t seed, int64_t off, int rt) { xk::EnvCfg c; memset
 template <typename T, typename Sc> void init(const xk::EnvCfg &c, int64_t E, double *state) {
     for (int64_t e = 0; e < E; e++) for (int a = 1; a >= 0; a--) { xs::Lane<T, Sc> L; xs::lane_init<T>(c, e, L); store(L, a, state + e * Sc::STATE_DIM); }
 }
-// mode 0: step, 1: reset of the envs with mask[e] != 0 (all without a mask); key (optional): the row-set class of the last substep
+// mode 0: step, 1: reset of the envs with mask[e] != 0 (all without a mask), 2 (tests only): one bare xs::tick of every env,
+// which writes state and key and no other output; key (optional): the row-set class of the last substep
 struct Job {
     int mode; xk::EnvCfg cfg; int64_t E; double *state; const double *act; const uint8_t *mask;
     double *obs, *ag, *dg, *rew; uint8_t *done, *succ, *key; PairShared *sh; int arm;
@@ -93,7 +94,15 @@ template <typename T, typename Sc> void *thread(void *p) {
         if (J.mode == 0) {
             T a[4]; for (int k = 0; k < 4; k++) a[k] = (T)J.act[e * 8 + 4 * J.arm + k];
             xs::lane_step<T>(J.cfg, L, J.arm, a, r, d, su, hl, x);
-        } else xs::lane_reset<T>(J.cfg, e, L, J.arm, hl, x);
+        } else if (J.mode == 1) xs::lane_reset<T>(J.cfg, e, L, J.arm, hl, x);
+        else {
+            xs::tick<T>(L, hl, J.arm, x);
+            J.sh->bar.wait();
+            store(L, J.arm, J.state + e * Sc::STATE_DIM);
+            if (J.arm == 0 && J.key) J.key[e] = (uint8_t)L.cls;
+            J.sh->bar.wait();
+            continue;
+        }
         T o8[8];
         xs::arm_obs(L, J.arm, o8);
         J.sh->bar.wait();

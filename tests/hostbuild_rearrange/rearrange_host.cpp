@@ -23,6 +23,21 @@ void ra_reset(int f32, uint64_t seed, int64_t off, int rt, int64_t E, double *st
     auto c = cubes::cfg(seed, off, rt);
     if (f32) cubes::run<float, Sc>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key); else cubes::run<double, Sc>(1, c, E, state, 0, mask, obs, ag, dg, 0, 0, 0, key);
 }
+// tests only: one bare tick (15 substeps towards the stored motor targets) of every row - the reset's tick without its draws
+void ra_tick(int f32, int64_t E, double *state, uint8_t *key) {
+    auto c = cubes::cfg(0, 0, 0);
+    if (f32) cubes::run<float, Sc>(2, c, E, state, 0, 0, 0, 0, 0, 0, 0, 0, key); else cubes::run<double, Sc>(2, c, E, state, 0, 0, 0, 0, 0, 0, 0, 0, key);
+}
+// tests only: the 16 arm entries of the observation (xs::arm_obs of both arms) of every row, float64
+void ra_arm_obs(int64_t E, const double *state, double *out) {
+    for (int64_t e = 0; e < E; e++)
+        for (int a = 0; a < 2; a++) {
+            xs::Lane<double, Sc> L; double o8[8];
+            cubes::load(state + e * Sc::STATE_DIM, a, L);
+            xs::arm_obs(L, a, o8);
+            for (int k = 0; k < 8; k++) out[e * 16 + 8 * a + k] = o8[k];
+        }
+}
 // the kernel's reward arithmetic (k_ra_compute_reward) over n rows of 12, in float32
 void ra_compute_reward(int rt, const float *ag, const float *g, int64_t n, float *out) {
     for (int64_t i = 0; i < n; i++) {

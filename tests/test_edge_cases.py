@@ -5,16 +5,19 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ENVS = [("XarmPDPickAndPlace-v0", 4), ("XarmReach-v0", 4), ("XarmPDHandover-v0", 8), ("XarmPDStackTower-v0", 8)]
+# (env id, action dim[, config])
+ENVS = [("XarmPDPickAndPlace-v0", 4), ("XarmReach-v0", 4), ("XarmPDHandover-v0", 8), ("XarmPDStackTower-v0", 8), ("XarmRearrange-v0", 8),
+        ("XarmHandover-v0", 8, dict(GUI=False, num_obj=2, same_side_rate=0.5, goal_shape="any", use_stand=False))]   # two sticks (test_stress.py)
+PARAMS = [pytest.param(*(e + (None,))[:3], id="%s-%d" % e[:2] + ("-cfg" if len(e) > 2 else "")) for e in ENVS]
 
 
-@pytest.mark.parametrize("env_id,A", ENVS)
-def test_masks_empty_batches_and_bad_arguments(env_id, A):
+@pytest.mark.parametrize("env_id,A,cfg", PARAMS)
+def test_masks_empty_batches_and_bad_arguments(env_id, A, cfg):
     import torch
     import gym_xarm_amd
     from gym_xarm_amd._native import XarmNativeError
     E = 37                                                       # not a multiple of 32 / 64
-    env = gym_xarm_amd.make(env_id, num_envs=E, seed=2, auto_reset=False)
+    env = gym_xarm_amd.make(env_id, num_envs=E, seed=2, auto_reset=False, config=cfg)
     env.reset()
     before = env.get_state().clone()
     env.reset(mask=torch.zeros(E, dtype=torch.uint8))            # empty mask: nothing changes
@@ -35,19 +38,19 @@ def test_masks_empty_batches_and_bad_arguments(env_id, A):
     with pytest.raises(ValueError):
         env.reset(mask=torch.zeros(E + 1, dtype=torch.uint8))
     with pytest.raises(XarmNativeError):
-        gym_xarm_amd.make(env_id, num_envs=0)
+        gym_xarm_amd.make(env_id, num_envs=0, config=cfg)
     env.close()
 
 
-@pytest.mark.parametrize("env_id,A", ENVS)
-def test_an_env_does_not_depend_on_its_batch(env_id, A):
+@pytest.mark.parametrize("env_id,A,cfg", PARAMS)
+def test_an_env_does_not_depend_on_its_batch(env_id, A, cfg):
     """every env of a small batch equals, bit for bit, the same global env id in a larger batch - whatever the grid
     size (ragged last workgroup, the XCD-contiguous block remap of the cooperative kernels with nwg % 8 != 0)"""
     import torch
     import gym_xarm_amd
     ref = None
     for E in (1000, 1, 33, 37 * 4 + 3, 999):
-        env = gym_xarm_amd.make(env_id, num_envs=E, seed=5)
+        env = gym_xarm_amd.make(env_id, num_envs=E, seed=5, config=cfg)
         env.reset()
         gen = torch.Generator(device=env.device)
         gen.manual_seed(1)

@@ -2,7 +2,9 @@
 float64 / float32.  The oracle stays StackTower's three-cube oracle: a Rearrange state that holds a StackTower state with the
 fourth cube parked on the table, away from every arm and cube, must follow OracleStackTower step for step (the parked cube's
 table rows touch only itself, its pairs are outside the broad phase, the rows left over are StackTower's in StackTower's
-order).  States where all four cubes interact are checked for physical invariants and float32 against float64."""
+order).  States where all four cubes interact are checked for physical invariants and float32 against float64.
+The reset: rearrange_host.reset_reference (NumPy + one bare tick) against the core's lane_reset, step_auto, and the shares of
+contact and exempt resets in the batch that the GPU reset tests use."""
 import os
 
 import numpy as np
@@ -200,6 +202,94 @@ def test_rearrange_host_reset_and_goal_sampling():
     from conftest import HostCore
     s3 = HostCore().st_init(16, f32=0, seed=11)
     assert np.array_equal(s3[:, 54:63], st[:16, R.BP:R.BP + 9])
+
+
+RESET_E, RESET_SEED = 161, 11        # the batch of the GPU full-reset test (tests/test_rearrange_gpu.py)
+STATE_FIELDS = ("state", "obs", "ag", "dg", "key")
+
+
+def reset_batch_actions(E, k):
+    """the k-th of the two random actions that precede the reset batches (CPU precondition and GPU tests alike)"""
+    return np.random.default_rng(700 + k).uniform(-1, 1, (E, 8)).astype(np.float32)
+
+
+def _after_two_steps(E, seed, off=0):
+    st = R.init(E, seed=seed, off=off)
+    for k in range(2):
+        st = R.step(st, reset_batch_actions(E, k), f32=0, seed=seed, off=off)[0]
+    return st
+
+
+def _assert_same(a, b, tol=1e-12):
+    for name, x, y in zip(STATE_FIELDS, a, b):
+        assert np.abs(np.asarray(x, dtype=np.float64) - np.asarray(y, dtype=np.float64)).max() <= tol, name
+
+
+def test_rearrange_reset_reference_equals_core_reset():
+    """reset_reference (NumPy teleport + oracle Philox draws + one bare tick of the core) against the core's own lane_reset, f64:
+    every state field and output within 1e-12 (measured: 0), episodes 0 -> 1 -> 2, a ragged mask, a batch over the 2^32 boundary"""
+    E = 48
+    st = _after_two_steps(E, seed=3)
+    assert np.abs(st[:, R.QT:R.QT + 18] - st[:, R.Q:R.Q + 18]).max() > 1e-3          # the old motor targets matter
+    one, ref = R.reset(st, seed=3), R.reset_reference(st, seed=3)
+    _assert_same(one, ref)
+    assert (ref[0][:, R.EPISODE] == 1).all() and (ref[0][:, R.STEPS] == 0).all()
+    two, ref2 = R.reset(one[0], seed=3), R.reset_reference(ref[0], seed=3)
+    _assert_same(two, ref2)
+    assert (ref2[0][:, R.EPISODE] == 2).all()
+    assert (np.abs(ref2[3] - ref[3]).reshape(E, 4, 3)[..., :2] > 0).all()           # new goals
+    # ragged mask: rows outside it keep their bits
+    m = np.zeros(E, np.uint8)
+    m[[0, 5, 31, 32, 47]] = 1
+    a, b = R.reset(st, mask=m, seed=3), R.reset_reference(st, mask=m, seed=3)
+    _assert_same(a, b)
+    assert np.array_equal(b[0][m == 0], st[m == 0]) and np.array_equal(b[0][m == 1], ref[0][m == 1])
+    # global env ids on both sides of the 32-bit word boundary: rows 0-23 have high word 0, rows 24-47 high word 1
+    off = 2 ** 32 - 24
+    st = _after_two_steps(E, seed=3, off=off)
+    a, b = R.reset(st, seed=3, off=off), R.reset_reference(st, seed=3, off=off)
+    _assert_same(a, b)
+    low = R.reset_reference(st, seed=3, off=0)          # the low word alone would give rows 24.. these goals
+    assert (np.abs(b[3][24:] - low[3][24:]).reshape(24, 4, 3)[..., :2] > 0).all()
+
+
+def test_rearrange_step_auto_resets_exactly_the_envs_that_end():
+    E = 8
+    st = _after_two_steps(E, seed=4)
+    st[:, R.STEPS] = [49, 48] * 4
+    act = reset_batch_actions(E, 0)
+    out = R.step_auto(st, act, seed=4)
+    s = out["step"]
+    assert np.array_equal(out["done"], [1, 0] * 4)
+    cube, goal = R.drawn(4, 0, [1] * E)
+    g = out["state"][:, R.GOAL:R.GOAL + 12].reshape(E, 4, 3)
+    assert np.array_equal(g[0::2, :, :2], goal[0::2]) and (g[..., 2] == 0.025).all()
+    assert np.array_equal(out["state"][1::2], s[0][1::2]) and np.array_equal(out["state"][1::2, R.GOAL:R.GOAL + 12], st[1::2, R.GOAL:R.GOAL + 12])
+    assert np.array_equal(out["state"][:, R.STEPS], [0, 49] * 4) and np.array_equal(out["state"][:, R.EPISODE], [1, 0] * 4)
+    assert np.array_equal(out["term"], s[1]) and np.array_equal(out["rew"], s[4])
+    assert np.array_equal(out["obs"][1::2], s[1][1::2]) and np.array_equal(out["dg"][0::2], out["state"][0::2, R.GOAL:R.GOAL + 12])
+    assert np.array_equal(out["obs"][0::2, 0:12], out["state"][0::2, R.BP:R.BP + 12]) and np.array_equal(out["ag"], out["obs"][:, 0:12])
+    # the core's own reset of those envs is the same reset
+    core = R.reset(s[0], mask=s[5], seed=4)
+    assert np.abs(core[0] - out["state"]).max() <= 1e-12
+
+
+def test_rearrange_reset_batch_holds_contact_resets_and_few_exempt(parity):
+    """what the GPU reset tests rely on, for their seed and size (161 envs, seed 11): cubes spawn without rejection, so a share
+    of the resets ends its tick with a cube pair in contact, and few are conditioned badly enough to be exempt.
+    Measured: 18.6 % contact resets (30 of 161); 12.4 % exempt (20, all of them contact resets: an overlapping spawn is pushed apart
+    within the tick, and the cube velocities it leaves answer a 1e-6 shift of the spawn with up to 0.23 m/s; seeds 1 - 22 gave
+    19 - 30 % contact resets and 12 - 21 % exempt, the exempt share about 0.6 of the contact share)."""
+    st = _after_two_steps(RESET_E, RESET_SEED)
+    ref = R.reset_reference(st, seed=RESET_SEED)
+    sens = R.reset_sens(st, ref, seed=RESET_SEED)
+    contact = (ref[4] & 0x3F) != 0
+    print("contact resets %.3f, exempt %.3f, max sens %.2e" % (contact.mean(), (sens > parity.SENS_EXEMPT).mean(), sens.max()))
+    assert contact.mean() >= 0.10
+    assert (sens > parity.SENS_EXEMPT).mean() <= 0.15
+    # the core's float32 build stays inside the project's bounds on this batch
+    f32 = R.reset(st, f32=1, seed=RESET_SEED)
+    parity.compare(f32[0][:, R.RESET_FIELDS], ref[0][:, R.RESET_FIELDS], sens, frac_tight=0.7, max_exempt=0.15, what="host f32 reset")
 
 
 def test_rearrange_host_reward_matches_reference_numpy():

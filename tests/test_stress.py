@@ -31,6 +31,7 @@ def test_oracle_free_spin_does_not_gain_energy(oracle):
     ("XarmPDHandover-v0", 2048, 8, 120, None),
     ("XarmHandover-v0", 2048, 8, 120, dict(GUI=False, num_obj=2, same_side_rate=0.5, goal_shape="any", use_stand=False)),   # the reference's test.py config
     ("XarmPDStackTower-v0", 2048, 8, 110, None),
+    ("XarmRearrange-v0", 2048, 8, 110, None),
 ])
 def test_long_hostile_rollouts_stay_finite(env_id, E, A, steps, cfg):
     import torch
