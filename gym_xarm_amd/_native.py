@@ -22,7 +22,7 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
-           "xarm_policy_act"]
+           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -93,6 +93,16 @@ class XarmPolicyWeights(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in POLICY_WEIGHT_FIELDS]
 
 
+class XarmA2CLayout(C.Structure):
+    """include/xarm_hip.h xarm_a2c_layout (20 bytes)"""
+    _fields_ = [("num_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("hidden", C.c_int32)]
+
+
+class XarmA2CParams(C.Structure):
+    """include/xarm_hip.h xarm_a2c_params (56 bytes)"""
+    _fields_ = [(k, C.c_double) for k in ("gamma", "lr", "alpha", "eps", "vf_coef", "ent_coef", "max_grad_norm")]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -147,6 +157,9 @@ def load(path=None):
     L.xarm_norm_obs.argtypes = [nl, npar] + [vp] * 6 + [C.c_int32, vp, vp]
     L.xarm_norm_step.argtypes = [nl, npar] + [vp] * 16
     L.xarm_policy_act.argtypes = [C.POINTER(XarmPolicyLayout), C.POINTER(XarmPolicyParams), C.POINTER(XarmPolicyWeights)] + [vp] * 10
+    al = C.POINTER(XarmA2CLayout)
+    L.xarm_a2c_workspace_bytes.argtypes = [al, C.POINTER(C.c_int64)]
+    L.xarm_a2c_update.argtypes = [al, C.POINTER(XarmA2CParams), C.POINTER(XarmPolicyWeights), C.POINTER(XarmPolicyWeights)] + [vp] * 11
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

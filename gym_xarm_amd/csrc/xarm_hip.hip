@@ -34,6 +34,7 @@
 #include "xarm_her_core.h"
 #include "xarm_norm_core.h"
 #include "xarm_policy_core.h"
+#include "xarm_a2c_core.h"
 
 using namespace xd;
 
@@ -983,6 +984,48 @@ int xarm_policy_act(const xarm_policy_layout *layout, const xarm_policy_params *
     a.action = out_action; a.env_action = out_env_action; a.logp = out_logp; a.value = out_value;
     const int le = xpol::launch_policy(a, calls_i64, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_policy_act: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ A2C update (xarm_k_a2c.hip)
+int xarm_a2c_workspace_bytes(const xarm_a2c_layout *layout, int64_t *bytes) {
+    if (const char *why = xa2c::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_a2c_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_a2c_workspace_bytes: NULL pointer");
+    xa2c::Shape s;
+    xa2c::Work k;
+    xa2c::fill_shape(s, layout);
+    xa2c::fill_work(k, s);
+    *bytes = k.total;
+    return XARM_OK;
+}
+
+int xarm_a2c_update(const xarm_a2c_layout *layout, const xarm_a2c_params *params, const xarm_policy_weights *weights,
+                    const xarm_policy_weights *square_avg, const float *obs, const float *action, const float *reward, const float *done,
+                    const float *use, const float *last_obs, void *workspace, float *out_returns, float *out_grad, float *out_stats,
+                    void *stream) {
+    if (const char *why = xa2c::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_a2c_update: %s", why);
+    if (const char *why = xa2c::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_a2c_update: %s", why);
+    if (!weights || !square_avg) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_a2c_update: weights / square_avg is NULL");
+    if (layout->num_envs == 0) return XARM_OK;
+    if (const char *why = xa2c::pointer_error(layout, weights, square_avg, obs, action, reward, done, last_obs, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_a2c_update: %s", why);
+    xa2c::Dev d = {};
+    xa2c::Work k;
+    xa2c::fill_shape(d.s, layout);
+    xa2c::fill_hyper(d.h, params);
+    xa2c::fill_work(k, d.s);
+    xa2c::tensors_of(weights, d.w);
+    xa2c::tensors_of(square_avg, d.sq);
+    d.pi = xpol::Tower{d.w[0], d.w[1], d.w[2], d.w[3], d.w[4], d.w[5]};
+    d.vf = xpol::Tower{d.w[6], d.w[7], d.w[8], d.w[9], d.w[10], d.w[11]};
+    d.obs = obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.last_obs = last_obs;
+    char *base = (char *)workspace;
+    d.boot = (float *)(base + k.boot); d.mean = (float *)(base + k.mean); d.env = (float *)(base + k.env); d.value = (float *)(base + k.value);
+    d.ret = (float *)(base + k.ret); d.partial = (float *)(base + k.partial); d.scal = (double *)(base + k.scal); d.grad = (float *)(base + k.grad);
+    d.normpart = (double *)(base + k.normpart);
+    d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
+    const int le = xa2c::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_a2c_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -1,0 +1,310 @@
+// xarm_k_a2c.hip - the kernels of the device-resident A2C update.  Core: xarm_a2c_core.h.
+// Built with -ffp-contract=off (build.py UNIT_FLAGS): every float32 operation is the one the host build performs.
+//
+// One update is six launches on the caller's stream:
+//   k_policy_act    (xarm_k_policy.hip, deterministic) on last_obs: the bootstrap value
+//   k_policy_act    on the T E rows of obs: mean and value of every row - the policy kernel's own bits
+//   k_a2c_returns   one thread per env: the return recursion from the bootstrap value down
+//   k_a2c_grad      grid (groups, 2 towers), 256 threads.  A workgroup walks the 64-row tiles g, g + groups, ... of ONE tower.  Per
+//                   tile, in LDS and transposed ([unit][row], stride 65: a lane per row and a lane per unit both read without bank
+//                   conflicts): the rows, h1 and h2 from the policy's chains (lane = row, wavefront w = units 16 w .. 16 w + 15, so
+//                   the weights are wavefront-uniform loads), the output deltas, then d2 and d1 in place over h2 and h1 once the
+//                   outer products that need h2 / h1 are taken.  The gradient lives in registers across the tiles: thread
+//                   (ib, jb) = (t & 15, t >> 4) owns the entries (ib + 16 a, jb + 16 b) of dW2 and dW1, thread (t & 63, t >> 6)
+//                   the entries of dW3.  At the end the workgroup stores its float32 sums to its own slice of the workspace,
+//                   and the policy tower's workgroups their loss / n_use / log_std sums (float64, lanes added in lane order).
+//   k_a2c_reduce    one thread per parameter: the slices added in float64 in group order, / n_use, the entropy term, the float32
+//                   gradient; a block's sum of squares (a fixed tree) to normpart; block 0 writes the losses
+//   k_a2c_apply     one thread per parameter: norm from normpart in block order, the clip, RMSprop
+// No atomics anywhere: the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+#include "xarm_a2c_core.h"
+
+namespace xa2c {
+
+constexpr int THREADS = 256, LS = ROWS + 1, UPW = 16;     // LDS row stride; units per wavefront in the lane = row stages
+static_assert(ROWS == 64 && THREADS == 4 * ROWS && UPW * (THREADS / 64) == HID, "four wavefronts: 64 rows x 16 units each");
+
+__global__ __launch_bounds__(256) void k_a2c_returns(Dev d) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= d.s.E) return;
+    float r = d.boot[e];
+    for (int k = d.s.T - 1; k >= 0; k--) {
+        const int64_t n = (int64_t)k * d.s.E + e;
+        r = return_step(d.h.gamma, d.done[n], d.reward[n], r);
+        d.ret[n] = r;
+        if (d.out_returns != nullptr) d.out_returns[n] = r;
+    }
+}
+
+// JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
+template <int JW> __global__ __launch_bounds__(THREADS) void k_a2c_grad(Dev d) {
+    __shared__ __attribute__((aligned(16))) float Xt[16 * JW * LS];
+    __shared__ __attribute__((aligned(16))) float H1t[HID * LS];
+    __shared__ __attribute__((aligned(16))) float H2t[HID * LS];
+    __shared__ __attribute__((aligned(16))) float D3t[MAX_ACT * LS];
+    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), u0 = UPW * wv, ib = t & 15, jb = t >> 4;
+    const bool is_pi = blockIdx.y == 0;
+    const Tower T = is_pi ? d.pi : d.vf;
+    const int D = d.s.D, A = d.s.A, G = d.s.G, g = blockIdx.x, nout = is_pi ? A : 1;
+    const int64_t N = d.s.N;
+
+    float g1[4][JW], gb1[4], g2[4][4], gb2[4], g3[4], gb3[4], dls[MAX_ACT];
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        gb1[a] = gb2[a] = g3[a] = gb3[a] = 0.0f;
+#pragma unroll
+        for (int b = 0; b < 4; b++) g2[a][b] = 0.0f;
+#pragma unroll
+        for (int m = 0; m < JW; m++) g1[a][m] = 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < MAX_ACT; c++) dls[c] = 0.0f;
+    double ploss = 0.0, vloss = 0.0, nuse = 0.0;
+
+    for (int64_t tile = g; tile < d.s.tiles; tile += G) {
+        const int64_t r0 = tile * ROWS;
+        // the tile's rows (zeros past the batch and past column D) and the deltas at the outputs (wavefront 0: lane = row)
+        for (int idx = t; idx < 16 * JW * ROWS; idx += THREADS) {
+            const int rr = idx / (16 * JW), j = idx - rr * (16 * JW);
+            const int64_t n = r0 + rr;
+            Xt[j * LS + rr] = (n < N && j < D) ? d.obs[n * D + j] : 0.0f;
+        }
+        if (wv == 0) {
+            const int64_t n = r0 + r;
+#pragma unroll
+            for (int c = 0; c < MAX_ACT; c++) D3t[c * LS + r] = 0.0f;
+            if (n < N) {
+                const float u = d.use != nullptr ? d.use[n] : 1.0f, v = d.value[n], rt = d.ret[n];
+                if (is_pi) {
+                    const float adv = rt - v;
+                    const float lp = pi_deltas(A, d.mean + n * A, d.action + n * A, d.w[12], adv, u, D3t + r, LS, dls);
+                    ploss += (double)(adv * lp * u);
+                    vloss += (double)((rt - v) * (rt - v) * u);
+                    nuse += (double)u;
+                } else {
+                    D3t[r] = value_delta(d.h.vf2, v, rt, u);
+                }
+            }
+        }
+        __syncthreads();
+
+        {   // h1
+            float acc[UPW];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) acc[u] = T.b1[u0 + u];
+            xpol::layer1_chains<UPW>(T.W1 + u0 * D, D, Xt + r, LS, acc);
+#pragma unroll
+            for (int u = 0; u < UPW; u++) H1t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
+        }
+        __syncthreads();
+        {   // h2
+            float acc[UPW];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) acc[u] = T.b2[u0 + u];
+            xpol::hidden_chains<UPW>(T.W2 + u0 * HID, H1t + r, LS, acc);
+#pragma unroll
+            for (int u = 0; u < UPW; u++) H2t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
+        }
+        __syncthreads();
+
+        // dW3, db3: thread (unit r, outputs 4 wv .. 4 wv + 3)
+        if (4 * wv < nout) {
+            for (int rr = 0; rr < ROWS; rr++) {
+                const float hv = H2t[r * LS + rr];
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    const float dv = D3t[(4 * wv + a) * LS + rr];
+                    g3[a] = fma32(dv, hv, g3[a]);
+                    gb3[a] += dv;
+                }
+            }
+        }
+        __syncthreads();
+        {   // d2 over h2
+            float pre[UPW];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
+            for (int c = 0; c < nout; c++) {
+                const float dv = D3t[c * LS + r];
+#pragma unroll
+                for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W3[c * HID + u0 + u], dv, pre[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < UPW; u++) {
+                const float hv = H2t[(u0 + u) * LS + r];
+                H2t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
+            }
+        }
+        __syncthreads();
+
+        // dW2, db2: thread (ib, jb) owns (ib + 16 a, jb + 16 b)
+        for (int rr = 0; rr < ROWS; rr++) {
+            float dv[4], hv[4];
+#pragma unroll
+            for (int a = 0; a < 4; a++) { dv[a] = H2t[(ib + 16 * a) * LS + rr]; hv[a] = H1t[(jb + 16 * a) * LS + rr]; }
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                gb2[a] += dv[a];
+#pragma unroll
+                for (int b = 0; b < 4; b++) g2[a][b] = fma32(dv[a], hv[b], g2[a][b]);
+            }
+        }
+        __syncthreads();
+        {   // d1 over h1
+            float pre[UPW];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
+            for (int k = 0; k < HID; k++) {
+                const float dv = H2t[k * LS + r];
+#pragma unroll
+                for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W2[k * HID + u0 + u], dv, pre[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < UPW; u++) {
+                const float hv = H1t[(u0 + u) * LS + r];
+                H1t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
+            }
+        }
+        __syncthreads();
+
+        // dW1, db1: thread (ib, jb) owns (ib + 16 a, jb + 16 m)
+        for (int rr = 0; rr < ROWS; rr++) {
+            float dv[4], xv[JW];
+#pragma unroll
+            for (int a = 0; a < 4; a++) dv[a] = H1t[(ib + 16 * a) * LS + rr];
+#pragma unroll
+            for (int m = 0; m < JW; m++) xv[m] = Xt[(jb + 16 * m) * LS + rr];
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                gb1[a] += dv[a];
+#pragma unroll
+                for (int m = 0; m < JW; m++) g1[a][m] = fma32(dv[a], xv[m], g1[a][m]);
+            }
+        }
+        __syncthreads();
+    }
+
+    // the workgroup's slice: one tower's tensors in the flat order
+    float *sW1 = d.partial + ((int64_t)blockIdx.y * G + g) * d.s.pstride, *sb1 = sW1 + HID * D, *sW2 = sb1 + HID, *sb2 = sW2 + HID * HID,
+          *sW3 = sb2 + HID, *sb3 = sW3 + nout * HID;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = ib + 16 * a;
+#pragma unroll
+        for (int m = 0; m < JW; m++)
+            if (jb + 16 * m < D) sW1[i * D + jb + 16 * m] = g1[a][m];
+#pragma unroll
+        for (int b = 0; b < 4; b++) sW2[i * HID + jb + 16 * b] = g2[a][b];
+        if (jb == 0) { sb1[i] = gb1[a]; sb2[i] = gb2[a]; }
+        const int c = 4 * wv + a;
+        if (c < nout) {
+            sW3[c * HID + r] = g3[a];
+            if (r == 0) sb3[c] = gb3[a];
+        }
+    }
+
+    if (is_pi) {    // the scalars: lanes of wavefront 0 added in lane order (the loop above ended on a barrier)
+        double *sc = (double *)H1t;
+        static_assert((3 + MAX_ACT) * 64 * sizeof(double) <= HID * LS * sizeof(float) && 3 + MAX_ACT <= NSCAL, "the scalars fit h1's tile");
+        if (wv == 0) {
+            sc[r] = ploss; sc[64 + r] = vloss; sc[128 + r] = nuse;
+#pragma unroll
+            for (int c = 0; c < MAX_ACT; c++) sc[(3 + c) * 64 + r] = (double)dls[c];
+        }
+        __syncthreads();
+        if (t < NSCAL) {
+            double sum = 0.0;
+            if (t < 3 + MAX_ACT)
+                for (int l = 0; l < 64; l++) sum += sc[t * 64 + l];
+            d.scal[(int64_t)g * NSCAL + t] = sum;
+        }
+    }
+}
+
+__device__ __forceinline__ double n_use_of(const Dev &d) {
+    double nuse = 0.0;
+    for (int g = 0; g < d.s.G; g++) nuse += d.scal[(int64_t)g * NSCAL + 2];
+    return nuse > 1.0 ? nuse : 1.0;
+}
+
+__global__ __launch_bounds__(RED) void k_a2c_reduce(Dev d) {
+    __shared__ double red[RED];
+    const int tid = threadIdx.x, G = d.s.G;
+    const int64_t p = (int64_t)blockIdx.x * RED + tid;
+    const double n_use = n_use_of(d);
+    double sq = 0.0;
+    if (p < d.s.P) {
+        double sum = 0.0;
+        const bool ls = p >= d.s.off[12];
+        if (ls) {
+            const int c = (int)(p - d.s.off[12]);
+            for (int g = 0; g < G; g++) sum += d.scal[(int64_t)g * NSCAL + 3 + c];
+        } else {
+            const int tower = p >= d.s.off[6] ? 1 : 0;
+            const float *base = d.partial + (int64_t)tower * G * d.s.pstride + (p - (tower ? d.s.off[6] : 0));
+            for (int g = 0; g < G; g++) sum += (double)base[(int64_t)g * d.s.pstride];
+        }
+        double v = sum / n_use;
+        if (ls) v -= d.h.ent_coef;
+        const float gf = (float)v;
+        d.grad[p] = gf;
+        if (d.out_grad != nullptr) d.out_grad[p] = gf;
+        sq = (double)gf * (double)gf;
+    }
+    red[tid] = sq;
+    __syncthreads();
+    for (int s = RED / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) d.normpart[blockIdx.x] = red[0];
+    if (blockIdx.x == 0 && tid == 0 && d.out_stats != nullptr) {
+        double ploss = 0.0, vloss = 0.0, ent = 0.0;
+        for (int g = 0; g < G; g++) { ploss += d.scal[(int64_t)g * NSCAL]; vloss += d.scal[(int64_t)g * NSCAL + 1]; }
+        for (int c = 0; c < d.s.A; c++) ent += (double)d.w[12][c] + 0.5 + 0.918938533204672742;
+        d.out_stats[0] = (float)(-ploss / n_use); d.out_stats[1] = (float)(vloss / n_use); d.out_stats[2] = (float)ent;
+        d.out_stats[4] = (float)n_use; d.out_stats[5] = d.out_stats[6] = d.out_stats[7] = 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(RED) void k_a2c_apply(Dev d) {
+    const int64_t p = (int64_t)blockIdx.x * RED + threadIdx.x;
+    double sum2 = 0.0;
+    for (int b = 0; b < d.s.NB; b++) sum2 += d.normpart[b];
+    const float norm = (float)__builtin_sqrt(sum2), coef = clip_coef(norm, d.h.max_norm);
+    if (p == 0 && d.out_stats != nullptr) d.out_stats[3] = norm;
+    if (p >= d.s.P) return;
+    float *wp = d.w[0], *sp = d.sq[0];
+    int64_t o = 0;
+#pragma unroll
+    for (int i = 1; i < NTENS; i++)
+        if (p >= d.s.off[i]) { wp = d.w[i]; sp = d.sq[i]; o = d.s.off[i]; }
+    float sq = sp[p - o], w = wp[p - o];
+    rmsprop(d.h, d.grad[p] * coef, sq, w);
+    sp[p - o] = sq;
+    wp[p - o] = w;
+}
+
+int launch_update(const Dev &d, void *stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    xpol::Args a = {};
+    a.E = d.s.E; a.obs = d.s.D; a.D = d.s.D; a.A = d.s.A; a.deterministic = 1; a.pi = d.pi; a.vf = d.vf; a.log_std = d.w[12];
+    a.x0 = d.last_obs; a.action = d.mean; a.env_action = d.env; a.value = d.boot;
+    int le = xpol::launch_policy(a, nullptr, stream);
+    if (le != 0) return le;
+    a.E = d.s.N; a.x0 = d.obs; a.value = d.value;
+    le = xpol::launch_policy(a, nullptr, stream);
+    if (le != 0) return le;
+    k_a2c_returns<<<dim3((unsigned)((d.s.E + 255) / 256)), dim3(256), 0, s>>>(d);
+    const dim3 grid((unsigned)d.s.G, 2), block(THREADS);
+    if (d.s.D <= 16) k_a2c_grad<1><<<grid, block, 0, s>>>(d);
+    else if (d.s.D <= 32) k_a2c_grad<2><<<grid, block, 0, s>>>(d);
+    else if (d.s.D <= 64) k_a2c_grad<4><<<grid, block, 0, s>>>(d);
+    else k_a2c_grad<6><<<grid, block, 0, s>>>(d);
+    k_a2c_reduce<<<dim3((unsigned)d.s.NB), dim3(RED), 0, s>>>(d);
+    k_a2c_apply<<<dim3((unsigned)d.s.NB), dim3(RED), 0, s>>>(d);
+    return (int)hipGetLastError();
+}
+
+}  // namespace xa2c

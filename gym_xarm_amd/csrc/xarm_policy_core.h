@@ -265,26 +265,58 @@ XARM_HD float finish_column(float mean, float log_std, float z, bool determinist
     return t - 0.918938533204672742f;
 }
 
+// ---- the layers' chains, NU units side by side (every unit's own chain is the one described at the top: from the bias, layer 1 over
+// the columns in natural order with the zero operand behind an odd D, layers 2 and 3 in the order KORD).  W: the first unit's row;
+// x / h: operand k at x[k * xs].  The host rows below run them with NU = 1, the A2C update (xarm_a2c_core.h) with a row's 16 units.
+constexpr int kord(int s) { return unit_of(s >> 5, (s >> 1) & 15, s & 1); }   // KORD[s]
+constexpr bool kord_is_the_table() {
+    for (int s = 0; s < HID; s++)
+        if (kord(s) != KORD[s]) return false;
+    return true;
+}
+static_assert(kord_is_the_table(), "kord(s) must be KORD[s]");
+template <int NU> XARM_HD void layer1_chains(const float *W, int D, const float *x, int xs, float (&acc)[NU]) {
+    for (int k = 0; k < D; k++) {
+        const float xk = x[k * xs];
+#pragma unroll
+        for (int u = 0; u < NU; u++) acc[u] = fma32(W[u * D + k], xk, acc[u]);
+    }
+    if (D & 1) {
+#pragma unroll
+        for (int u = 0; u < NU; u++) acc[u] = fma32(0.0f, 0.0f, acc[u]);
+    }
+}
+template <int NU> XARM_HD void hidden_chains(const float *W, const float *h, int hs, float (&acc)[NU]) {
+    for (int s = 0; s < HID; s++) {
+        const int k = kord(s);
+        const float hk = h[k * hs];
+#pragma unroll
+        for (int u = 0; u < NU; u++) acc[u] = fma32(W[u * HID + k], hk, acc[u]);
+    }
+}
+
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
-// ---- the whole row as plain loops (the host build; the kernel holds the same chains in MFMA accumulators)
-inline void tower_row(const Tower &T, const float *x, int D, int nout, float *out) {
-    float h1[HID], h2[HID];
-    const int Dp = (D + 1) & ~1;
+// ---- the whole row as plain loops (the host build; the kernel holds the same chains in MFMA accumulators); h1 / h2 are kept
+inline void tower_row_keep(const Tower &T, const float *x, int D, int nout, float *h1, float *h2, float *out) {
     for (int u = 0; u < HID; u++) {
-        float acc = T.b1[u];
-        for (int k = 0; k < Dp; k++) acc = fma32(k < D ? T.W1[u * D + k] : 0.0f, k < D ? x[k] : 0.0f, acc);
-        h1[u] = tanh_f(acc);
+        float acc[1] = {T.b1[u]};
+        layer1_chains<1>(T.W1 + u * D, D, x, 1, acc);
+        h1[u] = tanh_f(acc[0]);
     }
     for (int u = 0; u < HID; u++) {
-        float acc = T.b2[u];
-        for (int s = 0; s < HID; s++) acc = fma32(T.W2[u * HID + KORD[s]], h1[KORD[s]], acc);
-        h2[u] = tanh_f(acc);
+        float acc[1] = {T.b2[u]};
+        hidden_chains<1>(T.W2 + u * HID, h1, 1, acc);
+        h2[u] = tanh_f(acc[0]);
     }
     for (int u = 0; u < nout; u++) {
-        float acc = T.b3[u];
-        for (int s = 0; s < HID; s++) acc = fma32(T.W3[u * HID + KORD[s]], h2[KORD[s]], acc);
-        out[u] = acc;
+        float acc[1] = {T.b3[u]};
+        hidden_chains<1>(T.W3 + u * HID, h2, 1, acc);
+        out[u] = acc[0];
     }
+}
+inline void tower_row(const Tower &T, const float *x, int D, int nout, float *out) {
+    float h1[HID], h2[HID];
+    tower_row_keep(T, x, D, nout, h1, h2, out);
 }
 
 inline void row(const Args &a, int64_t e) {

@@ -1,0 +1,146 @@
+"""Device-resident A2C update: the update block of train.py - bootstrap value, n-step returns, the backward of both towers,
+`clip_grad_norm_` and `RMSprop.step` - as one stream-ordered call of six HIP launches (csrc/xarm_k_a2c.hip).
+
+The torch update of train.py runs on the order of a hundred small launches per update: a second forward of both towers over
+n_steps x num_envs rows under autograd, the backward, the clip and the optimiser.  `DeviceA2C` keeps the rollout in preallocated
+buffers and updates the module's own parameter tensors in place, so a `DevicePolicy` on the same module (or the module itself)
+sees the new weights in its next call.  The torch update stays as it is and is the checker (tests/test_a2c_host.py,
+tests/test_a2c_gpu.py)."""
+import ctypes as C
+
+import torch
+
+from . import _native
+
+HYPER = ("gamma", "lr", "alpha", "eps", "vf_coef", "ent_coef", "max_grad_norm")
+
+
+def module_params(model):
+    """the 13 parameter tensors of a train.ActorCritic in the order of include/xarm_hip.h xarm_policy_weights"""
+    m = model
+    return (m.pi[0].weight, m.pi[0].bias, m.pi[2].weight, m.pi[2].bias, m.pi[4].weight, m.pi[4].bias,
+            m.vf[0].weight, m.vf[0].bias, m.vf[2].weight, m.vf[2].bias, m.vf[4].weight, m.vf[4].bias, m.log_std)
+
+
+def load_square_avg(square_avg, opt, params):
+    """copy the `square_avg` state of a torch.optim.RMSprop built on `params` into the 13 state tensors (zeros for a parameter the
+    optimiser has not stepped yet).  Momentum and centred RMSprop have state the device update does not carry: refused."""
+    for g in opt.param_groups:
+        if g.get("momentum", 0) != 0 or g.get("centered", False) or g.get("weight_decay", 0) != 0:
+            raise ValueError("the device update is RMSprop without momentum, centring or weight decay")
+    with torch.no_grad():
+        for s, p in zip(square_avg, params):
+            st = opt.state.get(p, {})
+            if "square_avg" in st:
+                s.copy_(st["square_avg"])
+            else:
+                s.zero_()
+
+
+def export_square_avg(square_avg, opt, params):
+    """the other direction: the optimiser continues from the 13 state tensors.  A parameter the optimiser has not stepped yet gets
+    the state RMSprop itself would create (its `step` counter, which RMSprop keeps and never reads, starts at 0)."""
+    with torch.no_grad():
+        for s, p in zip(square_avg, params):
+            st = opt.state[p]
+            if "square_avg" in st:
+                st["square_avg"].copy_(s)
+            else:
+                st["step"] = torch.zeros((), dtype=torch.float32)
+                st["square_avg"] = s.detach().clone()
+
+
+class DeviceA2C:
+    """One A2C update per `update()` call on the model's GPU.
+
+    model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors; they are read and written in place.
+    `buffers`: obs [T, E, D], action [T, E, A], reward / done / use [T, E] and the workspace, allocated once; slice k of each is
+    contiguous, so `DevicePolicy.act_into` can write `buffers["action"][k]` directly.  `square_avg`: RMSprop's 13 state tensors.
+    `update(last_obs)` allocates nothing and reads nothing back, so it can be captured in a torch.cuda.graph; `stats` is the device
+    tensor [policy_loss, value_loss, entropy, grad_norm, n_use, 0, 0, 0] of the last update."""
+
+    def __init__(self, model, num_envs, n_steps=5, gamma=0.99, lr=7e-4, alpha=0.99, eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5):
+        self.model, self.num_envs, self.n_steps = model, int(num_envs), int(n_steps)
+        self.hyper = dict(gamma=gamma, lr=lr, alpha=alpha, eps=eps, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm)
+        self.obs_width = int(model.pi[0].in_features)
+        self.act_dim = int(model.pi[4].out_features)
+        if int(model.pi[0].out_features) != _native.POLICY_HIDDEN or int(model.pi[2].out_features) != _native.POLICY_HIDDEN:
+            raise ValueError("DeviceA2C updates 64-64 towers (XARM_POLICY_HIDDEN)")
+        self.device = model.log_std.device
+        if self.device.type != "cuda":
+            raise ValueError("DeviceA2C runs the update with HIP kernels on the model's GPU: the model is on '%s'.  There is no host "
+                             "path; the torch update of train.py (autograd, clip_grad_norm_, RMSprop) is the host implementation." % self.device)
+        self._L = _native.load()
+        T, E, D, A, dev = self.n_steps, self.num_envs, self.obs_width, self.act_dim, self.device
+        self._layout = _native.XarmA2CLayout(E, T, D, A, _native.POLICY_HIDDEN)
+        nbytes = C.c_int64(0)
+        _native.check(self._L, None, self._L.xarm_a2c_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_a2c_workspace_bytes")
+        self.buffers = {"obs": torch.zeros(T, E, D, device=dev), "action": torch.zeros(T, E, A, device=dev), "reward": torch.zeros(T, E, device=dev),
+                        "done": torch.zeros(T, E, device=dev), "use": torch.ones(T, E, device=dev),
+                        "workspace": torch.zeros(max(int(nbytes.value), 16) // 4, dtype=torch.float32, device=dev)}
+        self.square_avg = [torch.zeros_like(p) for p in self.params()]
+        self.stats = torch.zeros(8, device=dev)
+        self.num_params = sum(p.numel() for p in self.params())
+
+    def params(self):
+        return module_params(self.model)
+
+    def _weights(self, tensors):
+        w = _native.XarmPolicyWeights()
+        for k, t in zip(_native.POLICY_WEIGHT_FIELDS, tensors):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("DeviceA2C needs contiguous float32 tensors on %s (%s)" % (self.device, k))
+            setattr(w, k, t.data_ptr())
+        return w
+
+    def store(self, k, obs, action, reward, done, resetting=None):
+        """slot k of the rollout, as train.py's loop forms it: reward (1 - resetting), max(done, resetting), use = 1 - resetting.
+        action None: the action is already in buffers["action"][k]."""
+        b = self.buffers
+        b["obs"][k].copy_(obs)
+        if action is not None:
+            b["action"][k].copy_(action)
+        if resetting is None:
+            b["reward"][k].copy_(reward)
+            b["done"][k].copy_(done)
+            b["use"][k].fill_(1.0)
+        else:
+            r = resetting.float()
+            b["reward"][k].copy_(reward * (1.0 - r))
+            b["done"][k].copy_(torch.maximum(done.float(), r))
+            b["use"][k].copy_(1.0 - r)
+
+    def _call(self, weights, square_avg, last_obs, hyper, out_returns, out_grad, out_stats):
+        E, D = self.num_envs, self.obs_width
+        assert last_obs.dtype == torch.float32 and last_obs.is_contiguous() and tuple(last_obs.shape) == (E, D) and last_obs.device == self.device, \
+            "last_obs must be a contiguous float32 [num_envs, D] tensor on the model's device"
+        b = self.buffers
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        params = _native.XarmA2CParams(*[float(hyper[k]) for k in HYPER])
+        rc = self._L.xarm_a2c_update(C.byref(self._layout), C.byref(params), C.byref(self._weights(weights)), C.byref(self._weights(square_avg)),
+                                     p(b["obs"]), p(b["action"]), p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(b["workspace"]),
+                                     p(out_returns), p(out_grad), p(out_stats), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _native.check(self._L, None, rc, "xarm_a2c_update")
+
+    def update(self, last_obs, out_returns=None, out_grad=None):
+        """one update from the stored rollout and the observation after its last step; the module's parameters and `square_avg`
+        change in place, `stats` is rewritten.  out_returns [T, E] / out_grad [num_params] (debug): filled with the returns and with
+        the gradient before the clip.  No allocation, no host read; capturable."""
+        self._call(self.params(), self.square_avg, last_obs, self.hyper, out_returns, out_grad, self.stats)
+        return self.stats
+
+    def grad(self, last_obs):
+        """(flat gradient before the clip [num_params], returns [T, E], stats [8]) of the stored rollout, computed by the same call on
+        a scratch copy of the weights and of square_avg with lr = 0: the module is not touched (debug; allocates)"""
+        w, sq = [p.detach().clone() for p in self.params()], [s.clone() for s in self.square_avg]
+        g, r, st = torch.empty(self.num_params, device=self.device), torch.empty(self.n_steps, self.num_envs, device=self.device), torch.zeros(8, device=self.device)
+        self._call(w, sq, last_obs, dict(self.hyper, lr=0.0), r, g, st)
+        return g, r, st
+
+    def load_optimizer(self, opt):
+        """continue from a torch.optim.RMSprop built on the same module"""
+        load_square_avg(self.square_avg, opt, self.params())
+
+    def export_optimizer(self, opt):
+        """let a torch.optim.RMSprop built on the same module continue from this updater's state"""
+        export_square_avg(self.square_avg, opt, self.params())

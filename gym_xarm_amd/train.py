@@ -246,7 +246,8 @@ class ActorCritic(nn.Module):
 
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.99, lr=7e-4, seed=0, config=None, log_every=50,
-          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False):
+          quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
+          device_update=False):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -255,7 +256,10 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
     torch classes of this file.
     device_policy: the rollout's sample and clamp in one HIP launch (gym_xarm_amd/device_policy.py DevicePolicy) instead of
     `model.dist(obs).sample().clamp(-1, 1)`; the update is unchanged and recomputes log-probabilities and values with autograd
-    from the stored actions."""
+    from the stored actions.
+    device_update: the update itself - bootstrap value, returns, backward, clip_grad_norm_ and RMSprop - in HIP kernels on the
+    model's own parameters (gym_xarm_amd/device_a2c.py DeviceA2C) instead of the autograd block below; the rollout is stored in its
+    buffers and no torch optimiser is created."""
     torch.manual_seed(seed)
     if env is None:
         import gym_xarm_amd
@@ -271,7 +275,12 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
         monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     model = ActorCritic(venv.dim, env.act_dim).to(dev)
-    opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
+    if device_update:
+        from .device_a2c import DeviceA2C
+        a2c = DeviceA2C(model, num_envs, n_steps=n_steps, gamma=gamma, lr=lr, alpha=0.99, eps=1e-5)
+        env_action = torch.empty(num_envs, env.act_dim, device=dev)
+    else:
+        opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
     if device_policy:
         from .device_policy import DevicePolicy
         policy = DevicePolicy(model, seed=seed, row_offset=int(getattr(env, "_env_id_offset", 0)))
@@ -280,8 +289,12 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
     succ_sum, done_sum, raw_sum = torch.zeros((), device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)
     for it in range(1, updates + 1):
         obs_buf, act_buf, rew_buf, done_buf, use_buf = [], [], [], [], []
-        for _ in range(n_steps):
-            if device_policy:
+        for k in range(n_steps):
+            if device_policy and device_update:
+                # the sample lands in its slot of the rollout; env.step has read env_action when the next act_into rewrites it
+                out = policy.act_into({"action": a2c.buffers["action"][k], "env_action": env_action}, obs)
+                a, a_env = None, out["env_action"]
+            elif device_policy:
                 # fresh tensors every step: the buffers below keep `a`, and the update reads it
                 out = policy.act_into({"action": torch.empty(num_envs, env.act_dim, device=dev),
                                        "env_action": torch.empty(num_envs, env.act_dim, device=dev)}, obs)
@@ -295,30 +308,36 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
             if not device_normalize:
                 monitor.update(raw, done, ~info["resetting"] if "resetting" in info else None)
             if callback is not None:
-                callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (len(obs_buf) + 1) * num_envs)
-            obs_buf.append(obs); act_buf.append(a); rew_buf.append(nrew * (1.0 - resetting))
-            done_buf.append(torch.maximum(done.float(), resetting)); use_buf.append(1.0 - resetting)
+                callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (k + 1) * num_envs)
+            if device_update:
+                a2c.store(k, obs, a, nrew, done, info["resetting"] if "resetting" in info else None)
+            else:
+                obs_buf.append(obs); act_buf.append(a); rew_buf.append(nrew * (1.0 - resetting))
+                done_buf.append(torch.maximum(done.float(), resetting)); use_buf.append(1.0 - resetting)
             succ_sum += (info["is_success"].float() * done.float()).sum()
             done_sum += done.float().sum()
             raw_sum += raw.mean()
             obs = nobs
-        with torch.no_grad():
-            ret = model.value(obs)
-            rets = []
-            for k in reversed(range(n_steps)):
-                ret = rew_buf[k] + gamma * ret * (1.0 - done_buf[k])
-                rets.append(ret)
-            rets = torch.stack(rets[::-1])
-        O, A, U = torch.stack(obs_buf), torch.stack(act_buf), torch.stack(use_buf)
-        values = model.value(O)
-        adv = rets - values.detach()
-        logp = model.dist(O).log_prob(A).sum(-1)
-        n_use = U.sum().clamp(min=1.0)
-        loss = -(adv * logp * U).sum() / n_use + 0.5 * (((rets - values) ** 2) * U).sum() / n_use
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        nn.utils.clip_grad_norm_(model.parameters(), 0.5)
-        opt.step()
+        if device_update:
+            a2c.update(obs)
+        else:
+            with torch.no_grad():
+                ret = model.value(obs)
+                rets = []
+                for k in reversed(range(n_steps)):
+                    ret = rew_buf[k] + gamma * ret * (1.0 - done_buf[k])
+                    rets.append(ret)
+                rets = torch.stack(rets[::-1])
+            O, A, U = torch.stack(obs_buf), torch.stack(act_buf), torch.stack(use_buf)
+            values = model.value(O)
+            adv = rets - values.detach()
+            logp = model.dist(O).log_prob(A).sum(-1)
+            n_use = U.sum().clamp(min=1.0)
+            loss = -(adv * logp * U).sum() / n_use + 0.5 * (((rets - values) ** 2) * U).sum() / n_use
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+            opt.step()
         if it % log_every == 0 or it == updates:
             if dev.type == "cuda":
                 torch.cuda.synchronize()
@@ -351,13 +370,14 @@ def main():
     ap.add_argument("--check-freq", type=int, default=1000)
     ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
     ap.add_argument("--device-policy", action="store_true", help="the rollout's sample + clamp in one HIP launch (gym_xarm_amd/device_policy.py)")
+    ap.add_argument("--device-update", action="store_true", help="returns, backward, clip and RMSprop in HIP kernels (gym_xarm_amd/device_a2c.py)")
     args = ap.parse_args()
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
-                              device_policy=args.device_policy)
+                              device_policy=args.device_policy, device_update=args.device_update)
     if args.save:
         save_model(args.save, model, venv)
 

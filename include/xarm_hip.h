@@ -452,6 +452,54 @@ int xarm_policy_act(const xarm_policy_layout *layout, const xarm_policy_params *
                     const float *desired_goal, float *out_action, float *out_env_action, float *out_logp /* may be NULL */,
                     float *out_value /* may be NULL */, void *stream);
 
+/* ---- device-resident A2C update (gym_xarm_amd/csrc/xarm_a2c_core.h, xarm_k_a2c.hip): one update of
+ * gym_xarm_amd/train.py's loop - bootstrap value, n-step returns, the backward of both towers, torch's clip_grad_norm_ and
+ * torch's RMSprop (no momentum, not centred, no weight decay) - as six stream-ordered launches on `stream`, with no allocation,
+ * no host read and no side stream.  Everything is caller-owned float32 DEVICE memory, row-major; T = n_steps, E = num_envs,
+ * D = obs_dim, A = act_dim.
+ *   obs [T, E, D] (already normalised, flat), action [T, E, A], reward [T, E], done [T, E] (non-zero cuts the return),
+ *   use [T, E] (may be NULL = all ones), last_obs [E, D]
+ *   ret_T = value(last_obs); ret_k = fmaf(gamma (1 - done_k), ret_k+1, reward_k) in float32; adv = ret - value(obs) (no gradient
+ *   through ret or adv); n_use = max(sum use, 1);
+ *   loss = -sum(adv logp use) / n_use + vf_coef sum((ret - value)^2 use) / n_use - ent_coef sum_c(log_std_c + 1/2 + log(2 pi) / 2)
+ *   norm = sqrt(sum g^2) over the 13 tensors, g *= min(1, max_grad_norm / (norm + 1e-6));
+ *   sq = alpha sq + (1 - alpha) g^2; p -= lr g / (sqrt(sq) + eps)
+ *   weights     the policy's 13 tensors (xarm_policy_weights; the same alignment rule), READ AND WRITTEN in place
+ *   square_avg  RMSprop's 13 state tensors in the same shapes, read and written in place
+ *   workspace   xarm_a2c_workspace_bytes() bytes, 16-byte aligned; holds nothing between calls
+ *   out_returns [T, E], out_grad [P] (the gradient before the clip, after the 1 / n_use factor, the 13 tensors one after the other
+ *               in the struct's order), out_stats [8] = policy_loss, value_loss, entropy, grad_norm, n_use, 0, 0, 0: each may be NULL
+ * Sums over rows run in a fixed order through per-workgroup partials (no floating-point atomics): the same inputs give the same
+ * bits.  num_envs == 0 launches nothing. */
+typedef struct xarm_a2c_layout {
+    int32_t num_envs;
+    int32_t n_steps;            /* >= 1; n_steps * num_envs < 2^31 */
+    int32_t obs_dim;            /* D, 1 .. XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_POLICY_MAX_ACT */
+    int32_t hidden;             /* XARM_POLICY_HIDDEN */
+} xarm_a2c_layout;              /* 20 bytes */
+typedef struct xarm_a2c_params {
+    double gamma;               /* [0, 1] */
+    double lr;                  /* >= 0 */
+    double alpha;               /* [0, 1) */
+    double eps;                 /* > 0 */
+    double vf_coef;
+    double ent_coef;
+    double max_grad_norm;       /* > 0 */
+} xarm_a2c_params;              /* 56 bytes */
+/* *bytes = size of `workspace` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_a2c_workspace_bytes(const xarm_a2c_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: NULL layout / params / weights / square_avg, num_envs < 0, n_steps < 1, n_steps * num_envs >= 2^31, obs_dim outside
+ * [1, XARM_POLICY_MAX_DIM], act_dim outside [1, XARM_POLICY_MAX_ACT], hidden != XARM_POLICY_HIDDEN, gamma outside [0, 1], lr < 0,
+ * alpha outside [0, 1), eps <= 0, max_grad_norm <= 0, a vf_coef or ent_coef that is not finite, or with num_envs > 0 a NULL weight or
+ * square_avg tensor, a misaligned b1 / W2 / b2 / W3 of `weights`, a NULL obs / action / reward / done / last_obs, a NULL or not
+ * 16-byte aligned workspace. */
+int xarm_a2c_update(const xarm_a2c_layout *layout, const xarm_a2c_params *params, const xarm_policy_weights *weights,
+                    const xarm_policy_weights *square_avg, const float *obs, const float *action, const float *reward,
+                    const float *done, const float *use /* may be NULL */, const float *last_obs, void *workspace,
+                    float *out_returns /* may be NULL */, float *out_grad /* may be NULL */, float *out_stats /* may be NULL */,
+                    void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 

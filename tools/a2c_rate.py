@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Time the A2C update with device events: train.py's torch block - bootstrap value, return loop, the second forward under autograd,
+backward, clip_grad_norm_ and RMSprop.step - against device_a2c.py's DeviceA2C.update (six HIP launches).  Median of 3 warmed
+windows of 50 updates per leg.
+
+  python tools/a2c_rate.py [--out profiles/a2c_rate.json] [--envs 4096 65536] [--no-train]
+
+n_steps 5 at 4 096 and 65 536 envs (5 x 4 096 and 5 x 65 536 rows), Reach widths (14 columns) and PickAndPlace widths (30), act_dim 4.
+Both legs read the same stored rollout and start from the same ActorCritic; each updates its own copy.  Legs per size and width, in
+this order: torch, hip, torch again (drift).  `*_launches` is the number of kernels a leg enqueues per update, counted with the
+torch profiler after the last timed window of the run (a tracer slows the host: nothing is timed once it has been started).
+Then, unless --no-train, `env_steps_per_sec` of train() on XarmReach-v0 at 4 096 envs, 300 updates, with device_normalize,
+device_policy and device_update all on against all off: off, on, off again."""
+import argparse
+import copy
+import json
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gym_xarm_amd.device_a2c import DeviceA2C  # noqa: E402
+from gym_xarm_amd.train import ActorCritic, train  # noqa: E402
+
+CALLS = 50
+WIDTHS = {"XarmReach-v0": 14, "XarmPDPickAndPlace-v0": 30}
+ACT_DIM, N_STEPS, GAMMA = 4, 5, 0.99
+
+
+def timed(fn, iters, windows=3):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(windows):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return sorted(out)[len(out) // 2]
+
+
+def count_launches(fn):
+    """device kernels of one call; None when the profiler is not usable here"""
+    try:
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if e.device_type == DeviceType.CUDA)
+    except Exception as ex:
+        print("launch count unavailable: %r" % (ex,), file=sys.stderr)
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
+    ap.add_argument("--no-train", action="store_true")
+    args = ap.parse_args()
+    res = {"device": torch.cuda.get_device_name(0), "updates_per_window": CALLS, "n_steps": N_STEPS, "act_dim": ACT_DIM, "legs": []}
+    for env_id, D in WIDTHS.items():
+        for E in args.envs:
+            torch.manual_seed(0)
+            model_t = ActorCritic(D, ACT_DIM).cuda()
+            model_h = copy.deepcopy(model_t)
+            opt = torch.optim.RMSprop(model_t.parameters(), lr=7e-4, alpha=0.99, eps=1e-5)
+            a2c = DeviceA2C(model_h, E, n_steps=N_STEPS, gamma=GAMMA)
+            b = a2c.buffers
+            b["obs"].copy_((torch.rand(N_STEPS, E, D, device="cuda") * 2 - 1) * 3)
+            b["action"].normal_()
+            b["reward"].normal_()
+            b["done"].copy_((torch.rand(N_STEPS, E, device="cuda") < 0.04).float())
+            last = (torch.rand(E, D, device="cuda") * 2 - 1) * 3
+            obs_buf, act_buf, rew_buf, done_buf, use_buf = [[b[k][i].clone() for i in range(N_STEPS)] for k in ("obs", "action", "reward", "done", "use")]
+
+            def torch_call():
+                # gym_xarm_amd/train.py, the update block of train(), as it stands
+                with torch.no_grad():
+                    ret = model_t.value(last)
+                    rets = []
+                    for k in reversed(range(N_STEPS)):
+                        ret = rew_buf[k] + GAMMA * ret * (1.0 - done_buf[k])
+                        rets.append(ret)
+                    rets = torch.stack(rets[::-1])
+                O, A, U = torch.stack(obs_buf), torch.stack(act_buf), torch.stack(use_buf)
+                values = model_t.value(O)
+                adv = rets - values.detach()
+                logp = model_t.dist(O).log_prob(A).sum(-1)
+                n_use = U.sum().clamp(min=1.0)
+                loss = -(adv * logp * U).sum() / n_use + 0.5 * (((rets - values) ** 2) * U).sum() / n_use
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                nn.utils.clip_grad_norm_(model_t.parameters(), 0.5)
+                opt.step()
+
+            def hip_call():
+                a2c.update(last)
+
+            for _ in range(CALLS):
+                torch_call()
+                hip_call()
+            for impl, fn in (("torch_first", torch_call), ("hip", hip_call), ("torch_last", torch_call)):
+                ms = timed(fn, CALLS)
+                res["legs"].append(dict(widths=env_id, obs_width=D, num_envs=E, rows=N_STEPS * E, impl=impl, ms_per_update=ms))
+                print(json.dumps(res["legs"][-1]), flush=True)
+            keep = (torch_call, hip_call)
+    if not args.no_train:
+        res["train"] = []
+        for name, on in (("off_first", False), ("on", True), ("off_last", False)):
+            _, _, hist = train("XarmReach-v0", num_envs=4096, updates=300, config={"reward_type": "dense", "GUI": False}, log_every=300, quiet=True,
+                               device_normalize=on, device_policy=on, device_update=on)
+            res["train"].append(dict(leg=name, device_flags=on, env_steps_per_sec=hist[-1]["env_steps_per_sec"]))
+            print(json.dumps(res["train"][-1]), flush=True)
+    res["torch_launches"], res["hip_launches"] = count_launches(keep[0]), count_launches(keep[1])
+    print(json.dumps({"torch_launches": res["torch_launches"], "hip_launches": res["hip_launches"]}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(res, open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
