@@ -22,7 +22,7 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
-           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update"]
+           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -103,6 +103,20 @@ class XarmA2CParams(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("gamma", "lr", "alpha", "eps", "vf_coef", "ent_coef", "max_grad_norm")]
 
 
+PPO_HYPER = ("gamma", "gae_lambda", "clip_range", "lr", "beta1", "beta2", "eps", "vf_coef", "ent_coef", "max_grad_norm")
+PPO_MAX_STEPS = 4096        # optimiser steps per xarm_ppo_update call
+
+
+class XarmPPOLayout(C.Structure):
+    """include/xarm_hip.h xarm_ppo_layout (28 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("num_envs", "n_steps", "obs_dim", "act_dim", "hidden", "n_epochs", "batch_size")]
+
+
+class XarmPPOParams(C.Structure):
+    """include/xarm_hip.h xarm_ppo_params (88 bytes)"""
+    _fields_ = [(k, C.c_double) for k in PPO_HYPER] + [("normalize_advantage", C.c_int32)]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -160,6 +174,9 @@ def load(path=None):
     al = C.POINTER(XarmA2CLayout)
     L.xarm_a2c_workspace_bytes.argtypes = [al, C.POINTER(C.c_int64)]
     L.xarm_a2c_update.argtypes = [al, C.POINTER(XarmA2CParams), C.POINTER(XarmPolicyWeights), C.POINTER(XarmPolicyWeights)] + [vp] * 11
+    pl = C.POINTER(XarmPPOLayout)
+    L.xarm_ppo_workspace_bytes.argtypes = [pl, C.POINTER(C.c_int64)]
+    L.xarm_ppo_update.argtypes = [pl, C.POINTER(XarmPPOParams)] + [C.POINTER(XarmPolicyWeights)] * 3 + [vp] * 15
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

@@ -138,21 +138,23 @@ XARM_HD float return_step(float gamma, float done, float reward, float next) {
     return fma32(gamma * keep, next, reward);
 }
 
-// the policy head of one row: dmean[c * ds] for c < A, the row's log_std terms added to dls, returns logp
-XARM_HD float pi_deltas(int A, const float *mean, const float *action, const float *log_std, float adv, float use, float *dmean, int ds,
-                        float (&dls)[MAX_ACT]) {
-    const float q = -(adv * use);
+// the policy head of one row with dlogp's factor q given: mean_c at mean[c * ms]; DELTAS: dmean[c * ds] = q d_c iv_c for c < A (mean and dmean
+// may be the same memory) and the row's log_std terms added to dls; returns logp
+template <bool DELTAS> XARM_HD float pi_row(int A, const float *mean, int ms, const float *action, const float *log_std, float q, float *dmean, int ds,
+                                            float (&dls)[MAX_ACT]) {
     float lp = 0.0f;
 #pragma unroll
     for (int c = 0; c < MAX_ACT; c++) {
         if (c < A) {
             const float ls = log_std[c];
             const float iv = xpol::exp_f(-2.0f * ls);
-            const float d = action[c] - mean[c];
+            const float d = action[c] - mean[c * ms];
             const float dv = d * iv;
-            dmean[c * ds] = q * dv;
-            const float t = fma32(d, dv, -1.0f);
-            dls[c] = fma32(q, t, dls[c]);
+            if (DELTAS) {
+                dmean[c * ds] = q * dv;
+                const float t = fma32(d, dv, -1.0f);
+                dls[c] = fma32(q, t, dls[c]);
+            }
             float l = -0.5f * d;
             l = l * dv;
             l = l - ls;
@@ -161,6 +163,12 @@ XARM_HD float pi_deltas(int A, const float *mean, const float *action, const flo
         }
     }
     return lp;
+}
+
+// A2C's head: q = -(adv use)
+XARM_HD float pi_deltas(int A, const float *mean, const float *action, const float *log_std, float adv, float use, float *dmean, int ds,
+                        float (&dls)[MAX_ACT]) {
+    return pi_row<true>(A, mean, 1, action, log_std, -(adv * use), dmean, ds, dls);
 }
 
 XARM_HD float value_delta(float vf2, float value, float ret, float use) { return vf2 * ((value - ret) * use); }
@@ -179,6 +187,36 @@ XARM_HD void rmsprop(const Hyper &h, float g, float &sq, float &p) {
 }
 
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
+// one row's backward through one tower (tensors t0 .. t0 + 5 of the flat order), added to the float32 chunk sums
+inline void host_backward(const Shape &s, float *chunk, const Tower &T, int t0, const float *x, const float *h1, const float *h2, const float *d3, int nout) {
+    const int D = s.D;
+    float *gW1 = chunk + s.off[t0], *gb1 = chunk + s.off[t0 + 1], *gW2 = chunk + s.off[t0 + 2], *gb2 = chunk + s.off[t0 + 3],
+          *gW3 = chunk + s.off[t0 + 4], *gb3 = chunk + s.off[t0 + 5];
+    float d2[HID], d1[HID];
+    for (int c = 0; c < nout; c++) {
+        for (int j = 0; j < HID; j++) gW3[c * HID + j] = fma32(d3[c], h2[j], gW3[c * HID + j]);
+        gb3[c] += d3[c];
+    }
+    for (int j = 0; j < HID; j++) {
+        float pre = 0.0f;
+        for (int c = 0; c < nout; c++) pre = fma32(T.W3[c * HID + j], d3[c], pre);
+        d2[j] = pre * fma32(-h2[j], h2[j], 1.0f);
+    }
+    for (int i = 0; i < HID; i++) {
+        for (int j = 0; j < HID; j++) gW2[i * HID + j] = fma32(d2[i], h1[j], gW2[i * HID + j]);
+        gb2[i] += d2[i];
+    }
+    for (int j = 0; j < HID; j++) {
+        float pre = 0.0f;
+        for (int k = 0; k < HID; k++) pre = fma32(T.W2[k * HID + j], d2[k], pre);
+        d1[j] = pre * fma32(-h1[j], h1[j], 1.0f);
+    }
+    for (int i = 0; i < HID; i++) {
+        for (int j = 0; j < D; j++) gW1[i * D + j] = fma32(d1[i], x[j], gW1[i * D + j]);
+        gb1[i] += d1[i];
+    }
+}
+
 // ---- the whole update as plain loops (the host build).  w / sq: the 13 tensors.
 inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *const *sq, const float *obs, const float *action, const float *reward,
                         const float *done, const float *use, const float *last_obs, float *out_returns, float *out_grad, float *out_stats) {
@@ -205,31 +243,7 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         for (int64_t p = 0; p < s.P; p++) { G[(size_t)p] += (double)chunk[(size_t)p]; chunk[(size_t)p] = 0.0f; }
     };
     auto backward = [&](const Tower &T, int t0, const float *x, const float *h1, const float *h2, const float *d3, int nout) {
-        float *gW1 = &chunk[(size_t)s.off[t0]], *gb1 = &chunk[(size_t)s.off[t0 + 1]], *gW2 = &chunk[(size_t)s.off[t0 + 2]], *gb2 = &chunk[(size_t)s.off[t0 + 3]],
-              *gW3 = &chunk[(size_t)s.off[t0 + 4]], *gb3 = &chunk[(size_t)s.off[t0 + 5]];
-        float d2[HID], d1[HID];
-        for (int c = 0; c < nout; c++) {
-            for (int j = 0; j < HID; j++) gW3[c * HID + j] = fma32(d3[c], h2[j], gW3[c * HID + j]);
-            gb3[c] += d3[c];
-        }
-        for (int j = 0; j < HID; j++) {
-            float pre = 0.0f;
-            for (int c = 0; c < nout; c++) pre = fma32(T.W3[c * HID + j], d3[c], pre);
-            d2[j] = pre * fma32(-h2[j], h2[j], 1.0f);
-        }
-        for (int i = 0; i < HID; i++) {
-            for (int j = 0; j < HID; j++) gW2[i * HID + j] = fma32(d2[i], h1[j], gW2[i * HID + j]);
-            gb2[i] += d2[i];
-        }
-        for (int j = 0; j < HID; j++) {
-            float pre = 0.0f;
-            for (int k = 0; k < HID; k++) pre = fma32(T.W2[k * HID + j], d2[k], pre);
-            d1[j] = pre * fma32(-h1[j], h1[j], 1.0f);
-        }
-        for (int i = 0; i < HID; i++) {
-            for (int j = 0; j < D; j++) gW1[i * D + j] = fma32(d1[i], x[j], gW1[i * D + j]);
-            gb1[i] += d1[i];
-        }
+        host_backward(s, chunk.data(), T, t0, x, h1, h2, d3, nout);
     };
     for (int64_t n = 0; n < s.N; n++) {
         const float *x = obs + n * D;

@@ -1,0 +1,198 @@
+// xarm_grad_tile.h - one 64-row tile of the two-tower backward, shared by the gradient kernels of the A2C update (xarm_k_a2c.hip,
+// DESIGN.md 21) and of the PPO update (xarm_k_ppo.hip).  Device code only; both units are built with -ffp-contract=off.
+//
+// A workgroup of 256 threads works on ONE tower.  Per tile, in LDS and transposed ([unit][row], stride 65: a lane per row and a lane
+// per unit both read without bank conflicts): the rows, h1 and h2 from the policy's chains (lane = row, wavefront w = units
+// 16 w .. 16 w + 15, so the weights are wavefront-uniform loads), the output deltas, then d2 and d1 in place over h2 and h1 once the
+// outer products that need h2 / h1 are taken.  The gradient lives in registers across the tiles (TileGrad): thread
+// (ib, jb) = (t & 15, t >> 4) owns the entries (ib + 16 a, jb + 16 b) of dW2 and dW1, thread (t & 63, t >> 6) the entries of dW3.
+//
+// What differs between the algorithms is the Head:
+//   int64_t row(int rr)               the batch row in tile slot rr, or -1 for an empty slot (its row enters as zeros)
+//   void deltas(int r, float *D3)     called by lane r of wavefront 0: writes the output deltas of slot r to D3[c * LS], c < nout (they are
+//                                     zero when it is called; an empty slot leaves them so)
+//   FROM_H2                           false: the deltas need nothing of this tile's forward and are written with its load.
+//                                     true: the tower's outputs W3 h2 + b3 (the policy's chain, order KORD) are put to D3[c * LS] first and
+//                                     deltas() replaces them - a head that needs mean / value under the CURRENT weights.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "xarm_a2c_core.h"
+
+namespace xa2c {
+
+constexpr int THREADS = 256, LS = ROWS + 1, UPW = 16;     // LDS row stride; units per wavefront in the lane = row stages
+static_assert(ROWS == 64 && THREADS == 4 * ROWS && UPW * (THREADS / 64) == HID, "four wavefronts: 64 rows x 16 units each");
+
+struct TileLds {
+    float *Xt, *H1t, *H2t, *D3t;       // [16 JW][LS], [HID][LS], [HID][LS], [MAX_ACT][LS]
+};
+
+// JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
+template <int JW> struct TileGrad {
+    float g1[4][JW], gb1[4], g2[4][4], gb2[4], g3[4], gb3[4];
+
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            gb1[a] = gb2[a] = g3[a] = gb3[a] = 0.0f;
+#pragma unroll
+            for (int b = 0; b < 4; b++) g2[a][b] = 0.0f;
+#pragma unroll
+            for (int m = 0; m < JW; m++) g1[a][m] = 0.0f;
+        }
+    }
+
+    // the workgroup's slice: one tower's tensors in the flat order
+    __device__ __forceinline__ void store(float *slice, int D, int nout) const {
+        const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), ib = t & 15, jb = t >> 4;
+        float *sW1 = slice, *sb1 = sW1 + HID * D, *sW2 = sb1 + HID, *sb2 = sW2 + HID * HID, *sW3 = sb2 + HID, *sb3 = sW3 + nout * HID;
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const int i = ib + 16 * a;
+#pragma unroll
+            for (int m = 0; m < JW; m++)
+                if (jb + 16 * m < D) sW1[i * D + jb + 16 * m] = g1[a][m];
+#pragma unroll
+            for (int b = 0; b < 4; b++) sW2[i * HID + jb + 16 * b] = g2[a][b];
+            if (jb == 0) { sb1[i] = gb1[a]; sb2[i] = gb2[a]; }
+            const int c = 4 * wv + a;
+            if (c < nout) {
+                sW3[c * HID + r] = g3[a];
+                if (r == 0) sb3[c] = gb3[a];
+            }
+        }
+    }
+};
+
+// one tile; ends on a barrier, so the caller may rewrite what row() reads and call it again
+template <int JW, class Head>
+__device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const float *obs, const TileLds &L, Head &head, TileGrad<JW> &G) {
+    float *const Xt = L.Xt, *const H1t = L.H1t, *const H2t = L.H2t, *const D3t = L.D3t;
+    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), u0 = UPW * wv, ib = t & 15, jb = t >> 4;
+
+    // the tile's rows (zeros in empty slots and past column D) and the deltas at the outputs (wavefront 0: lane = row)
+    for (int idx = t; idx < 16 * JW * ROWS; idx += THREADS) {
+        const int rr = idx / (16 * JW), j = idx - rr * (16 * JW);
+        const int64_t n = head.row(rr);
+        Xt[j * LS + rr] = (n >= 0 && j < D) ? obs[n * D + j] : 0.0f;
+    }
+    if (wv == 0) {
+#pragma unroll
+        for (int c = 0; c < MAX_ACT; c++) D3t[c * LS + r] = 0.0f;
+        if constexpr (!Head::FROM_H2) head.deltas(r, D3t + r);
+    }
+    __syncthreads();
+
+    {   // h1
+        float acc[UPW];
+#pragma unroll
+        for (int u = 0; u < UPW; u++) acc[u] = T.b1[u0 + u];
+        xpol::layer1_chains<UPW>(T.W1 + u0 * D, D, Xt + r, LS, acc);
+#pragma unroll
+        for (int u = 0; u < UPW; u++) H1t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
+    }
+    __syncthreads();
+    {   // h2
+        float acc[UPW];
+#pragma unroll
+        for (int u = 0; u < UPW; u++) acc[u] = T.b2[u0 + u];
+        xpol::hidden_chains<UPW>(T.W2 + u0 * HID, H1t + r, LS, acc);
+#pragma unroll
+        for (int u = 0; u < UPW; u++) H2t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
+    }
+    __syncthreads();
+
+    if constexpr (Head::FROM_H2) {
+        // the outputs: wavefront w takes outputs 4 w .. 4 w + 3 (rows of W3 past nout do not exist and are not read)
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const int c = 4 * wv + a;
+            if (c < nout) {
+                float acc[1] = {T.b3[c]};
+                xpol::hidden_chains<1>(T.W3 + c * HID, H2t + r, LS, acc);
+                D3t[c * LS + r] = acc[0];
+            }
+        }
+        __syncthreads();
+        if (wv == 0) head.deltas(r, D3t + r);
+        __syncthreads();
+    }
+
+    // dW3, db3: thread (unit r, outputs 4 wv .. 4 wv + 3)
+    if (4 * wv < nout) {
+        for (int rr = 0; rr < ROWS; rr++) {
+            const float hv = H2t[r * LS + rr];
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                const float dv = D3t[(4 * wv + a) * LS + rr];
+                G.g3[a] = fma32(dv, hv, G.g3[a]);
+                G.gb3[a] += dv;
+            }
+        }
+    }
+    __syncthreads();
+    {   // d2 over h2
+        float pre[UPW];
+#pragma unroll
+        for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
+        for (int c = 0; c < nout; c++) {
+            const float dv = D3t[c * LS + r];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W3[c * HID + u0 + u], dv, pre[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < UPW; u++) {
+            const float hv = H2t[(u0 + u) * LS + r];
+            H2t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
+        }
+    }
+    __syncthreads();
+
+    // dW2, db2: thread (ib, jb) owns (ib + 16 a, jb + 16 b)
+    for (int rr = 0; rr < ROWS; rr++) {
+        float dv[4], hv[4];
+#pragma unroll
+        for (int a = 0; a < 4; a++) { dv[a] = H2t[(ib + 16 * a) * LS + rr]; hv[a] = H1t[(jb + 16 * a) * LS + rr]; }
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            G.gb2[a] += dv[a];
+#pragma unroll
+            for (int b = 0; b < 4; b++) G.g2[a][b] = fma32(dv[a], hv[b], G.g2[a][b]);
+        }
+    }
+    __syncthreads();
+    {   // d1 over h1
+        float pre[UPW];
+#pragma unroll
+        for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
+        for (int k = 0; k < HID; k++) {
+            const float dv = H2t[k * LS + r];
+#pragma unroll
+            for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W2[k * HID + u0 + u], dv, pre[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < UPW; u++) {
+            const float hv = H1t[(u0 + u) * LS + r];
+            H1t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
+        }
+    }
+    __syncthreads();
+
+    // dW1, db1: thread (ib, jb) owns (ib + 16 a, jb + 16 m)
+    for (int rr = 0; rr < ROWS; rr++) {
+        float dv[4], xv[JW];
+#pragma unroll
+        for (int a = 0; a < 4; a++) dv[a] = H1t[(ib + 16 * a) * LS + rr];
+#pragma unroll
+        for (int m = 0; m < JW; m++) xv[m] = Xt[(jb + 16 * m) * LS + rr];
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            G.gb1[a] += dv[a];
+#pragma unroll
+            for (int m = 0; m < JW; m++) G.g1[a][m] = fma32(dv[a], xv[m], G.g1[a][m]);
+        }
+    }
+    __syncthreads();
+}
+
+}  // namespace xa2c

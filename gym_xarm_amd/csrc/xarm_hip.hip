@@ -35,6 +35,7 @@
 #include "xarm_norm_core.h"
 #include "xarm_policy_core.h"
 #include "xarm_a2c_core.h"
+#include "xarm_ppo_core.h"
 
 using namespace xd;
 
@@ -1026,6 +1027,52 @@ int xarm_a2c_update(const xarm_a2c_layout *layout, const xarm_a2c_params *params
     d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
     const int le = xa2c::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_a2c_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ PPO update (xarm_k_ppo.hip)
+int xarm_ppo_workspace_bytes(const xarm_ppo_layout *layout, int64_t *bytes) {
+    if (const char *why = xppo::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppo_workspace_bytes: NULL pointer");
+    xppo::Shape s;
+    xppo::Work k;
+    xppo::fill_shape(s, layout);
+    xppo::fill_work(k, s);
+    *bytes = k.total;
+    return XARM_OK;
+}
+
+int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params, const xarm_policy_weights *weights,
+                    const xarm_policy_weights *exp_avg, const xarm_policy_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *action, const float *reward, const float *done, const float *use, const float *last_obs,
+                    const float *old_logp, const int32_t *perm, void *workspace, float *out_adv, float *out_returns, float *out_grad,
+                    float *out_stats, void *stream) {
+    if (const char *why = xppo::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
+    if (const char *why = xppo::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
+    if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppo_update: weights / exp_avg / exp_avg_sq is NULL");
+    if (layout->num_envs == 0) return XARM_OK;
+    if (const char *why = xppo::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, last_obs, perm, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
+    xppo::Dev d = {};
+    xppo::Work k;
+    xppo::fill_shape(d.s, layout);
+    xppo::fill_hyper(d.h, params);
+    xppo::fill_work(k, d.s);
+    xa2c::tensors_of(weights, d.w);
+    xa2c::tensors_of(exp_avg, d.m);
+    xa2c::tensors_of(exp_avg_sq, d.v);
+    d.pi = xpol::Tower{d.w[0], d.w[1], d.w[2], d.w[3], d.w[4], d.w[5]};
+    d.vf = xpol::Tower{d.w[6], d.w[7], d.w[8], d.w[9], d.w[10], d.w[11]};
+    d.step = step_i64;
+    d.obs = obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.last_obs = last_obs; d.old_logp = old_logp; d.perm = perm;
+    char *base = (char *)workspace;
+    d.boot = (float *)(base + k.boot); d.mean = (float *)(base + k.mean); d.env = (float *)(base + k.env); d.value = (float *)(base + k.value);
+    d.adv = (float *)(base + k.adv); d.ret = (float *)(base + k.ret); d.oldlp = (float *)(base + k.oldlp); d.musig = (double *)(base + k.musig);
+    d.partial = (float *)(base + k.partial); d.scal = (double *)(base + k.scal); d.grad = (float *)(base + k.grad);
+    d.normpart = (double *)(base + k.normpart); d.adam = (float *)(base + k.adam);
+    d.out_adv = out_adv; d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
+    const int le = xppo::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_ppo_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

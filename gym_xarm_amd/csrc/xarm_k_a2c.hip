@@ -5,7 +5,8 @@
 //   k_policy_act    (xarm_k_policy.hip, deterministic) on last_obs: the bootstrap value
 //   k_policy_act    on the T E rows of obs: mean and value of every row - the policy kernel's own bits
 //   k_a2c_returns   one thread per env: the return recursion from the bootstrap value down
-//   k_a2c_grad      grid (groups, 2 towers), 256 threads.  A workgroup walks the 64-row tiles g, g + groups, ... of ONE tower.  Per
+//   k_a2c_grad      grid (groups, 2 towers), 256 threads.  A workgroup walks the 64-row tiles g, g + groups, ... of ONE tower.  The tile
+//                   body is xa2c::grad_tile (xarm_grad_tile.h, shared with the PPO update); A2CHead below supplies rows and deltas.  Per
 //                   tile, in LDS and transposed ([unit][row], stride 65: a lane per row and a lane per unit both read without bank
 //                   conflicts): the rows, h1 and h2 from the policy's chains (lane = row, wavefront w = units 16 w .. 16 w + 15, so
 //                   the weights are wavefront-uniform loads), the output deltas, then d2 and d1 in place over h2 and h1 once the
@@ -18,12 +19,9 @@
 //   k_a2c_apply     one thread per parameter: norm from normpart in block order, the clip, RMSprop
 // No atomics anywhere: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
-#include "xarm_a2c_core.h"
+#include "xarm_grad_tile.h"
 
 namespace xa2c {
-
-constexpr int THREADS = 256, LS = ROWS + 1, UPW = 16;     // LDS row stride; units per wavefront in the lane = row stages
-static_assert(ROWS == 64 && THREADS == 4 * ROWS && UPW * (THREADS / 64) == HID, "four wavefronts: 64 rows x 16 units each");
 
 __global__ __launch_bounds__(256) void k_a2c_returns(Dev d) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -37,172 +35,57 @@ __global__ __launch_bounds__(256) void k_a2c_returns(Dev d) {
     }
 }
 
+// A2C's head: the deltas come from the call-start mean / value / returns, so they are written with the tile's load
+struct A2CHead {
+    static constexpr bool FROM_H2 = false;
+    const Dev &d;
+    bool is_pi;
+    int64_t r0;
+    float (&dls)[MAX_ACT];
+    double &ploss, &vloss, &nuse;
+    __device__ __forceinline__ int64_t row(int rr) const { const int64_t n = r0 + rr; return n < d.s.N ? n : -1; }
+    __device__ __forceinline__ void deltas(int r, float *D3) {
+        const int64_t n = r0 + r;
+        if (n < d.s.N) {
+            const float u = d.use != nullptr ? d.use[n] : 1.0f, v = d.value[n], rt = d.ret[n];
+            if (is_pi) {
+                const float adv = rt - v;
+                const float lp = pi_deltas(d.s.A, d.mean + n * d.s.A, d.action + n * d.s.A, d.w[12], adv, u, D3, LS, dls);
+                ploss += (double)(adv * lp * u);
+                vloss += (double)((rt - v) * (rt - v) * u);
+                nuse += (double)u;
+            } else {
+                D3[0] = value_delta(d.h.vf2, v, rt, u);
+            }
+        }
+    }
+};
+
 // JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
 template <int JW> __global__ __launch_bounds__(THREADS) void k_a2c_grad(Dev d) {
     __shared__ __attribute__((aligned(16))) float Xt[16 * JW * LS];
     __shared__ __attribute__((aligned(16))) float H1t[HID * LS];
     __shared__ __attribute__((aligned(16))) float H2t[HID * LS];
     __shared__ __attribute__((aligned(16))) float D3t[MAX_ACT * LS];
-    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), u0 = UPW * wv, ib = t & 15, jb = t >> 4;
+    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const bool is_pi = blockIdx.y == 0;
     const Tower T = is_pi ? d.pi : d.vf;
     const int D = d.s.D, A = d.s.A, G = d.s.G, g = blockIdx.x, nout = is_pi ? A : 1;
-    const int64_t N = d.s.N;
 
-    float g1[4][JW], gb1[4], g2[4][4], gb2[4], g3[4], gb3[4], dls[MAX_ACT];
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        gb1[a] = gb2[a] = g3[a] = gb3[a] = 0.0f;
-#pragma unroll
-        for (int b = 0; b < 4; b++) g2[a][b] = 0.0f;
-#pragma unroll
-        for (int m = 0; m < JW; m++) g1[a][m] = 0.0f;
-    }
+    TileGrad<JW> acc;
+    acc.zero();
+    float dls[MAX_ACT];
 #pragma unroll
     for (int c = 0; c < MAX_ACT; c++) dls[c] = 0.0f;
     double ploss = 0.0, vloss = 0.0, nuse = 0.0;
+    A2CHead head = {d, is_pi, 0, dls, ploss, vloss, nuse};
+    const TileLds L = {Xt, H1t, H2t, D3t};
 
     for (int64_t tile = g; tile < d.s.tiles; tile += G) {
-        const int64_t r0 = tile * ROWS;
-        // the tile's rows (zeros past the batch and past column D) and the deltas at the outputs (wavefront 0: lane = row)
-        for (int idx = t; idx < 16 * JW * ROWS; idx += THREADS) {
-            const int rr = idx / (16 * JW), j = idx - rr * (16 * JW);
-            const int64_t n = r0 + rr;
-            Xt[j * LS + rr] = (n < N && j < D) ? d.obs[n * D + j] : 0.0f;
-        }
-        if (wv == 0) {
-            const int64_t n = r0 + r;
-#pragma unroll
-            for (int c = 0; c < MAX_ACT; c++) D3t[c * LS + r] = 0.0f;
-            if (n < N) {
-                const float u = d.use != nullptr ? d.use[n] : 1.0f, v = d.value[n], rt = d.ret[n];
-                if (is_pi) {
-                    const float adv = rt - v;
-                    const float lp = pi_deltas(A, d.mean + n * A, d.action + n * A, d.w[12], adv, u, D3t + r, LS, dls);
-                    ploss += (double)(adv * lp * u);
-                    vloss += (double)((rt - v) * (rt - v) * u);
-                    nuse += (double)u;
-                } else {
-                    D3t[r] = value_delta(d.h.vf2, v, rt, u);
-                }
-            }
-        }
-        __syncthreads();
-
-        {   // h1
-            float acc[UPW];
-#pragma unroll
-            for (int u = 0; u < UPW; u++) acc[u] = T.b1[u0 + u];
-            xpol::layer1_chains<UPW>(T.W1 + u0 * D, D, Xt + r, LS, acc);
-#pragma unroll
-            for (int u = 0; u < UPW; u++) H1t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
-        }
-        __syncthreads();
-        {   // h2
-            float acc[UPW];
-#pragma unroll
-            for (int u = 0; u < UPW; u++) acc[u] = T.b2[u0 + u];
-            xpol::hidden_chains<UPW>(T.W2 + u0 * HID, H1t + r, LS, acc);
-#pragma unroll
-            for (int u = 0; u < UPW; u++) H2t[(u0 + u) * LS + r] = xpol::tanh_f(acc[u]);
-        }
-        __syncthreads();
-
-        // dW3, db3: thread (unit r, outputs 4 wv .. 4 wv + 3)
-        if (4 * wv < nout) {
-            for (int rr = 0; rr < ROWS; rr++) {
-                const float hv = H2t[r * LS + rr];
-#pragma unroll
-                for (int a = 0; a < 4; a++) {
-                    const float dv = D3t[(4 * wv + a) * LS + rr];
-                    g3[a] = fma32(dv, hv, g3[a]);
-                    gb3[a] += dv;
-                }
-            }
-        }
-        __syncthreads();
-        {   // d2 over h2
-            float pre[UPW];
-#pragma unroll
-            for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
-            for (int c = 0; c < nout; c++) {
-                const float dv = D3t[c * LS + r];
-#pragma unroll
-                for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W3[c * HID + u0 + u], dv, pre[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < UPW; u++) {
-                const float hv = H2t[(u0 + u) * LS + r];
-                H2t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
-            }
-        }
-        __syncthreads();
-
-        // dW2, db2: thread (ib, jb) owns (ib + 16 a, jb + 16 b)
-        for (int rr = 0; rr < ROWS; rr++) {
-            float dv[4], hv[4];
-#pragma unroll
-            for (int a = 0; a < 4; a++) { dv[a] = H2t[(ib + 16 * a) * LS + rr]; hv[a] = H1t[(jb + 16 * a) * LS + rr]; }
-#pragma unroll
-            for (int a = 0; a < 4; a++) {
-                gb2[a] += dv[a];
-#pragma unroll
-                for (int b = 0; b < 4; b++) g2[a][b] = fma32(dv[a], hv[b], g2[a][b]);
-            }
-        }
-        __syncthreads();
-        {   // d1 over h1
-            float pre[UPW];
-#pragma unroll
-            for (int u = 0; u < UPW; u++) pre[u] = 0.0f;
-            for (int k = 0; k < HID; k++) {
-                const float dv = H2t[k * LS + r];
-#pragma unroll
-                for (int u = 0; u < UPW; u++) pre[u] = fma32(T.W2[k * HID + u0 + u], dv, pre[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < UPW; u++) {
-                const float hv = H1t[(u0 + u) * LS + r];
-                H1t[(u0 + u) * LS + r] = pre[u] * fma32(-hv, hv, 1.0f);
-            }
-        }
-        __syncthreads();
-
-        // dW1, db1: thread (ib, jb) owns (ib + 16 a, jb + 16 m)
-        for (int rr = 0; rr < ROWS; rr++) {
-            float dv[4], xv[JW];
-#pragma unroll
-            for (int a = 0; a < 4; a++) dv[a] = H1t[(ib + 16 * a) * LS + rr];
-#pragma unroll
-            for (int m = 0; m < JW; m++) xv[m] = Xt[(jb + 16 * m) * LS + rr];
-#pragma unroll
-            for (int a = 0; a < 4; a++) {
-                gb1[a] += dv[a];
-#pragma unroll
-                for (int m = 0; m < JW; m++) g1[a][m] = fma32(dv[a], xv[m], g1[a][m]);
-            }
-        }
-        __syncthreads();
+        head.r0 = tile * ROWS;
+        grad_tile<JW>(T, D, nout, d.obs, L, head, acc);
     }
-
-    // the workgroup's slice: one tower's tensors in the flat order
-    float *sW1 = d.partial + ((int64_t)blockIdx.y * G + g) * d.s.pstride, *sb1 = sW1 + HID * D, *sW2 = sb1 + HID, *sb2 = sW2 + HID * HID,
-          *sW3 = sb2 + HID, *sb3 = sW3 + nout * HID;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const int i = ib + 16 * a;
-#pragma unroll
-        for (int m = 0; m < JW; m++)
-            if (jb + 16 * m < D) sW1[i * D + jb + 16 * m] = g1[a][m];
-#pragma unroll
-        for (int b = 0; b < 4; b++) sW2[i * HID + jb + 16 * b] = g2[a][b];
-        if (jb == 0) { sb1[i] = gb1[a]; sb2[i] = gb2[a]; }
-        const int c = 4 * wv + a;
-        if (c < nout) {
-            sW3[c * HID + r] = g3[a];
-            if (r == 0) sb3[c] = gb3[a];
-        }
-    }
+    acc.store(d.partial + ((int64_t)blockIdx.y * G + g) * d.s.pstride, D, nout);
 
     if (is_pi) {    // the scalars: lanes of wavefront 0 added in lane order (the loop above ended on a barrier)
         double *sc = (double *)H1t;

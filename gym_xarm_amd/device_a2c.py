@@ -50,6 +50,41 @@ def export_square_avg(square_avg, opt, params):
                 st["square_avg"] = s.detach().clone()
 
 
+def rollout_buffers(T, E, D, A, dev, workspace_bytes):
+    """the rollout storage of the device updates (DeviceA2C, DevicePPO): obs [T, E, D], action [T, E, A], reward / done / use [T, E]
+    and the call's workspace"""
+    return {"obs": torch.zeros(T, E, D, device=dev), "action": torch.zeros(T, E, A, device=dev), "reward": torch.zeros(T, E, device=dev),
+            "done": torch.zeros(T, E, device=dev), "use": torch.ones(T, E, device=dev),
+            "workspace": torch.zeros(max(int(workspace_bytes), 16) // 4, dtype=torch.float32, device=dev)}
+
+
+def store_rollout(b, k, obs, action, reward, done, resetting=None):
+    """slot k of the rollout buffers `b`, as train.py's loop forms it: reward (1 - resetting), max(done, resetting),
+    use = 1 - resetting.  action None: the action is already in b["action"][k]."""
+    b["obs"][k].copy_(obs)
+    if action is not None:
+        b["action"][k].copy_(action)
+    if resetting is None:
+        b["reward"][k].copy_(reward)
+        b["done"][k].copy_(done)
+        b["use"][k].fill_(1.0)
+    else:
+        r = resetting.float()
+        b["reward"][k].copy_(reward * (1.0 - r))
+        b["done"][k].copy_(torch.maximum(done.float(), r))
+        b["use"][k].copy_(1.0 - r)
+
+
+def policy_weights(tensors, device, who):
+    """the 13 tensors as an xarm_policy_weights of device pointers"""
+    w = _native.XarmPolicyWeights()
+    for k, t in zip(_native.POLICY_WEIGHT_FIELDS, tensors):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
+            raise ValueError("%s needs contiguous float32 tensors on %s (%s)" % (who, device, k))
+        setattr(w, k, t.data_ptr())
+    return w
+
+
 class DeviceA2C:
     """One A2C update per `update()` call on the model's GPU.
 
@@ -75,9 +110,7 @@ class DeviceA2C:
         self._layout = _native.XarmA2CLayout(E, T, D, A, _native.POLICY_HIDDEN)
         nbytes = C.c_int64(0)
         _native.check(self._L, None, self._L.xarm_a2c_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_a2c_workspace_bytes")
-        self.buffers = {"obs": torch.zeros(T, E, D, device=dev), "action": torch.zeros(T, E, A, device=dev), "reward": torch.zeros(T, E, device=dev),
-                        "done": torch.zeros(T, E, device=dev), "use": torch.ones(T, E, device=dev),
-                        "workspace": torch.zeros(max(int(nbytes.value), 16) // 4, dtype=torch.float32, device=dev)}
+        self.buffers = rollout_buffers(T, E, D, A, dev, nbytes.value)
         self.square_avg = [torch.zeros_like(p) for p in self.params()]
         self.stats = torch.zeros(8, device=dev)
         self.num_params = sum(p.numel() for p in self.params())
@@ -86,29 +119,12 @@ class DeviceA2C:
         return module_params(self.model)
 
     def _weights(self, tensors):
-        w = _native.XarmPolicyWeights()
-        for k, t in zip(_native.POLICY_WEIGHT_FIELDS, tensors):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                raise ValueError("DeviceA2C needs contiguous float32 tensors on %s (%s)" % (self.device, k))
-            setattr(w, k, t.data_ptr())
-        return w
+        return policy_weights(tensors, self.device, "DeviceA2C")
 
     def store(self, k, obs, action, reward, done, resetting=None):
         """slot k of the rollout, as train.py's loop forms it: reward (1 - resetting), max(done, resetting), use = 1 - resetting.
         action None: the action is already in buffers["action"][k]."""
-        b = self.buffers
-        b["obs"][k].copy_(obs)
-        if action is not None:
-            b["action"][k].copy_(action)
-        if resetting is None:
-            b["reward"][k].copy_(reward)
-            b["done"][k].copy_(done)
-            b["use"][k].fill_(1.0)
-        else:
-            r = resetting.float()
-            b["reward"][k].copy_(reward * (1.0 - r))
-            b["done"][k].copy_(torch.maximum(done.float(), r))
-            b["use"][k].copy_(1.0 - r)
+        store_rollout(self.buffers, k, obs, action, reward, done, resetting)
 
     def _call(self, weights, square_avg, last_obs, hyper, out_returns, out_grad, out_stats):
         E, D = self.num_envs, self.obs_width

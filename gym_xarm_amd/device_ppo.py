@@ -1,0 +1,159 @@
+"""Device-resident PPO update: stable-baselines3's `PPO.train()` on a stored rollout - GAE(lambda), `n_epochs` passes over shuffled
+minibatches, per-minibatch advantage normalisation, the clipped surrogate, the backward of both towers, `clip_grad_norm_` and
+`Adam.step` - as one stream-ordered call of 4 + 3 S HIP launches, S = n_epochs x minibatches (csrc/xarm_k_ppo.hip).
+
+A torch PPO update is S times the launch chain of an A2C update (forward of both towers under autograd, backward, clip, optimiser);
+`DevicePPO` keeps the rollout in the buffers `DeviceA2C` uses and updates the module's own parameter tensors in place, so a
+`DevicePolicy` on the same module (or the module itself) sees the new weights in its next call.  The torch PPO block of train.py
+stays as it is and is the checker (tests/test_ppo_host.py, tests/test_ppo_gpu.py)."""
+import ctypes as C
+
+import torch
+
+from . import _native
+from .device_a2c import module_params, policy_weights, rollout_buffers, store_rollout
+
+
+def _check_adam(opt):
+    for g in opt.param_groups:
+        if g.get("amsgrad", False) or g.get("weight_decay", 0) != 0 or g.get("maximize", False):
+            raise ValueError("the device update is Adam without amsgrad, weight decay or maximize")
+
+
+def load_adam(exp_avg, exp_avg_sq, step, opt, params):
+    """copy the state of a torch.optim.Adam built on `params` into the 13 + 13 state tensors and the step counter (zeros for a
+    parameter the optimiser has not stepped yet)"""
+    _check_adam(opt)
+    steps = set()
+    with torch.no_grad():
+        for m, v, p in zip(exp_avg, exp_avg_sq, params):
+            st = opt.state.get(p, {})
+            if "exp_avg" in st:
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+                steps.add(int(st["step"]))
+            else:
+                m.zero_()
+                v.zero_()
+                steps.add(0)
+        if len(steps) != 1:
+            raise ValueError("the device update keeps one step count for all parameters; the optimiser holds %s" % sorted(steps))
+        step.fill_(steps.pop())
+
+
+def export_adam(exp_avg, exp_avg_sq, step, opt, params):
+    """the other direction: the optimiser continues from the state tensors and the step counter (reads `step` back)"""
+    _check_adam(opt)
+    t = float(int(step.item()))
+    with torch.no_grad():
+        for m, v, p in zip(exp_avg, exp_avg_sq, params):
+            st = opt.state[p]
+            if "exp_avg" in st:
+                st["exp_avg"].copy_(m)
+                st["exp_avg_sq"].copy_(v)
+                st["step"].fill_(t)
+            else:
+                st["step"] = torch.tensor(t, dtype=torch.float32)
+                st["exp_avg"] = m.detach().clone()
+                st["exp_avg_sq"] = v.detach().clone()
+
+
+class DevicePPO:
+    """One PPO update per `update()` call on the model's GPU.
+
+    model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors; they are read and written in place.
+    `buffers` and `store(k, ...)` are DeviceA2C's.  `exp_avg`, `exp_avg_sq` (13 tensors each) and `step` (int64 [1]) are Adam's state,
+    `perm` (int32 [n_epochs, N]) the minibatch order: all device tensors.  `stats` [S, 8]: one row per optimiser step of the last update,
+    policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, 0.  batch_size None: ceil(N / 4)."""
+
+    def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
+                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0):
+        self.model, self.num_envs, self.n_steps, self.n_epochs = model, int(num_envs), int(n_steps), int(n_epochs)
+        N = self.num_envs * self.n_steps
+        self.batch_size = int(batch_size) if batch_size is not None else max(1, -(-N // 4))
+        self.hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip_range, lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, vf_coef=vf_coef,
+                          ent_coef=ent_coef, max_grad_norm=max_grad_norm)
+        self.normalize_advantage = bool(normalize_advantage)
+        self.obs_width = int(model.pi[0].in_features)
+        self.act_dim = int(model.pi[4].out_features)
+        if int(model.pi[0].out_features) != _native.POLICY_HIDDEN or int(model.pi[2].out_features) != _native.POLICY_HIDDEN:
+            raise ValueError("DevicePPO updates 64-64 towers (XARM_POLICY_HIDDEN)")
+        self.device = model.log_std.device
+        if self.device.type != "cuda":
+            raise ValueError("DevicePPO runs the update with HIP kernels on the model's GPU: the model is on '%s'.  There is no host "
+                             "path; the torch PPO block of train.py (autograd, clip_grad_norm_, Adam) is the host implementation." % self.device)
+        self._L = _native.load()
+        T, E, D, A, dev = self.n_steps, self.num_envs, self.obs_width, self.act_dim, self.device
+        self._layout = _native.XarmPPOLayout(E, T, D, A, _native.POLICY_HIDDEN, self.n_epochs, self.batch_size)
+        nbytes = C.c_int64(0)
+        _native.check(self._L, None, self._L.xarm_ppo_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_ppo_workspace_bytes")
+        self.minibatches = -(-N // min(self.batch_size, N)) if N > 0 else 0
+        self.num_steps = self.n_epochs * self.minibatches
+        self.launches = 4 + 3 * self.num_steps
+        self.buffers = rollout_buffers(T, E, D, A, dev, nbytes.value)
+        self.exp_avg = [torch.zeros_like(p) for p in self.params()]
+        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params()]
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.perm = torch.arange(N, dtype=torch.int32, device=dev).repeat(self.n_epochs, 1).contiguous()
+        self.stats = torch.zeros(max(self.num_steps, 1), 8, device=dev)
+        self.num_params = sum(p.numel() for p in self.params())
+        self._gen = torch.Generator(device=dev)
+        self._gen.manual_seed(int(seed))
+
+    def params(self):
+        return module_params(self.model)
+
+    def store(self, k, obs, action, reward, done, resetting=None):
+        """slot k of the rollout (device_a2c.store_rollout)"""
+        store_rollout(self.buffers, k, obs, action, reward, done, resetting)
+
+    def shuffle(self):
+        """a fresh permutation per epoch from the object's own seeded device generator, in place (allocates: not for a capture)"""
+        N = self.num_envs * self.n_steps
+        for ep in range(self.n_epochs):
+            self.perm[ep].copy_(torch.randperm(N, generator=self._gen, device=self.device))
+
+    def _call(self, weights, exp_avg, exp_avg_sq, step, last_obs, hyper, old_logp, out_adv, out_returns, out_grad, out_stats):
+        E, D, T = self.num_envs, self.obs_width, self.n_steps
+        assert last_obs.dtype == torch.float32 and last_obs.is_contiguous() and tuple(last_obs.shape) == (E, D) and last_obs.device == self.device, \
+            "last_obs must be a contiguous float32 [num_envs, D] tensor on the model's device"
+        for t, shape in ((old_logp, (T, E)), (out_adv, (T, E)), (out_returns, (T, E)), (out_grad, (self.num_params,))):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == self.device), \
+                "old_logp / out_adv / out_returns [n_steps, num_envs] and out_grad [num_params]: contiguous float32 on the model's device"
+        b = self.buffers
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        params = _native.XarmPPOParams(*([float(hyper[k]) for k in _native.PPO_HYPER] + [int(self.normalize_advantage)]))
+        W = lambda ts: C.byref(policy_weights(ts, self.device, "DevicePPO"))
+        rc = self._L.xarm_ppo_update(C.byref(self._layout), C.byref(params), W(weights), W(exp_avg), W(exp_avg_sq), p(step), p(b["obs"]), p(b["action"]),
+                                     p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(old_logp), p(self.perm), p(b["workspace"]), p(out_adv),
+                                     p(out_returns), p(out_grad), p(out_stats), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _native.check(self._L, None, rc, "xarm_ppo_update")
+
+    def update(self, last_obs, shuffle=True, old_logp=None, out_adv=None, out_returns=None, out_grad=None):
+        """one update from the stored rollout and the observation after its last step; the module's parameters, Adam's state and `step`
+        change in place, `stats` is rewritten.  shuffle: refill `perm` first.  With shuffle=False nothing is allocated and nothing is
+        read back, so the call can be captured in a torch.cuda.graph; a captured user calls shuffle() between replays.  old_logp [T, E]:
+        used in place of the log-probabilities at call start.  out_adv / out_returns [T, E], out_grad [num_params] (debug): the
+        advantages before normalisation, the returns and step 0's gradient before the clip."""
+        if shuffle:
+            self.shuffle()
+        self._call(self.params(), self.exp_avg, self.exp_avg_sq, self.step, last_obs, self.hyper, old_logp, out_adv, out_returns, out_grad, self.stats)
+        return self.stats
+
+    def grad(self, last_obs, old_logp=None):
+        """(step 0's flat gradient before the clip [num_params], adv [T, E], returns [T, E], stats [S, 8]) of the stored rollout and the
+        present `perm`, computed by the same call on scratch copies of the weights and of Adam's state with lr = 0: the module is not
+        touched (debug; allocates)"""
+        w, m, v = [p.detach().clone() for p in self.params()], [s.clone() for s in self.exp_avg], [s.clone() for s in self.exp_avg_sq]
+        dev, T, E = self.device, self.n_steps, self.num_envs
+        g, a, r, st = torch.empty(self.num_params, device=dev), torch.empty(T, E, device=dev), torch.empty(T, E, device=dev), torch.zeros_like(self.stats)
+        self._call(w, m, v, self.step.clone(), last_obs, dict(self.hyper, lr=0.0), old_logp, a, r, g, st)
+        return g, a, r, st
+
+    def load_optimizer(self, opt):
+        """continue from a torch.optim.Adam built on the same module"""
+        load_adam(self.exp_avg, self.exp_avg_sq, self.step, opt, self.params())
+
+    def export_optimizer(self, opt):
+        """let a torch.optim.Adam built on the same module continue from this updater's state"""
+        export_adam(self.exp_avg, self.exp_avg_sq, self.step, opt, self.params())

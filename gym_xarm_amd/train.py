@@ -245,9 +245,9 @@ class ActorCritic(nn.Module):
         return self.vf(x).squeeze(-1)
 
 
-def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.99, lr=7e-4, seed=0, config=None, log_every=50,
+def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
-          device_update=False):
+          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -259,7 +259,16 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
     from the stored actions.
     device_update: the update itself - bootstrap value, returns, backward, clip_grad_norm_ and RMSprop - in HIP kernels on the
     model's own parameters (gym_xarm_amd/device_a2c.py DeviceA2C) instead of the autograd block below; the rollout is stored in its
-    buffers and no torch optimiser is created."""
+    buffers and no torch optimiser is created.
+    algo: "a2c" (n_steps 5, lr 7e-4: the reference's learner) or "ppo" (n_steps 16, lr 3e-4): stable-baselines3's PPO.train() on each
+    rollout - GAE(gae_lambda) from the rollout's values, n_epochs passes over shuffled minibatches of batch_size rows (None: a quarter
+    of the rollout), per-minibatch advantage normalisation over the used rows, the surrogate clipped at clip_range, clip_grad_norm_
+    and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO)."""
+    if algo not in ("a2c", "ppo"):
+        raise ValueError("algo must be 'a2c' or 'ppo'")
+    ppo = algo == "ppo"
+    n_steps = (16 if ppo else 5) if n_steps is None else n_steps
+    lr = (3e-4 if ppo else 7e-4) if lr is None else lr
     torch.manual_seed(seed)
     if env is None:
         import gym_xarm_amd
@@ -275,10 +284,19 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
         monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     model = ActorCritic(venv.dim, env.act_dim).to(dev)
-    if device_update:
+    n_rows = n_steps * num_envs
+    batch_size = max(1, -(-n_rows // 4)) if batch_size is None else min(int(batch_size), n_rows)
+    if device_update and ppo:
+        from .device_ppo import DevicePPO
+        a2c = DevicePPO(model, num_envs, n_steps=n_steps, n_epochs=n_epochs, batch_size=batch_size, gamma=gamma, gae_lambda=gae_lambda,
+                        clip_range=clip_range, lr=lr, eps=1e-5, seed=seed)
+        env_action = torch.empty(num_envs, env.act_dim, device=dev)
+    elif device_update:
         from .device_a2c import DeviceA2C
         a2c = DeviceA2C(model, num_envs, n_steps=n_steps, gamma=gamma, lr=lr, alpha=0.99, eps=1e-5)
         env_action = torch.empty(num_envs, env.act_dim, device=dev)
+    elif ppo:
+        opt = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
     else:
         opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
     if device_policy:
@@ -320,6 +338,37 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=5, gamma=0.
             obs = nobs
         if device_update:
             a2c.update(obs)
+        elif ppo:
+            O, A, U = torch.stack(obs_buf).flatten(0, 1), torch.stack(act_buf).flatten(0, 1), torch.stack(use_buf).flatten()
+            with torch.no_grad():
+                values = model.value(torch.stack(obs_buf))
+                old_logp = model.dist(O).log_prob(A).sum(-1)
+                next_value, next_adv, advs = model.value(obs), torch.zeros(num_envs, device=dev), []
+                for k in reversed(range(n_steps)):
+                    keep = 1.0 - done_buf[k]
+                    delta = rew_buf[k] + gamma * keep * next_value - values[k]
+                    next_adv = delta + gamma * gae_lambda * keep * next_adv
+                    next_value = values[k]
+                    advs.append(next_adv)
+                adv = torch.stack(advs[::-1])
+                rets, adv = (adv + values).flatten(), adv.flatten()
+            for _ in range(n_epochs):
+                perm = torch.randperm(n_rows, device=dev)
+                for m in range(0, n_rows, batch_size):
+                    idx = perm[m:m + batch_size]
+                    u, a_mb = U[idx], adv[idx]
+                    n = u.sum()
+                    n_use = n.clamp(min=1.0)
+                    mu = (a_mb * u).sum() / n_use
+                    sigma = ((((a_mb - mu) ** 2) * u).sum() / (n - 1.0).clamp(min=1.0)).sqrt()
+                    a_hat = torch.where(n > 1.0, (a_mb - mu) / (sigma + 1e-8), a_mb)
+                    ratio = (model.dist(O[idx]).log_prob(A[idx]).sum(-1) - old_logp[idx]).exp()
+                    surr = torch.min(ratio * a_hat, ratio.clamp(1.0 - clip_range, 1.0 + clip_range) * a_hat)
+                    loss = -(surr * u).sum() / n_use + 0.5 * (((rets[idx] - model.value(O[idx])) ** 2) * u).sum() / n_use
+                    opt.zero_grad(set_to_none=True)
+                    loss.backward()
+                    nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+                    opt.step()
         else:
             with torch.no_grad():
                 ret = model.value(obs)
@@ -370,14 +419,19 @@ def main():
     ap.add_argument("--check-freq", type=int, default=1000)
     ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
     ap.add_argument("--device-policy", action="store_true", help="the rollout's sample + clamp in one HIP launch (gym_xarm_amd/device_policy.py)")
-    ap.add_argument("--device-update", action="store_true", help="returns, backward, clip and RMSprop in HIP kernels (gym_xarm_amd/device_a2c.py)")
+    ap.add_argument("--device-update", action="store_true", help="the update in HIP kernels (gym_xarm_amd/device_a2c.py, device_ppo.py)")
+    ap.add_argument("--algo", choices=("a2c", "ppo"), default="a2c", help="a2c: n-step returns, RMSprop; ppo: GAE, clipped surrogate, Adam")
+    ap.add_argument("--n-steps", type=int, default=None, help="rollout length (a2c 5, ppo 16)")
+    ap.add_argument("--n-epochs", type=int, default=4, help="ppo: passes over a rollout")
+    ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout)")
     args = ap.parse_args()
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
-                              device_policy=args.device_policy, device_update=args.device_update)
+                              device_policy=args.device_policy, device_update=args.device_update, algo=args.algo, n_steps=args.n_steps,
+                              n_epochs=args.n_epochs, batch_size=args.batch_size)
     if args.save:
         save_model(args.save, model, venv)
 

@@ -500,6 +500,64 @@ int xarm_a2c_update(const xarm_a2c_layout *layout, const xarm_a2c_params *params
                     float *out_returns /* may be NULL */, float *out_grad /* may be NULL */, float *out_stats /* may be NULL */,
                     void *stream);
 
+/* ---- device-resident PPO update (gym_xarm_amd/csrc/xarm_ppo_core.h, xarm_k_ppo.hip): one PPO.train() of
+ * stable-baselines3 on a stored rollout - GAE(lambda), n_epochs passes over shuffled minibatches, per-minibatch advantage
+ * normalisation, the clipped surrogate, the backward of both towers, torch's clip_grad_norm_ and torch's Adam (no amsgrad, no weight
+ * decay) - as 4 + 3 S stream-ordered launches on `stream`, S = n_epochs * ceil(N / batch_size), N = n_steps * num_envs, with no
+ * allocation, no host read and no side stream.  Memory, shapes and the A2C arguments are those of xarm_a2c_update.
+ *   v_k = value(obs_k), v_T = value(last_obs) and old_logp (the log-probability of the stored action) under the weights at call start;
+ *   keep = 1 - [done_k != 0]; delta = fmaf(gamma keep, v_k+1, reward_k) - v_k; adv_k = fmaf(gamma lambda keep, adv_k+1, delta), adv_T = 0;
+ *   ret_k = adv_k + v_k (no gradient through adv or ret)
+ *   step s = epoch * M + m reads the rows perm[epoch][m * B .. min((m + 1) * B, N)); an entry outside [0, N) counts as a row with
+ *   use = 0 and nothing is read through it.  n = sum use over the step's rows, n_use = max(n, 1);
+ *   A^ = (adv - mu) / (sigma + 1e-8) with the step's float64 mean and unbiased standard deviation over its used rows (adv itself when
+ *   n <= 1 or normalize_advantage == 0); rho = exp(logp - old_logp);
+ *   loss = -sum(min(rho A^, clamp(rho, 1 - clip_range, 1 + clip_range) A^) use) / n_use + vf_coef sum((ret - value)^2 use) / n_use
+ *          - ent_coef sum_c(log_std_c + 1/2 + log(2 pi) / 2), logp and value under the weights of the step;
+ *   the clip of A2C; t = ++step; m += (1 - beta1)(g - m); v = beta2 v + (1 - beta2) g^2;
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   exp_avg, exp_avg_sq  Adam's 13 + 13 state tensors in the weights' shapes, read and written in place
+ *   step_i64    device int64 [1]: Adam's step count, advanced by S on the device (a replayed graph continues the count)
+ *   old_logp    [T, E], may be NULL (computed at call start); perm int32 [n_epochs, N], each row a permutation of 0 .. N - 1
+ *   workspace   xarm_ppo_workspace_bytes() bytes, 16-byte aligned; holds nothing between calls
+ *   out_adv / out_returns [T, E], out_grad [P] (step 0's gradient before the clip), out_stats [S, 8], row s = policy_loss, value_loss,
+ *               entropy, grad_norm, n_use, approx_kl = sum(((rho - 1) - log rho) use) / n_use, clip_fraction =
+ *               sum([|rho - 1| > clip_range] use) / n_use, 0: each may be NULL
+ * No floating-point atomics: the same inputs and perm give the same bits.  num_envs == 0 launches nothing. */
+typedef struct xarm_ppo_layout {
+    int32_t num_envs;
+    int32_t n_steps;            /* >= 1; n_steps * num_envs < 2^31 */
+    int32_t obs_dim;            /* D, 1 .. XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_POLICY_MAX_ACT */
+    int32_t hidden;             /* XARM_POLICY_HIDDEN */
+    int32_t n_epochs;           /* >= 1 */
+    int32_t batch_size;         /* >= 1; n_epochs * ceil(N / batch_size) <= 4096 */
+} xarm_ppo_layout;              /* 28 bytes */
+typedef struct xarm_ppo_params {
+    double gamma;               /* [0, 1] */
+    double gae_lambda;          /* [0, 1] */
+    double clip_range;          /* > 0 */
+    double lr;                  /* >= 0 */
+    double beta1;               /* [0, 1) */
+    double beta2;               /* [0, 1) */
+    double eps;                 /* > 0 */
+    double vf_coef;
+    double ent_coef;
+    double max_grad_norm;       /* > 0 */
+    int32_t normalize_advantage;
+} xarm_ppo_params;              /* 88 bytes */
+/* *bytes = size of `workspace` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_ppo_workspace_bytes(const xarm_ppo_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: everything xarm_a2c_update refuses (with exp_avg / exp_avg_sq in square_avg's place), n_epochs < 1, batch_size < 1,
+ * n_epochs * ceil(N / batch_size) > 4096, gae_lambda outside [0, 1], a clip_range that is not finite or <= 0, beta1 or beta2 outside
+ * [0, 1), or with num_envs > 0 a NULL exp_avg / exp_avg_sq tensor, a NULL step_i64, a NULL perm. */
+int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params, const xarm_policy_weights *weights,
+                    const xarm_policy_weights *exp_avg, const xarm_policy_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *action, const float *reward, const float *done, const float *use /* may be NULL */,
+                    const float *last_obs, const float *old_logp /* may be NULL */, const int32_t *perm, void *workspace,
+                    float *out_adv /* may be NULL */, float *out_returns /* may be NULL */, float *out_grad /* may be NULL */,
+                    float *out_stats /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
