@@ -22,7 +22,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
-           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update"]
+           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update",
+           "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -117,6 +118,26 @@ class XarmPPOParams(C.Structure):
     _fields_ = [(k, C.c_double) for k in PPO_HYPER] + [("normalize_advantage", C.c_int32)]
 
 
+SAC_MAX_ACT = 8             # XARM_SAC_MAX_ACT
+SAC_HYPER = ("gamma", "lr", "tau", "ent_coef", "target_entropy", "beta1", "beta2", "eps")
+SAC_TOWERS = ("actor", "q1", "q2", "q1_target", "q2_target")
+
+
+class XarmSACLayout(C.Structure):
+    """include/xarm_hip.h xarm_sac_layout (24 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("batch_size", "obs_dim", "act_dim", "hidden")] + [("row_offset", C.c_int64)]
+
+
+class XarmSACParams(C.Structure):
+    """include/xarm_hip.h xarm_sac_params (80 bytes)"""
+    _fields_ = [("seed", C.c_uint64)] + [(k, C.c_double) for k in SAC_HYPER] + [("auto_ent_coef", C.c_int32), ("deterministic", C.c_int32)]
+
+
+class XarmSACWeights(C.Structure):
+    """include/xarm_hip.h xarm_sac_weights (31 device pointers): five towers of W1, b1, W2, b2, W3, b3 and log_alpha"""
+    _fields_ = [(k, C.c_void_p * 6) for k in SAC_TOWERS] + [("log_alpha", C.c_void_p)]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -177,6 +198,10 @@ def load(path=None):
     pl = C.POINTER(XarmPPOLayout)
     L.xarm_ppo_workspace_bytes.argtypes = [pl, C.POINTER(C.c_int64)]
     L.xarm_ppo_update.argtypes = [pl, C.POINTER(XarmPPOParams)] + [C.POINTER(XarmPolicyWeights)] * 3 + [vp] * 15
+    sl, sp, sw = C.POINTER(XarmSACLayout), C.POINTER(XarmSACParams), C.POINTER(XarmSACWeights)
+    L.xarm_sac_workspace_bytes.argtypes = [sl, C.POINTER(C.c_int64)]
+    L.xarm_sac_act.argtypes = [sl, sp, sw] + [vp] * 5
+    L.xarm_sac_update.argtypes = [sl, sp, sw, sw, sw] + [vp] * 15
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

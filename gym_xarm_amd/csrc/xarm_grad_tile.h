@@ -1,5 +1,6 @@
 // xarm_grad_tile.h - one 64-row tile of the two-tower backward, shared by the gradient kernels of the A2C update (xarm_k_a2c.hip,
-// DESIGN.md 21) and of the PPO update (xarm_k_ppo.hip).  Device code only; both units are built with -ffp-contract=off.
+// DESIGN.md 21), of the PPO update (xarm_k_ppo.hip) and of the SAC update (xarm_k_sac.hip).  Device code
+// only; the units are built with -ffp-contract=off.
 //
 // A workgroup of 256 threads works on ONE tower.  Per tile, in LDS and transposed ([unit][row], stride 65: a lane per row and a lane
 // per unit both read without bank conflicts): the rows, h1 and h2 from the policy's chains (lane = row, wavefront w = units
@@ -14,6 +15,13 @@
 //   FROM_H2                           false: the deltas need nothing of this tile's forward and are written with its load.
 //                                     true: the tower's outputs W3 h2 + b3 (the policy's chain, order KORD) are put to D3[c * LS] first and
 //                                     deltas() replaces them - a head that needs mean / value under the CURRENT weights.
+// Two optional traits, which a head that does not name them leaves off (A2C's and PPO's do not: their instantiations are the
+// operations above and nothing else):
+//   INPUT_GRAD = true                 behind d1 the tile also forms the gradient at the tower's input, dx_j = sum_i W1[i][j] d1_i (i
+//                                     ascending, fmaf from 0), for the columns col0() <= j < col0() + ncol(): lane r of wavefront w calls
+//                                     void input_grad(int r, int c, float dx) for slot r and c = w, w + 4, ... (c counted from col0())
+//   WEIGHT_GRAD = false               the outer products (dW3, dW2, dW1 and the bias sums) are skipped and G is not touched: a pass that
+//                                     wants the tower's outputs and its input gradient only
 #pragma once
 #include <hip/hip_runtime.h>
 #include "xarm_a2c_core.h"
@@ -22,6 +30,11 @@ namespace xa2c {
 
 constexpr int THREADS = 256, LS = ROWS + 1, UPW = 16;     // LDS row stride; units per wavefront in the lane = row stages
 static_assert(ROWS == 64 && THREADS == 4 * ROWS && UPW * (THREADS / 64) == HID, "four wavefronts: 64 rows x 16 units each");
+
+template <class H, class = void> struct head_input_grad { static constexpr bool value = false; };
+template <class H> struct head_input_grad<H, decltype((void)H::INPUT_GRAD)> { static constexpr bool value = H::INPUT_GRAD; };
+template <class H, class = void> struct head_weight_grad { static constexpr bool value = true; };
+template <class H> struct head_weight_grad<H, decltype((void)H::WEIGHT_GRAD)> { static constexpr bool value = H::WEIGHT_GRAD; };
 
 struct TileLds {
     float *Xt, *H1t, *H2t, *D3t;       // [16 JW][LS], [HID][LS], [HID][LS], [MAX_ACT][LS]
@@ -64,25 +77,13 @@ template <int JW> struct TileGrad {
     }
 };
 
-// one tile; ends on a barrier, so the caller may rewrite what row() reads and call it again
-template <int JW, class Head>
-__device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const float *obs, const TileLds &L, Head &head, TileGrad<JW> &G) {
+// the forward of one tile from the rows in Xt: h1 and h2 by the policy's chains (lane = row, wavefront w = units 16 w .. 16 w + 15) and,
+// with OUTPUTS, the tower's outputs W3 h2 + b3 in D3t[c * LS + row], c < nout.  r, wv: the thread's lane and (wavefront-uniform)
+// wavefront.  Starts behind a barrier on Xt, ends on a barrier.
+template <bool OUTPUTS>
+__device__ __forceinline__ void tile_forward(const Tower &T, int D, int nout, const TileLds &L, int r, int wv) {
     float *const Xt = L.Xt, *const H1t = L.H1t, *const H2t = L.H2t, *const D3t = L.D3t;
-    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), u0 = UPW * wv, ib = t & 15, jb = t >> 4;
-
-    // the tile's rows (zeros in empty slots and past column D) and the deltas at the outputs (wavefront 0: lane = row)
-    for (int idx = t; idx < 16 * JW * ROWS; idx += THREADS) {
-        const int rr = idx / (16 * JW), j = idx - rr * (16 * JW);
-        const int64_t n = head.row(rr);
-        Xt[j * LS + rr] = (n >= 0 && j < D) ? obs[n * D + j] : 0.0f;
-    }
-    if (wv == 0) {
-#pragma unroll
-        for (int c = 0; c < MAX_ACT; c++) D3t[c * LS + r] = 0.0f;
-        if constexpr (!Head::FROM_H2) head.deltas(r, D3t + r);
-    }
-    __syncthreads();
-
+    const int u0 = UPW * wv;
     {   // h1
         float acc[UPW];
 #pragma unroll
@@ -102,7 +103,7 @@ __device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const
     }
     __syncthreads();
 
-    if constexpr (Head::FROM_H2) {
+    if constexpr (OUTPUTS) {
         // the outputs: wavefront w takes outputs 4 w .. 4 w + 3 (rows of W3 past nout do not exist and are not read)
 #pragma unroll
         for (int a = 0; a < 4; a++) {
@@ -114,23 +115,51 @@ __device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const
             }
         }
         __syncthreads();
+    }
+}
+
+// one tile; ends on a barrier, so the caller may rewrite what row() reads and call it again
+template <int JW, class Head>
+__device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const float *obs, const TileLds &L, Head &head, TileGrad<JW> &G) {
+    float *const Xt = L.Xt, *const H1t = L.H1t, *const H2t = L.H2t, *const D3t = L.D3t;
+    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), u0 = UPW * wv, ib = t & 15, jb = t >> 4;
+
+    // the tile's rows (zeros in empty slots and past column D) and the deltas at the outputs (wavefront 0: lane = row)
+    for (int idx = t; idx < 16 * JW * ROWS; idx += THREADS) {
+        const int rr = idx / (16 * JW), j = idx - rr * (16 * JW);
+        const int64_t n = head.row(rr);
+        Xt[j * LS + rr] = (n >= 0 && j < D) ? obs[n * D + j] : 0.0f;
+    }
+    if (wv == 0) {
+#pragma unroll
+        for (int c = 0; c < MAX_ACT; c++) D3t[c * LS + r] = 0.0f;
+        if constexpr (!Head::FROM_H2) head.deltas(r, D3t + r);
+    }
+    __syncthreads();
+
+    tile_forward<Head::FROM_H2>(T, D, nout, L, r, wv);
+
+    if constexpr (Head::FROM_H2) {
         if (wv == 0) head.deltas(r, D3t + r);
         __syncthreads();
     }
 
-    // dW3, db3: thread (unit r, outputs 4 wv .. 4 wv + 3)
-    if (4 * wv < nout) {
-        for (int rr = 0; rr < ROWS; rr++) {
-            const float hv = H2t[r * LS + rr];
+    constexpr bool WG = head_weight_grad<Head>::value;
+    if constexpr (WG) {
+        // dW3, db3: thread (unit r, outputs 4 wv .. 4 wv + 3)
+        if (4 * wv < nout) {
+            for (int rr = 0; rr < ROWS; rr++) {
+                const float hv = H2t[r * LS + rr];
 #pragma unroll
-            for (int a = 0; a < 4; a++) {
-                const float dv = D3t[(4 * wv + a) * LS + rr];
-                G.g3[a] = fma32(dv, hv, G.g3[a]);
-                G.gb3[a] += dv;
+                for (int a = 0; a < 4; a++) {
+                    const float dv = D3t[(4 * wv + a) * LS + rr];
+                    G.g3[a] = fma32(dv, hv, G.g3[a]);
+                    G.gb3[a] += dv;
+                }
             }
         }
+        __syncthreads();
     }
-    __syncthreads();
     {   // d2 over h2
         float pre[UPW];
 #pragma unroll
@@ -148,19 +177,21 @@ __device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const
     }
     __syncthreads();
 
-    // dW2, db2: thread (ib, jb) owns (ib + 16 a, jb + 16 b)
-    for (int rr = 0; rr < ROWS; rr++) {
-        float dv[4], hv[4];
+    if constexpr (WG) {
+        // dW2, db2: thread (ib, jb) owns (ib + 16 a, jb + 16 b)
+        for (int rr = 0; rr < ROWS; rr++) {
+            float dv[4], hv[4];
 #pragma unroll
-        for (int a = 0; a < 4; a++) { dv[a] = H2t[(ib + 16 * a) * LS + rr]; hv[a] = H1t[(jb + 16 * a) * LS + rr]; }
+            for (int a = 0; a < 4; a++) { dv[a] = H2t[(ib + 16 * a) * LS + rr]; hv[a] = H1t[(jb + 16 * a) * LS + rr]; }
 #pragma unroll
-        for (int a = 0; a < 4; a++) {
-            G.gb2[a] += dv[a];
+            for (int a = 0; a < 4; a++) {
+                G.gb2[a] += dv[a];
 #pragma unroll
-            for (int b = 0; b < 4; b++) G.g2[a][b] = fma32(dv[a], hv[b], G.g2[a][b]);
+                for (int b = 0; b < 4; b++) G.g2[a][b] = fma32(dv[a], hv[b], G.g2[a][b]);
+            }
         }
+        __syncthreads();
     }
-    __syncthreads();
     {   // d1 over h1
         float pre[UPW];
 #pragma unroll
@@ -178,18 +209,29 @@ __device__ __forceinline__ void grad_tile(const Tower &T, int D, int nout, const
     }
     __syncthreads();
 
-    // dW1, db1: thread (ib, jb) owns (ib + 16 a, jb + 16 m)
-    for (int rr = 0; rr < ROWS; rr++) {
-        float dv[4], xv[JW];
+    if constexpr (head_input_grad<Head>::value) {
+        // dx over the head's columns: lane = row, wavefront wv the columns wv, wv + 4, ... (W1's column is a wavefront-uniform load)
+        const int c0 = head.col0(), nc = head.ncol();
+        for (int c = wv; c < nc; c += THREADS / 64) {
+            float dx = 0.0f;
+            for (int i = 0; i < HID; i++) dx = fma32(T.W1[i * D + c0 + c], H1t[i * LS + r], dx);
+            head.input_grad(r, c, dx);
+        }
+    }
+    if constexpr (WG) {
+        // dW1, db1: thread (ib, jb) owns (ib + 16 a, jb + 16 m)
+        for (int rr = 0; rr < ROWS; rr++) {
+            float dv[4], xv[JW];
 #pragma unroll
-        for (int a = 0; a < 4; a++) dv[a] = H1t[(ib + 16 * a) * LS + rr];
+            for (int a = 0; a < 4; a++) dv[a] = H1t[(ib + 16 * a) * LS + rr];
 #pragma unroll
-        for (int m = 0; m < JW; m++) xv[m] = Xt[(jb + 16 * m) * LS + rr];
+            for (int m = 0; m < JW; m++) xv[m] = Xt[(jb + 16 * m) * LS + rr];
 #pragma unroll
-        for (int a = 0; a < 4; a++) {
-            G.gb1[a] += dv[a];
+            for (int a = 0; a < 4; a++) {
+                G.gb1[a] += dv[a];
 #pragma unroll
-            for (int m = 0; m < JW; m++) G.g1[a][m] = fma32(dv[a], xv[m], G.g1[a][m]);
+                for (int m = 0; m < JW; m++) G.g1[a][m] = fma32(dv[a], xv[m], G.g1[a][m]);
+            }
         }
     }
     __syncthreads();

@@ -36,6 +36,7 @@
 #include "xarm_policy_core.h"
 #include "xarm_a2c_core.h"
 #include "xarm_ppo_core.h"
+#include "xarm_sac_core.h"
 
 using namespace xd;
 
@@ -1073,6 +1074,74 @@ int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params
     d.out_adv = out_adv; d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
     const int le = xppo::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_ppo_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ SAC update (xarm_k_sac.hip)
+int xarm_sac_workspace_bytes(const xarm_sac_layout *layout, int64_t *bytes) {
+    if (const char *why = xsac::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sac_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sac_workspace_bytes: NULL pointer");
+    xsac::Shape s;
+    xsac::Work k;
+    xsac::fill_shape(s, layout);
+    xsac::fill_work(k, s);
+    *bytes = k.total;
+    return XARM_OK;
+}
+
+int xarm_sac_act(const xarm_sac_layout *layout, const xarm_sac_params *params, const xarm_sac_weights *weights, int64_t *calls_i64,
+                 const float *obs, float *out_action, float *out_logp, void *stream) {
+    if (const char *why = xsac::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sac_act: %s", why);
+    if (!params) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sac_act: params is NULL");
+    if (!weights) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sac_act: weights is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xsac::act_pointer_error(params, weights, calls_i64, obs, out_action)) return fail(nullptr, XARM_E_INVALID, "xarm_sac_act: %s", why);
+    xsac::Dev d = {};
+    xsac::fill_shape(d.s, layout);
+    d.h.seed = params->seed;
+    d.h.deterministic = params->deterministic != 0;
+    d.actor = xsac::tower_of(weights->actor);
+    d.calls = calls_i64; d.obs = obs; d.out_action = out_action; d.out_logp = out_logp;
+    const int le = xsac::launch_act(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sac_act: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_sac_update(const xarm_sac_layout *layout, const xarm_sac_params *params, const xarm_sac_weights *weights,
+                    const xarm_sac_weights *exp_avg, const xarm_sac_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *next_obs, const float *action, const float *reward, const float *done, const float *use,
+                    const float *noise_pi, const float *noise_next, void *workspace, float *out_grad, float *out_dqda, float *out_target,
+                    float *out_stats, void *stream) {
+    if (const char *why = xsac::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sac_update: %s", why);
+    if (const char *why = xsac::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_sac_update: %s", why);
+    if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sac_update: weights / exp_avg / exp_avg_sq is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xsac::pointer_error(weights, exp_avg, exp_avg_sq, step_i64, obs, next_obs, action, reward, done, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_sac_update: %s", why);
+    xsac::Dev d = {};
+    xsac::Work k;
+    xsac::fill_shape(d.s, layout);
+    xsac::fill_hyper(d.h, params);
+    xsac::fill_work(k, d.s);
+    xsac::tensors_of(weights, d.w);
+    xsac::tensors_of(exp_avg, d.m);
+    xsac::tensors_of(exp_avg_sq, d.v);
+    for (int i = 0; i < 6; i++) {
+        d.tq[i] = const_cast<float *>(weights->q1_target[i]);
+        d.tq[6 + i] = const_cast<float *>(weights->q2_target[i]);
+    }
+    d.actor = xsac::tower_of(weights->actor); d.q1 = xsac::tower_of(weights->q1); d.q2 = xsac::tower_of(weights->q2);
+    d.q1t = xsac::tower_of(weights->q1_target); d.q2t = xsac::tower_of(weights->q2_target);
+    d.step = step_i64;
+    d.obs = obs; d.next_obs = next_obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.noise_pi = noise_pi; d.noise_next = noise_next;
+    char *base = (char *)workspace;
+    d.hdr = (float *)(base + k.hdr); d.y = (float *)(base + k.y); d.logp = (float *)(base + k.logp); d.z = (float *)(base + k.z);
+    d.xq = (float *)(base + k.xq); d.xpi = (float *)(base + k.xpi); d.qpi = (float *)(base + k.qpi); d.dqda = (float *)(base + k.dqda);
+    d.partial = (float *)(base + k.partial); d.scal_rows = (double *)(base + k.scal_rows); d.scal_q = (double *)(base + k.scal_q);
+    d.scal_p = (double *)(base + k.scal_p);
+    d.out_grad = out_grad; d.out_dqda = out_dqda; d.out_target = out_target; d.out_stats = out_stats;
+    const int le = xsac::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sac_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

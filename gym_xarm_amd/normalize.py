@@ -130,14 +130,44 @@ class DeviceVecNormalize:
         return {"nobs": torch.empty(self.num_envs, self.dim, device=self.device), "nrew": torch.empty(self.num_envs, device=self.device)}
 
     def reset(self):
+        self._lib()                                   # a CPU env is refused before it is touched
+        return self.reset_from(self.env.reset())
+
+    def reset_from(self, obs):
+        """reset()'s work on an observation the caller took from env.reset() itself (gym_xarm_amd/sac.py keeps the raw dict for its
+        replay buffer): the returns are zeroed, the statistics updated and the normalised observation returned"""
         L = self._lib()
-        obs = self.env.reset()
         nobs = torch.empty(self.num_envs, self.dim, device=self.device)
         rc = L.xarm_norm_obs(C.byref(self.layout), C.byref(self._params()), C.c_void_p(self.stats.data_ptr()),
                              C.c_void_p(self.ret.data_ptr()), C.c_void_p(self.work.data_ptr()), *self._parts(obs), 1,
                              C.c_void_p(nobs.data_ptr()), self._stream())
         _native.check(L, None, rc, "xarm_norm_obs")
         return nobs
+
+    def normalize_rows(self, out, observation, achieved_goal=None, desired_goal=None):
+        """out [B, dim] <- the B rows observation | achieved_goal | desired_goal normalised with the statistics as they are (one
+        xarm_norm_obs launch with update = 0; nothing is updated).  B is free: the rows of a replay sample.  The call's workspace is
+        allocated at the first call with a given B; after that no allocation and no host read, so it can be captured."""
+        L = self._lib()
+        B = int(observation.shape[0])
+        parts = [observation] if self.goal_dim == 0 else [observation, achieved_goal, desired_goal]
+        for x, w in zip(parts, (self.obs_dim, self.goal_dim, self.goal_dim)):
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.shape == (B, w) and x.device == self.stats.device, \
+                "row parts must be contiguous float32 [B, dim] tensors on the env's device"
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, self.dim) and out.device == self.stats.device, "out"
+        if not hasattr(self, "_row_calls"):
+            self._row_calls = {}
+        if B not in self._row_calls:
+            layout = _native.XarmNormLayout(B, self.obs_dim, self.goal_dim, max(B, 1))
+            nbytes = C.c_int64(0)
+            _native.check(L, None, L.xarm_norm_work_bytes(C.byref(layout), C.byref(nbytes)), "xarm_norm_work_bytes")
+            self._row_calls[B] = (layout, torch.empty(max(nbytes.value // 8, 1), device=self.device, dtype=torch.int64))
+        layout, work = self._row_calls[B]
+        params = _native.XarmNormParams(self.clip_obs, self.clip_reward, self.eps, self.gamma, 0.0, 0)
+        rc = L.xarm_norm_obs(C.byref(layout), C.byref(params), C.c_void_p(self.stats.data_ptr()), None, C.c_void_p(work.data_ptr()),
+                             *([C.c_void_p(x.data_ptr()) for x in parts] + [None] * (3 - len(parts))), 0, C.c_void_p(out.data_ptr()), self._stream())
+        _native.check(L, None, rc, "xarm_norm_obs")
+        return out
 
     def step_into(self, out, obs, rew, done, keep=None, t_seconds=None):
         """Normalise one env step's outputs into out["nobs"] [E, dim] / out["nrew"] [E] and update statistics, returns and the

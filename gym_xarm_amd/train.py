@@ -419,15 +419,26 @@ def main():
     ap.add_argument("--check-freq", type=int, default=1000)
     ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
     ap.add_argument("--device-policy", action="store_true", help="the rollout's sample + clamp in one HIP launch (gym_xarm_amd/device_policy.py)")
-    ap.add_argument("--device-update", action="store_true", help="the update in HIP kernels (gym_xarm_amd/device_a2c.py, device_ppo.py)")
-    ap.add_argument("--algo", choices=("a2c", "ppo"), default="a2c", help="a2c: n-step returns, RMSprop; ppo: GAE, clipped surrogate, Adam")
+    ap.add_argument("--device-update", action="store_true", help="the update in HIP kernels (gym_xarm_amd/device_a2c.py, device_ppo.py, device_sac.py)")
+    ap.add_argument("--algo", choices=("a2c", "ppo", "sac"), default="a2c",
+                    help="a2c: n-step returns, RMSprop; ppo: GAE, clipped surrogate, Adam; sac: SAC + HER (gym_xarm_amd/sac.py train_sac: --updates "
+                         "counts env steps)")
     ap.add_argument("--n-steps", type=int, default=None, help="rollout length (a2c 5, ppo 16)")
     ap.add_argument("--n-epochs", type=int, default=4, help="ppo: passes over a rollout")
-    ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout)")
+    ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout); sac: rows per step (256)")
+    ap.add_argument("--gradient-steps", type=int, default=1, help="sac: SAC steps per training env step")
     args = ap.parse_args()
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
+    if args.algo == "sac":
+        from . import sac
+        model, venv, hist = sac.train_sac(args.env, num_envs=args.num_envs, steps=args.updates, batch_size=args.batch_size or 256,
+                                          gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
+                                          device_update=args.device_update, device_normalize=args.device_normalize)
+        if args.save:
+            save_model(args.save, model, venv)
+        return
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
                               device_policy=args.device_policy, device_update=args.device_update, algo=args.algo, n_steps=args.n_steps,

@@ -558,6 +558,86 @@ int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params
                     float *out_adv /* may be NULL */, float *out_returns /* may be NULL */, float *out_grad /* may be NULL */,
                     float *out_stats /* may be NULL */, void *stream);
 
+/* ---- device-resident SAC update (gym_xarm_amd/csrc/xarm_sac_core.h, xarm_k_sac.hip): ONE gradient step of
+ * stable-baselines3's SAC.train() on a batch drawn from a replay buffer - the squashed-Gaussian actor on obs and next_obs, the
+ * entropy coefficient's step, the soft target, the step of both critics, the actor's step through the updated critics and the
+ * Polyak step of the targets - as six stream-ordered launches on `stream`, with no allocation, no host read, no atomics and no side
+ * stream.  Everything is caller-owned float32 DEVICE memory, row-major; B = batch_size, D = obs_dim, A = act_dim.
+ *   model    actor D -> 64 -> 64 -> 2A (tanh; outputs 0 .. A-1 the mean, A .. 2A-1 log_std), q1 / q2 / q1_target / q2_target
+ *            D + A -> 64 -> 64 -> 1 (tanh) on the row obs | action, log_alpha [1]; W in [out, in] layout as xarm_policy_weights
+ *   actor    ls = clamp(log_std, -20, 2); u = mean + exp(ls) z; a = tanh(u);
+ *            logp = sum_c(-z_c^2 / 2 - ls_c - log(2 pi) / 2) - sum_c log(1 - a_c^2 + 1e-6)
+ *   step     alpha = auto_ent_coef ? exp(log_alpha) : ent_coef, read before anything is stepped; use NULL = all ones;
+ *            n_use = max(sum use, 1); every mean below is sum(. use) / n_use
+ *            a_pi, logp_pi = actor(obs; z_pi);   a', logp' = actor(next_obs; z_next)
+ *            alpha_loss = -mean(log_alpha (logp_pi + target_entropy)), Adam on log_alpha (auto_ent_coef only)
+ *            y = reward + gamma (1 - done) (min(q1_target, q2_target)(next_obs | a') - alpha logp')      (no gradient)
+ *            critic_loss = (mean((q1(obs | action) - y)^2) + mean((q2(obs | action) - y)^2)) / 2, Adam on q1 and q2
+ *            actor_loss = mean(alpha logp_pi - min(q1, q2)(obs | a_pi)) under the stepped critics, Adam on the actor
+ *            target = (1 - tau) target + tau critic
+ *            Adam: t = ++step; m += (1 - beta1)(g - m); v = beta2 v + (1 - beta2) g^2;
+ *            p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps); no gradient clip
+ *   weights  the 31 tensors, READ AND WRITTEN in place (b1, W2, b2 and W3 of each tower 16-byte aligned)
+ *   exp_avg, exp_avg_sq  Adam's state of actor, q1, q2 and log_alpha in the same struct; the target fields are not read
+ *   step_i64 device int64 [1]: Adam's step count of the three optimisers, advanced by one on the device per call
+ *   noise_pi / noise_next [B, A]: the step's z.  NULL: Philox keyed by (seed, row, *step_i64 at call start, a tag per stream of noise)
+ *   workspace   xarm_sac_workspace_bytes() bytes, 16-byte aligned; holds nothing between calls
+ *   out_grad [P] (actor's 6 tensors, q1's, q2's, log_alpha: the gradients after the 1 / n_use factor), out_dqda [2, B, A] (d q_i /
+ *   d action at obs | a_pi under the stepped critics), out_target [B] (y), out_stats [8] = critic_loss, actor_loss, alpha_loss, alpha,
+ *   mean logp_pi, mean min-Q(obs | a_pi), n_use, 0: each may be NULL
+ * xarm_sac_act is the rollout / deployment call: out_action [B, A] = tanh(u) (tanh(mean) when deterministic), out_logp [B] (may be
+ * NULL), noise as xarm_policy_act draws it - Philox keyed by (seed, row_offset + row, *calls, column block) - and a stochastic call
+ * is followed by a one-thread launch that advances `calls`.  A row's result does not depend on the batch it is in.
+ * Sums over rows run in a fixed order through per-workgroup partials: the same inputs give the same bits.  batch_size == 0
+ * launches nothing. */
+#define XARM_SAC_MAX_ACT 8         /* 1 <= act_dim <= this: the actor's 2 act_dim outputs fill XARM_POLICY_MAX_ACT columns */
+typedef struct xarm_sac_layout {
+    int32_t batch_size;         /* B >= 0: rows of the call */
+    int32_t obs_dim;            /* D >= 1, D + act_dim <= XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_SAC_MAX_ACT */
+    int32_t hidden;             /* XARM_POLICY_HIDDEN */
+    int64_t row_offset;         /* xarm_sac_act: global index of row 0 (>= 0) */
+} xarm_sac_layout;              /* 24 bytes */
+typedef struct xarm_sac_params {
+    uint64_t seed;
+    double gamma;               /* [0, 1] */
+    double lr;                  /* >= 0 */
+    double tau;                 /* [0, 1] */
+    double ent_coef;            /* the fixed alpha (finite, >= 0); read when auto_ent_coef == 0 */
+    double target_entropy;      /* finite; stable-baselines3's default is -act_dim */
+    double beta1;               /* [0, 1) */
+    double beta2;               /* [0, 1) */
+    double eps;                 /* > 0 */
+    int32_t auto_ent_coef;      /* != 0: alpha = exp(log_alpha) and log_alpha is trained */
+    int32_t deterministic;      /* xarm_sac_act: != 0: action = tanh(mean), no noise is drawn, calls is not advanced */
+} xarm_sac_params;              /* 80 bytes */
+typedef struct xarm_sac_weights {
+    const float *actor[6];      /* W1 [64, D], b1 [64], W2 [64, 64], b2 [64], W3 [2 A, 64], b3 [2 A] */
+    const float *q1[6];         /* W1 [64, D + A], b1, W2, b2, W3 [1, 64], b3 [1] */
+    const float *q2[6];
+    const float *q1_target[6];
+    const float *q2_target[6];
+    const float *log_alpha;     /* [1] */
+} xarm_sac_weights;             /* 31 device pointers */
+/* *bytes = size of `workspace` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_sac_workspace_bytes(const xarm_sac_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: NULL layout / params / weights, batch_size < 0, obs_dim < 1, act_dim outside [1, XARM_SAC_MAX_ACT],
+ * obs_dim + act_dim > XARM_POLICY_MAX_DIM, hidden != XARM_POLICY_HIDDEN, row_offset < 0, or with batch_size > 0 a NULL or misaligned
+ * actor tensor, a NULL obs or out_action, a NULL calls with deterministic == 0. */
+int xarm_sac_act(const xarm_sac_layout *layout, const xarm_sac_params *params, const xarm_sac_weights *weights, int64_t *calls_i64,
+                 const float *obs, float *out_action, float *out_logp /* may be NULL */, void *stream);
+/* XARM_E_INVALID: everything the layout check of xarm_sac_act refuses, NULL exp_avg / exp_avg_sq, gamma or tau outside [0, 1], lr < 0,
+ * an ent_coef that is not finite and >= 0, a target_entropy that is not finite, beta1 or beta2 outside [0, 1), eps <= 0, or with
+ * batch_size > 0 a NULL weight tensor, a NULL exp_avg / exp_avg_sq tensor of actor, q1, q2 or log_alpha, a misaligned b1 / W2 / b2 /
+ * W3, a NULL step_i64 / obs / next_obs / action / reward / done, a NULL or not 16-byte aligned workspace. */
+int xarm_sac_update(const xarm_sac_layout *layout, const xarm_sac_params *params, const xarm_sac_weights *weights,
+                    const xarm_sac_weights *exp_avg, const xarm_sac_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *next_obs, const float *action, const float *reward, const float *done,
+                    const float *use /* may be NULL */, const float *noise_pi /* may be NULL */,
+                    const float *noise_next /* may be NULL */, void *workspace, float *out_grad /* may be NULL */,
+                    float *out_dqda /* may be NULL */, float *out_target /* may be NULL */, float *out_stats /* may be NULL */,
+                    void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
