@@ -23,7 +23,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
            "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update",
-           "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update"]
+           "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
+           "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -138,6 +139,21 @@ class XarmSACWeights(C.Structure):
     _fields_ = [(k, C.c_void_p * 6) for k in SAC_TOWERS] + [("log_alpha", C.c_void_p)]
 
 
+SACW_MAX_LAYERS = 3         # XARM_SACW_MAX_LAYERS
+SACW_WIDTHS = (64, 128, 192, 256)
+SACW_ACTIVATIONS = {"tanh": 0, "relu": 1}   # XARM_SACW_TANH, XARM_SACW_RELU
+
+
+class XarmSACWLayout(C.Structure):
+    """include/xarm_hip.h xarm_sacw_layout (32 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("batch_size", "obs_dim", "act_dim", "hidden", "n_hidden", "activation")] + [("row_offset", C.c_int64)]
+
+
+class XarmSACWWeights(C.Structure):
+    """include/xarm_hip.h xarm_sacw_weights (41 device pointers): five towers of W1, b1, ..., W_out, b_out (eight slots) and log_alpha"""
+    _fields_ = [(k, C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))) for k in SAC_TOWERS] + [("log_alpha", C.c_void_p)]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -202,6 +218,10 @@ def load(path=None):
     L.xarm_sac_workspace_bytes.argtypes = [sl, C.POINTER(C.c_int64)]
     L.xarm_sac_act.argtypes = [sl, sp, sw] + [vp] * 5
     L.xarm_sac_update.argtypes = [sl, sp, sw, sw, sw] + [vp] * 15
+    wl, ww = C.POINTER(XarmSACWLayout), C.POINTER(XarmSACWWeights)
+    L.xarm_sacw_workspace_bytes.argtypes = [wl, C.POINTER(C.c_int64)]
+    L.xarm_sacw_act.argtypes = [wl, sp, ww] + [vp] * 6
+    L.xarm_sacw_update.argtypes = [wl, sp, ww, ww, ww] + [vp] * 16
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

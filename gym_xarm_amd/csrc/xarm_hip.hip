@@ -37,6 +37,7 @@
 #include "xarm_a2c_core.h"
 #include "xarm_ppo_core.h"
 #include "xarm_sac_core.h"
+#include "xarm_sacw_core.h"
 
 using namespace xd;
 
@@ -1142,6 +1143,62 @@ int xarm_sac_update(const xarm_sac_layout *layout, const xarm_sac_params *params
     d.out_grad = out_grad; d.out_dqda = out_dqda; d.out_target = out_target; d.out_stats = out_stats;
     const int le = xsac::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sac_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ wide SAC update (xarm_k_sacw.hip)
+int xarm_sacw_workspace_bytes(const xarm_sacw_layout *layout, int64_t *bytes) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sacw_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sacw_workspace_bytes: NULL pointer");
+    xsacw::Dev d = {};
+    xsacw::fill_shape(d.s, layout);
+    *bytes = xsacw::fill_work(d, nullptr);
+    return XARM_OK;
+}
+
+int xarm_sacw_act(const xarm_sacw_layout *layout, const xarm_sac_params *params, const xarm_sacw_weights *weights, int64_t *calls_i64,
+                  const float *obs, void *workspace, float *out_action, float *out_logp, void *stream) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sacw_act: %s", why);
+    if (!params) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sacw_act: params is NULL");
+    if (!weights) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sacw_act: weights is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xsacw::act_pointer_error(layout, params, weights, calls_i64, obs, workspace, out_action))
+        return fail(nullptr, XARM_E_INVALID, "xarm_sacw_act: %s", why);
+    xsacw::Dev d = {};
+    xsacw::fill_shape(d.s, layout);
+    d.h.seed = params->seed;
+    d.h.deterministic = params->deterministic != 0;
+    for (int i = 0; i < d.s.tp; i++) d.w[i] = const_cast<float *>(weights->actor[i]);
+    xsacw::fill_work_act(d, workspace);
+    d.calls = calls_i64; d.obs = obs; d.out_action = out_action; d.out_logp = out_logp;
+    const int le = xsacw::launch_act(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sacw_act: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *params, const xarm_sacw_weights *weights,
+                     const xarm_sacw_weights *exp_avg, const xarm_sacw_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                     const float *next_obs, const float *action, const float *reward, const float *done, const float *use,
+                     const float *noise_pi, const float *noise_next, void *workspace, float *out_grad, float *out_dqda, float *out_target,
+                     float *out_stats, float *out_q, void *stream) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_sacw_update: %s", why);
+    if (const char *why = xsac::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_sacw_update: %s", why);
+    if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_sacw_update: weights / exp_avg / exp_avg_sq is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xsacw::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, next_obs, action, reward, done, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_sacw_update: %s", why);
+    xsacw::Dev d = {};
+    xsacw::fill_shape(d.s, layout);
+    xsac::fill_hyper(d.h, params);
+    xsacw::tensors_of(d.s, weights, d.w, d.tq);
+    xsacw::tensors_of(d.s, exp_avg, d.m, nullptr);
+    xsacw::tensors_of(d.s, exp_avg_sq, d.v, nullptr);
+    xsacw::fill_work(d, workspace);
+    d.step = step_i64;
+    d.obs = obs; d.next_obs = next_obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.noise_pi = noise_pi; d.noise_next = noise_next;
+    d.out_grad = out_grad; d.out_dqda = out_dqda; d.out_target = out_target; d.out_stats = out_stats; d.out_q = out_q;
+    const int le = xsacw::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sacw_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -6,8 +6,10 @@ it steps the batched env with the actor, stores every transition in a HER buffer
 HIP kernels on the module's own parameters (gym_xarm_amd/device_sac.py DeviceSAC); the torch block stays the default and
 the checker.
 
-The networks are the project's 64-64 tanh shape (`policy_kwargs=dict(net_arch=[64, 64], activation_fn=nn.Tanh)` in SB3's terms).  Out
-of scope: ReLU, wider nets such as the reference's [256, 256, 256], `use_sde`, `n_critics != 2`.
+The networks default to the project's 64-64 tanh shape (`policy_kwargs=dict(net_arch=[64, 64], activation_fn=nn.Tanh)` in SB3's terms);
+`net_arch` and `activation` ("tanh" or "relu") build any other, the reference's `net_arch=[256, 256, 256]` with SB3's ReLU among them.  The
+torch block runs every shape; the device update runs equal widths of 64, 128, 192 or 256 units in two or three hidden layers (DESIGN.md
+24).  Out of scope: `use_sde`, `n_critics != 2`.
 
   python -m gym_xarm_amd.train --algo sac --env XarmReach-v0 --num-envs 256 --updates 2000 --reward-type sparse --device-update
 """
@@ -23,19 +25,33 @@ import torch.nn as nn
 LOG_STD_MIN, LOG_STD_MAX, SQUASH_EPS = -20.0, 2.0, 1e-6
 
 
-def _tower(n_in, n_out):
-    return nn.Sequential(nn.Linear(n_in, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, n_out))
+ACTIVATIONS = {"tanh": nn.Tanh, "relu": nn.ReLU}
+
+
+def _tower(n_in, n_out, net_arch=(64, 64), activation="tanh"):
+    layers, last = [], n_in
+    for width in net_arch:
+        layers += [nn.Linear(last, width), ACTIVATIONS[activation]()]
+        last = width
+    return nn.Sequential(*layers, nn.Linear(last, n_out))
 
 
 class SacPolicy(nn.Module):
-    """SB3's SAC 'MlpPolicy' with net_arch [64, 64] and tanh: a squashed-Gaussian actor D -> 64 -> 64 -> 2A (rows 0 .. A-1 of the last
-    layer the mean, A .. 2A-1 log_std), two critics and their targets D + A -> 64 -> 64 -> 1, and log_alpha."""
+    """SB3's SAC 'MlpPolicy': a squashed-Gaussian actor D -> net_arch -> 2A (rows 0 .. A-1 of the last layer the mean, A .. 2A-1
+    log_std), two critics and their targets D + A -> net_arch -> 1, and log_alpha.  net_arch: the hidden widths (default (64, 64));
+    activation: "tanh" (default) or "relu" (SB3's own default for SAC).  Both are kept as attributes."""
 
-    def __init__(self, obs_dim, act_dim):
+    def __init__(self, obs_dim, act_dim, net_arch=(64, 64), activation="tanh"):
         super().__init__()
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-        self.actor = _tower(obs_dim, 2 * act_dim)
-        self.q1, self.q2 = _tower(obs_dim + act_dim, 1), _tower(obs_dim + act_dim, 1)
+        self.net_arch, self.activation = tuple(int(n) for n in net_arch), str(activation)
+        if not self.net_arch or min(self.net_arch) < 1:
+            raise ValueError("net_arch must name at least one hidden layer of at least one unit")
+        if self.activation not in ACTIVATIONS:
+            raise ValueError("activation must be 'tanh' or 'relu', not %r" % (activation,))
+        tower = lambda n_in, n_out: _tower(n_in, n_out, self.net_arch, self.activation)
+        self.actor = tower(obs_dim, 2 * act_dim)
+        self.q1, self.q2 = tower(obs_dim + act_dim, 1), tower(obs_dim + act_dim, 1)
         self.q1_target, self.q2_target = copy.deepcopy(self.q1), copy.deepcopy(self.q2)
         for p in list(self.q1_target.parameters()) + list(self.q2_target.parameters()):
             p.requires_grad_(False)
@@ -138,13 +154,16 @@ def normalized_batch(venv, s):
 
 def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
               lr=1e-3, tau=0.005, ent_coef="auto", target_entropy=None, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None,
-              log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None):
+              log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None,
+              net_arch=None, activation=None):
     """SAC + HER on a batched goal env.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
     2 x max_episode_steps, so that closed episodes exist) every `train_freq`-th step runs `gradient_steps` SAC steps on `batch_size`
     relabelled rows.  Observations are normalised at sample time with the running statistics; rewards stay raw.
     device_update: the rollout action and the SAC step in HIP kernels (DeviceSAC).  device_normalize: DeviceVecNormalize (statistics,
     Monitor and - with device_update - the sample's normalisation in HIP kernels); with both on a GPU env an iteration reads nothing
     back outside logging.  log_dir, check_freq: Monitor CSV, best-model checkpoints and the final statistics as in train().
+    net_arch, activation: SacPolicy's (None: 64-64 tanh); a best-model checkpoint of another shape carries both beside the state_dict
+    (`load_checkpoint` rebuilds the module).
     Returns (model, venv, hist)."""
     from .her import DeviceHerReplayBuffer, HerReplayBuffer
     from .train import EpisodeMonitor, SaveOnBestTrainingRewardCallback, VecNormalize
@@ -168,11 +187,11 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     Buffer = DeviceHerReplayBuffer if dev.type == "cuda" else HerReplayBuffer
     buffer = Buffer(env, horizon=horizon, n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=seed)
-    model = SacPolicy(venv.dim, act_dim).to(dev)
+    model = SacPolicy(venv.dim, act_dim, (64, 64) if net_arch is None else net_arch, "tanh" if activation is None else activation).to(dev)
     if device_update:
         from .device_sac import DeviceSAC
         dsac = DeviceSAC(model, batch_size, gamma=gamma, lr=lr, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, seed=seed,
-                         row_offset=int(getattr(env, "_env_id_offset", 0)))
+                         row_offset=int(getattr(env, "_env_id_offset", 0)), act_rows=num_envs)
         act_out = {"action": torch.empty(num_envs, act_dim, device=dev)}
         sample = buffer.alloc_out(batch_size)
     else:
@@ -238,3 +257,20 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
         torch.cuda.synchronize()
     env.close()
     return model, venv, hist
+
+
+def load_checkpoint(path):
+    """(SacPolicy, vecnormalize state) of a checkpoint written by train_sac (`best_model.safetensors`, train.save_model): the tensors are
+    `policy.<state_dict key>` and `vecnormalize.<key>`; the file's metadata holds `net_arch` ("256,256,256") and `activation`, from which
+    the module is rebuilt before its state_dict is loaded (a file without them is the 64-64 tanh shape); obs_dim and act_dim are read off
+    the actor's first and last layer"""
+    from safetensors import safe_open
+    from safetensors.torch import load_file
+    with safe_open(path, framework="pt") as f:
+        meta = f.metadata() or {}
+    sd = load_file(path)
+    pol = {k[len("policy."):]: v for k, v in sd.items() if k.startswith("policy.")}
+    arch = tuple(int(n) for n in meta["net_arch"].split(",")) if "net_arch" in meta else (64, 64)
+    model = SacPolicy(pol["actor.0.weight"].shape[1], pol["actor.%d.bias" % (2 * len(arch))].shape[0] // 2, arch, meta.get("activation", "tanh"))
+    model.load_state_dict(pol)
+    return model, {k[len("vecnormalize."):]: v for k, v in sd.items() if k.startswith("vecnormalize.")}

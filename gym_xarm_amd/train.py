@@ -218,7 +218,12 @@ def save_model(path, model, venv):
     from safetensors.torch import save_file
     sd = {"policy." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
     sd.update({"vecnormalize." + k: v.detach().cpu().contiguous() for k, v in venv.state_dict().items()})
-    save_file(sd, path)
+    # a module that records its shape (sac.SacPolicy) has it written beside the tensors, in the file's metadata: the tensors' keys are
+    # the state_dict's for every shape, and sac.load_checkpoint rebuilds the module from the two entries
+    meta = None
+    if hasattr(model, "net_arch") and hasattr(model, "activation"):
+        meta = {"net_arch": ",".join(str(int(n)) for n in model.net_arch), "activation": str(model.activation)}
+    save_file(sd, path, metadata=meta)
 
 
 def load_model(path, model, venv):
@@ -407,7 +412,7 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     return model, venv, hist
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="XarmReach-v0")
     ap.add_argument("--num-envs", type=int, default=4096)
@@ -427,7 +432,9 @@ def main():
     ap.add_argument("--n-epochs", type=int, default=4, help="ppo: passes over a rollout")
     ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout); sac: rows per step (256)")
     ap.add_argument("--gradient-steps", type=int, default=1, help="sac: SAC steps per training env step")
-    args = ap.parse_args()
+    ap.add_argument("--net-arch", type=int, nargs="+", default=None, help="sac: hidden widths (default 64 64; the reference's sparse branch: 256 256 256)")
+    ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="sac: tanh (default) or relu (stable-baselines3's SAC default)")
+    args = ap.parse_args(argv)
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
@@ -435,7 +442,8 @@ def main():
         from . import sac
         model, venv, hist = sac.train_sac(args.env, num_envs=args.num_envs, steps=args.updates, batch_size=args.batch_size or 256,
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
-                                          device_update=args.device_update, device_normalize=args.device_normalize)
+                                          device_update=args.device_update, device_normalize=args.device_normalize,
+                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation)
         if args.save:
             save_model(args.save, model, venv)
         return

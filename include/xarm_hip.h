@@ -638,6 +638,54 @@ int xarm_sac_update(const xarm_sac_layout *layout, const xarm_sac_params *params
                     float *out_dqda /* may be NULL */, float *out_target /* may be NULL */, float *out_stats /* may be NULL */,
                     void *stream);
 
+/* ---- wide device-resident SAC (gym_xarm_amd/csrc/xarm_sacw_core.h, xarm_k_sacw.hip): the step of xarm_sac_update and
+ * the act call of xarm_sac_act for equal-width towers of n_hidden = 2 or 3 hidden layers of hidden = 64, 128, 192 or 256 units, tanh
+ * or ReLU - stable-baselines3's `policy_kwargs=dict(net_arch=[256, 256, 256])` among them.  Arguments and semantics are xarm_sac_*'s
+ * with these changes: the layout names hidden, n_hidden and activation; a tower is 2 (n_hidden + 1) pointers W1, b1, ..., W_out, b_out
+ * (nn.Linear's [out, in] layout) in arrays sized for n_hidden = 3, the unused tail ignored; xarm_sacw_act takes a workspace too (the
+ * activations of a layer-by-layer forward live there); xarm_sacw_update has one more optional output, out_q [2, B] = q1 and q2 at
+ * obs | action as the critic stage computes them.  out_grad [P] holds the actor's 2 (n_hidden + 1) tensors, q1's, q2's, log_alpha.
+ * The dense work is a chain of per-layer GEMM launches on v_mfma_f32_32x32x2_f32 - 6 n_hidden + 11 launches per step, n_hidden + 2 (+ the
+ * tick) per act call, a function of n_hidden alone - with no allocation, no host read, no atomics and no side stream.  Sums over rows
+ * run in a fixed order (float32 within one of at most 16 contiguous row ranges, float64 across them): the same inputs give the same
+ * bits.  Out of scope: unequal widths, n_critics != 2, use_sde.  batch_size == 0 launches nothing. */
+#define XARM_SACW_MAX_LAYERS 3    /* n_hidden is 2 or 3 */
+#define XARM_SACW_MAX_HIDDEN 256  /* hidden is 64, 128, 192 or 256 */
+#define XARM_SACW_TANH 0
+#define XARM_SACW_RELU 1
+typedef struct xarm_sacw_layout {
+    int32_t batch_size;         /* B >= 0: rows of the call */
+    int32_t obs_dim;            /* D >= 1, D + act_dim <= XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_SAC_MAX_ACT */
+    int32_t hidden;             /* 64, 128, 192 or 256 */
+    int32_t n_hidden;           /* 2 or 3 */
+    int32_t activation;         /* XARM_SACW_TANH or XARM_SACW_RELU */
+    int64_t row_offset;         /* xarm_sacw_act: global index of row 0 (>= 0) */
+} xarm_sacw_layout;             /* 32 bytes */
+typedef struct xarm_sacw_weights {
+    const float *actor[2 * (XARM_SACW_MAX_LAYERS + 1)];     /* W1 [H, D], b1 [H], W2 [H, H], b2 [H], (W3 [H, H], b3 [H],) W_out [2 A, H], b_out [2 A] */
+    const float *q1[2 * (XARM_SACW_MAX_LAYERS + 1)];        /* W1 [H, D + A], b1, ..., W_out [1, H], b_out [1] */
+    const float *q2[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *q1_target[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *q2_target[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *log_alpha;     /* [1] */
+} xarm_sacw_weights;            /* 41 device pointers */
+/* *bytes = size of `workspace` for this layout (of either call).  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_sacw_workspace_bytes(const xarm_sacw_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: what xarm_sac_act refuses, with hidden outside {64, 128, 192, 256}, n_hidden outside {2, 3} or activation outside
+ * {XARM_SACW_TANH, XARM_SACW_RELU} in place of hidden != 64; with batch_size > 0 a NULL actor tensor, a tensor from b1 to W_out that is
+ * not 16-byte aligned, a NULL or not 16-byte aligned workspace. */
+int xarm_sacw_act(const xarm_sacw_layout *layout, const xarm_sac_params *params, const xarm_sacw_weights *weights, int64_t *calls_i64,
+                  const float *obs, void *workspace, float *out_action, float *out_logp /* may be NULL */, void *stream);
+/* XARM_E_INVALID: what xarm_sac_update refuses, with the layout check above. */
+int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *params, const xarm_sacw_weights *weights,
+                     const xarm_sacw_weights *exp_avg, const xarm_sacw_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                     const float *next_obs, const float *action, const float *reward, const float *done,
+                     const float *use /* may be NULL */, const float *noise_pi /* may be NULL */,
+                     const float *noise_next /* may be NULL */, void *workspace, float *out_grad /* may be NULL */,
+                     float *out_dqda /* may be NULL */, float *out_target /* may be NULL */, float *out_stats /* may be NULL */,
+                     float *out_q /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
