@@ -12,7 +12,7 @@ UNITS = ["xarm_hip.hip", "xarm_k_pnp.hip", "xarm_k_pnp_coop.hip", "xarm_k_reach.
          "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip", "xarm_k_policy.hip", "xarm_k_a2c.hip", "xarm_k_ppo.hip", "xarm_k_sac.hip", "xarm_k_sacw.hip"]
 HEADERS = ["xarm_dev.h", "xarm_core.h", "xarm7_pd_model.h", "xarm_reach_core.h", "xarm7_reach_model.h", "xarm_handover_core.h", "xarm_handover2_core.h",
            "xarm_stack_core.h", "xarm_rearrange_core.h", "xarm_cubes_dev.h", "xarm_coop_core.h", "xarm_reach_coop_core.h", "xarm_handover_coop_core.h", "xarm_render_core.h",
-           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h", "xarm_policy_core.h", "xarm_a2c_core.h", "xarm_grad_tile.h", "xarm_ppo_core.h", "xarm_sac_core.h", "xarm_sacw_core.h"]
+           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h", "xarm_policy_core.h", "xarm_opt_core.h", "xarm_a2c_core.h", "xarm_grad_tile.h", "xarm_ppo_core.h", "xarm_sac_core.h", "xarm_sacw_core.h"]
 SOURCES = UNITS + HEADERS
 # per-unit extra flags.  Tried and not shipped: "-ffp-contract=on" for xarm_k_pnp.hip / xarm_k_handover.hip (fused multiply-adds
 # only where the source writes them, so that k_step_fast / k_ho_step_fast compute the BITS of k_step / k_ho_step on every env
@@ -31,6 +31,7 @@ SOURCES = UNITS + HEADERS
 # unit (csrc/xarm_ppo_core.h) shares the A2C unit's tile (csrc/xarm_grad_tile.h) and is built the same way, and so is the SAC update
 # unit (csrc/xarm_sac_core.h): its rows - a, logp, y, dq/da - are the host build's bits.  The wide SAC unit (csrc/xarm_sacw_core.h) runs
 # its GEMMs as f32 MFMA chains in k order and everything else through the same spelled-out functions: all it writes is the host build's bits.
+# What follows the gradient in the four learners - slice sums, n_use, the clip, RMSprop, Adam - is csrc/xarm_opt_core.h, under the same flag in every one.
 # "-DXC_SWEEP_COPY" for the cooperative Handover unit: xc::sweep_all keeps its one-set form there (csrc/xarm_coop_core.h).  The two-set
 # form is bit for bit the same arithmetic and what the PickAndPlace unit runs, but built into this unit it made an env's result
 # depend on the env that shares its wavefront (tests/test_edge_cases.py::test_an_env_does_not_depend_on_its_batch, Handover, batch

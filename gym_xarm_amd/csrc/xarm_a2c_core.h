@@ -15,14 +15,14 @@
 //   backward  d2 = (W3^T d3) (1 - h2^2), d1 = (W2^T d2) (1 - h1^2); dW = sum_rows d (x) input, db = sum_rows d
 //   flat      the 13 tensors one after the other in xarm_policy_weights' order: P floats
 //   gradient  g = (float)(sum / n_use), n_use = max(sum use, 1); log_std: - ent_coef on top
-//   clip      norm = (float) sqrt(sum (double) g^2); g *= min(1, max_grad_norm / (norm + 1e-6))
-//   RMSprop   sq = alpha sq + (1 - alpha) g g; p = p - lr (g / (sqrt(sq) + eps))
+//   clip      norm = (float) sqrt(sum (double) g^2); then xopt::clip_coef and xopt::rmsprop (xarm_opt_core.h)
 #pragma once
 #include <stdint.h>
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
 #include <vector>
 #endif
 #include "xarm_policy_core.h"
+#include "xarm_opt_core.h"
 
 namespace xa2c {
 
@@ -45,7 +45,8 @@ struct Shape {
 };
 
 struct Hyper {
-    float gamma, lr, alpha, one_m_alpha, eps, vf2, max_norm;
+    float gamma, vf2, max_norm;
+    xopt::RmsProp rms;
     double ent_coef;
 };
 
@@ -113,8 +114,8 @@ inline void fill_shape(Shape &s, const xarm_a2c_layout *l) {
 }
 
 inline void fill_hyper(Hyper &h, const xarm_a2c_params *p) {
-    h.gamma = (float)p->gamma; h.lr = (float)p->lr; h.alpha = (float)p->alpha; h.one_m_alpha = (float)(1.0 - p->alpha); h.eps = (float)p->eps;
-    h.vf2 = (float)(2.0 * p->vf_coef); h.max_norm = (float)p->max_grad_norm; h.ent_coef = p->ent_coef;
+    h.gamma = (float)p->gamma; h.rms.lr = (float)p->lr; h.rms.alpha = (float)p->alpha; h.rms.one_m_alpha = (float)(1.0 - p->alpha);
+    h.rms.eps = (float)p->eps; h.vf2 = (float)(2.0 * p->vf_coef); h.max_norm = (float)p->max_grad_norm; h.ent_coef = p->ent_coef;
 }
 
 inline void fill_work(Work &k, const Shape &s) {
@@ -172,19 +173,6 @@ XARM_HD float pi_deltas(int A, const float *mean, const float *action, const flo
 }
 
 XARM_HD float value_delta(float vf2, float value, float ret, float use) { return vf2 * ((value - ret) * use); }
-
-XARM_HD float clip_coef(float norm, float max_norm) {
-    const float c = max_norm / (norm + 1e-6f);
-    return c < 1.0f ? c : 1.0f;
-}
-
-XARM_HD void rmsprop(const Hyper &h, float g, float &sq, float &p) {
-    const float gg = g * g;
-    const float s = h.alpha * sq + h.one_m_alpha * gg;
-    const float avg = __builtin_sqrtf(s) + h.eps;
-    sq = s;
-    p = p - h.lr * (g / avg);
-}
 
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
 // one row's backward through one tower (tensors t0 .. t0 + 5 of the flat order), added to the float32 chunk sums
@@ -261,17 +249,17 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         nuse += (double)u;
         if ((n + 1) % ROWS == 0 || n + 1 == s.N) flush();
     }
-    const double n_use = nuse > 1.0 ? nuse : 1.0;
+    const double n_use = xopt::n_use(nuse);
     std::vector<float> g((size_t)s.P);
-    double sum2 = 0.0, ent = 0.0;
+    double sum2 = 0.0;
     for (int64_t p = 0; p < s.P; p++) {
         double v = G[(size_t)p] / n_use;
         if (p >= s.off[12]) v -= h.ent_coef;
         g[(size_t)p] = (float)v;
         sum2 += (double)g[(size_t)p] * (double)g[(size_t)p];
     }
-    for (int c = 0; c < A; c++) ent += (double)log_std[c] + 0.5 + 0.918938533204672742;
-    const float norm = (float)__builtin_sqrt(sum2), coef = clip_coef(norm, h.max_norm);
+    const double ent = xopt::gaussian_entropy(log_std, A);
+    const float norm = (float)__builtin_sqrt(sum2), coef = xopt::clip_coef(norm, h.max_norm);
     if (out_grad)
         for (int64_t p = 0; p < s.P; p++) out_grad[p] = g[(size_t)p];
     if (out_stats) {
@@ -280,7 +268,7 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         out_stats[4] = (float)n_use;
     }
     for (int i = 0; i < NTENS; i++)
-        for (int64_t p = s.off[i]; p < s.off[i + 1]; p++) rmsprop(h, g[(size_t)p] * coef, sq[i][p - s.off[i]], w[i][p - s.off[i]]);
+        for (int64_t p = s.off[i]; p < s.off[i + 1]; p++) xopt::rmsprop(h.rms, g[(size_t)p] * coef, sq[i][p - s.off[i]], w[i][p - s.off[i]]);
 }
 #endif
 

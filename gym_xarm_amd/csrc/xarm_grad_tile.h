@@ -1,6 +1,8 @@
 // xarm_grad_tile.h - one 64-row tile of the two-tower backward, shared by the gradient kernels of the A2C update (xarm_k_a2c.hip,
 // DESIGN.md 21), of the PPO update (xarm_k_ppo.hip) and of the SAC update (xarm_k_sac.hip).  Device code
-// only; the units are built with -ffp-contract=off.
+// only; the units are built with -ffp-contract=off.  Next to the tile, what those kernels share around it: the tile's LDS declaration
+// (XARM_TILE_LDS), the launch of the instantiation that fits a width (XARM_TILE_LAUNCH), a workgroup's scalar record (store_scalars),
+// the block tree (block_sum) and the reduce / apply bodies of the A2C and PPO updates (reduce_block, norm_and_clip).
 //
 // A workgroup of 256 threads works on ONE tower.  Per tile, in LDS and transposed ([unit][row], stride 65: a lane per row and a lane
 // per unit both read without bank conflicts): the rows, h1 and h2 from the policy's chains (lane = row, wavefront w = units
@@ -39,6 +41,104 @@ template <class H> struct head_weight_grad<H, decltype((void)H::WEIGHT_GRAD)> { 
 struct TileLds {
     float *Xt, *H1t, *H2t, *D3t;       // [16 JW][LS], [HID][LS], [HID][LS], [MAX_ACT][LS]
 };
+
+// a tile kernel's LDS: the four arrays and L, their TileLds.  JW: 16 JW >= D columns in the tile
+#define XARM_TILE_LDS(JW)                                                                   \
+    __shared__ __attribute__((aligned(16))) float Xt[16 * JW * xa2c::LS];                   \
+    __shared__ __attribute__((aligned(16))) float H1t[xpol::HID * xa2c::LS];                \
+    __shared__ __attribute__((aligned(16))) float H2t[xpol::HID * xa2c::LS];                \
+    __shared__ __attribute__((aligned(16))) float D3t[xpol::MAX_ACT * xa2c::LS];            \
+    const xa2c::TileLds L = {Xt, H1t, H2t, D3t}
+
+// launch the instantiation of a tile kernel that holds W columns: KERNEL<JW><<<GRID, THREADS, 0, STREAM>>>(arguments)
+#define XARM_TILE_LAUNCH(W, KERNEL, GRID, STREAM, ...)                                                          \
+    do {                                                                                                        \
+        if ((W) <= 16) KERNEL<1><<<GRID, dim3(xa2c::THREADS), 0, STREAM>>>(__VA_ARGS__);                        \
+        else if ((W) <= 32) KERNEL<2><<<GRID, dim3(xa2c::THREADS), 0, STREAM>>>(__VA_ARGS__);                   \
+        else if ((W) <= 64) KERNEL<4><<<GRID, dim3(xa2c::THREADS), 0, STREAM>>>(__VA_ARGS__);                   \
+        else KERNEL<6><<<GRID, dim3(xa2c::THREADS), 0, STREAM>>>(__VA_ARGS__);                                  \
+    } while (0)
+
+// the lanes of wavefront 0 hold NS float64 sums each; slot k of this workgroup's record <- the lanes added in lane order.  lds: h1's tile
+template <int NS> __device__ __forceinline__ void store_scalars(float *lds, const double (&sums)[NS], double *record) {
+    const int t = threadIdx.x;
+    double *sc = (double *)lds;
+    static_assert(NS * 64 * sizeof(double) <= HID * LS * sizeof(float), "the scalars fit h1's tile");
+    __syncthreads();
+    if (t < 64) {
+#pragma unroll
+        for (int i = 0; i < NS; i++) sc[i * 64 + t] = sums[i];
+    }
+    __syncthreads();
+    if (t < NS) {
+        double sum = 0.0;
+        for (int l = 0; l < 64; l++) sum += sc[t * 64 + l];
+        record[t] = sum;
+    }
+}
+
+// ---- behind the gradient kernel, one thread per flat parameter in blocks of RED: what k_a2c_reduce / k_a2c_apply and k_ppo_reduce /
+// k_ppo_apply share.  scal: the policy tower's group records, nscal doubles each (slot 2: sum use, slots 3 + c: log_std_c's sums)
+
+// a block's sum of one double per thread: a fixed tree; every thread gets the sum
+__device__ __forceinline__ double block_sum(double *red, double x) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = x;
+    __syncthreads();
+    for (int s = RED / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__device__ __forceinline__ double groups_n_use(const Shape &s, const double *scal, int nscal) {
+    double nuse = 0.0;
+    for (int g = 0; g < s.G; g++) nuse += scal[(int64_t)g * nscal + 2];
+    return xopt::n_use(nuse);
+}
+
+// the gradient of flat parameter p: its groups' sums added in float64 in group order, / n_use, the entropy term on log_std
+__device__ __forceinline__ float param_grad(const Shape &s, const float *partial, const double *scal, int nscal, double n_use, double ent_coef, int64_t p) {
+    const bool ls = p >= s.off[12];
+    double sum = 0.0;
+    if (ls) {
+        const int c = (int)(p - s.off[12]);
+        for (int g = 0; g < s.G; g++) sum += scal[(int64_t)g * nscal + 3 + c];
+    } else {
+        const int tower = p >= s.off[6] ? 1 : 0;
+        sum = xopt::slice_sum(partial + (int64_t)tower * s.G * s.pstride + (p - (tower ? s.off[6] : 0)), s.G, s.pstride);
+    }
+    double v = sum / n_use;
+    if (ls) v -= ent_coef;
+    return (float)v;
+}
+
+// the reduce kernel's body: grad (and out_grad, nullable) of the block's parameters, the block's sum of squares to normpart; returns n_use
+__device__ __forceinline__ double reduce_block(const Shape &s, const float *partial, const double *scal, int nscal, double ent_coef, float *grad,
+                                               float *out_grad, double *red, double *normpart) {
+    const int64_t p = (int64_t)blockIdx.x * RED + threadIdx.x;
+    const double n_use = groups_n_use(s, scal, nscal);
+    double sq = 0.0;
+    if (p < s.P) {
+        const float gf = param_grad(s, partial, scal, nscal, n_use, ent_coef, p);
+        grad[p] = gf;
+        if (out_grad != nullptr) out_grad[p] = gf;
+        sq = (double)gf * (double)gf;
+    }
+    sq = block_sum(red, sq);
+    if (threadIdx.x == 0) normpart[blockIdx.x] = sq;
+    return n_use;
+}
+
+// the apply kernel's head: the norm from normpart in block order; returns the clip coefficient
+__device__ __forceinline__ float norm_and_clip(const Shape &s, const double *normpart, float max_norm, float &norm) {
+    double sum2 = 0.0;
+    for (int b = 0; b < s.NB; b++) sum2 += normpart[b];
+    norm = (float)__builtin_sqrt(sum2);
+    return xopt::clip_coef(norm, max_norm);
+}
 
 // JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
 template <int JW> struct TileGrad {

@@ -63,11 +63,7 @@ struct A2CHead {
 
 // JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
 template <int JW> __global__ __launch_bounds__(THREADS) void k_a2c_grad(Dev d) {
-    __shared__ __attribute__((aligned(16))) float Xt[16 * JW * LS];
-    __shared__ __attribute__((aligned(16))) float H1t[HID * LS];
-    __shared__ __attribute__((aligned(16))) float H2t[HID * LS];
-    __shared__ __attribute__((aligned(16))) float D3t[MAX_ACT * LS];
-    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    XARM_TILE_LDS(JW);
     const bool is_pi = blockIdx.y == 0;
     const Tower T = is_pi ? d.pi : d.vf;
     const int D = d.s.D, A = d.s.A, G = d.s.G, g = blockIdx.x, nout = is_pi ? A : 1;
@@ -79,7 +75,6 @@ template <int JW> __global__ __launch_bounds__(THREADS) void k_a2c_grad(Dev d) {
     for (int c = 0; c < MAX_ACT; c++) dls[c] = 0.0f;
     double ploss = 0.0, vloss = 0.0, nuse = 0.0;
     A2CHead head = {d, is_pi, 0, dls, ploss, vloss, nuse};
-    const TileLds L = {Xt, H1t, H2t, D3t};
 
     for (int64_t tile = g; tile < d.s.tiles; tile += G) {
         head.r0 = tile * ROWS;
@@ -87,65 +82,23 @@ template <int JW> __global__ __launch_bounds__(THREADS) void k_a2c_grad(Dev d) {
     }
     acc.store(d.partial + ((int64_t)blockIdx.y * G + g) * d.s.pstride, D, nout);
 
-    if (is_pi) {    // the scalars: lanes of wavefront 0 added in lane order (the loop above ended on a barrier)
-        double *sc = (double *)H1t;
-        static_assert((3 + MAX_ACT) * 64 * sizeof(double) <= HID * LS * sizeof(float) && 3 + MAX_ACT <= NSCAL, "the scalars fit h1's tile");
-        if (wv == 0) {
-            sc[r] = ploss; sc[64 + r] = vloss; sc[128 + r] = nuse;
+    if (is_pi) {    // the scalars: loss, value loss, use, the log_std terms
+        static_assert(3 + MAX_ACT <= NSCAL, "a record holds the scalars");
+        double sums[NSCAL] = {ploss, vloss, nuse};
 #pragma unroll
-            for (int c = 0; c < MAX_ACT; c++) sc[(3 + c) * 64 + r] = (double)dls[c];
-        }
-        __syncthreads();
-        if (t < NSCAL) {
-            double sum = 0.0;
-            if (t < 3 + MAX_ACT)
-                for (int l = 0; l < 64; l++) sum += sc[t * 64 + l];
-            d.scal[(int64_t)g * NSCAL + t] = sum;
-        }
+        for (int c = 0; c < MAX_ACT; c++) sums[3 + c] = (double)dls[c];
+        store_scalars<NSCAL>(H1t, sums, d.scal + (int64_t)g * NSCAL);
     }
-}
-
-__device__ __forceinline__ double n_use_of(const Dev &d) {
-    double nuse = 0.0;
-    for (int g = 0; g < d.s.G; g++) nuse += d.scal[(int64_t)g * NSCAL + 2];
-    return nuse > 1.0 ? nuse : 1.0;
 }
 
 __global__ __launch_bounds__(RED) void k_a2c_reduce(Dev d) {
     __shared__ double red[RED];
-    const int tid = threadIdx.x, G = d.s.G;
-    const int64_t p = (int64_t)blockIdx.x * RED + tid;
-    const double n_use = n_use_of(d);
-    double sq = 0.0;
-    if (p < d.s.P) {
-        double sum = 0.0;
-        const bool ls = p >= d.s.off[12];
-        if (ls) {
-            const int c = (int)(p - d.s.off[12]);
-            for (int g = 0; g < G; g++) sum += d.scal[(int64_t)g * NSCAL + 3 + c];
-        } else {
-            const int tower = p >= d.s.off[6] ? 1 : 0;
-            const float *base = d.partial + (int64_t)tower * G * d.s.pstride + (p - (tower ? d.s.off[6] : 0));
-            for (int g = 0; g < G; g++) sum += (double)base[(int64_t)g * d.s.pstride];
-        }
-        double v = sum / n_use;
-        if (ls) v -= d.h.ent_coef;
-        const float gf = (float)v;
-        d.grad[p] = gf;
-        if (d.out_grad != nullptr) d.out_grad[p] = gf;
-        sq = (double)gf * (double)gf;
-    }
-    red[tid] = sq;
-    __syncthreads();
-    for (int s = RED / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) d.normpart[blockIdx.x] = red[0];
-    if (blockIdx.x == 0 && tid == 0 && d.out_stats != nullptr) {
-        double ploss = 0.0, vloss = 0.0, ent = 0.0;
+    const int G = d.s.G;
+    const double n_use = reduce_block(d.s, d.partial, d.scal, NSCAL, d.h.ent_coef, d.grad, d.out_grad, red, d.normpart);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && d.out_stats != nullptr) {
+        double ploss = 0.0, vloss = 0.0;
         for (int g = 0; g < G; g++) { ploss += d.scal[(int64_t)g * NSCAL]; vloss += d.scal[(int64_t)g * NSCAL + 1]; }
-        for (int c = 0; c < d.s.A; c++) ent += (double)d.w[12][c] + 0.5 + 0.918938533204672742;
+        const double ent = xopt::gaussian_entropy(d.w[12], d.s.A);
         d.out_stats[0] = (float)(-ploss / n_use); d.out_stats[1] = (float)(vloss / n_use); d.out_stats[2] = (float)ent;
         d.out_stats[4] = (float)n_use; d.out_stats[5] = d.out_stats[6] = d.out_stats[7] = 0.0f;
     }
@@ -153,20 +106,16 @@ __global__ __launch_bounds__(RED) void k_a2c_reduce(Dev d) {
 
 __global__ __launch_bounds__(RED) void k_a2c_apply(Dev d) {
     const int64_t p = (int64_t)blockIdx.x * RED + threadIdx.x;
-    double sum2 = 0.0;
-    for (int b = 0; b < d.s.NB; b++) sum2 += d.normpart[b];
-    const float norm = (float)__builtin_sqrt(sum2), coef = clip_coef(norm, d.h.max_norm);
+    float norm;
+    const float coef = norm_and_clip(d.s, d.normpart, d.h.max_norm, norm);
     if (p == 0 && d.out_stats != nullptr) d.out_stats[3] = norm;
     if (p >= d.s.P) return;
-    float *wp = d.w[0], *sp = d.sq[0];
-    int64_t o = 0;
-#pragma unroll
-    for (int i = 1; i < NTENS; i++)
-        if (p >= d.s.off[i]) { wp = d.w[i]; sp = d.sq[i]; o = d.s.off[i]; }
-    float sq = sp[p - o], w = wp[p - o];
-    rmsprop(d.h, d.grad[p] * coef, sq, w);
-    sp[p - o] = sq;
-    wp[p - o] = w;
+    const int i = xopt::tensor_at<NTENS>(d.s.off, 0, p);
+    const int64_t e = p - d.s.off[i];
+    float sq = d.sq[i][e], w = d.w[i][e];
+    xopt::rmsprop(d.h.rms, d.grad[p] * coef, sq, w);
+    d.sq[i][e] = sq;
+    d.w[i][e] = w;
 }
 
 int launch_update(const Dev &d, void *stream) {
@@ -180,11 +129,8 @@ int launch_update(const Dev &d, void *stream) {
     le = xpol::launch_policy(a, nullptr, stream);
     if (le != 0) return le;
     k_a2c_returns<<<dim3((unsigned)((d.s.E + 255) / 256)), dim3(256), 0, s>>>(d);
-    const dim3 grid((unsigned)d.s.G, 2), block(THREADS);
-    if (d.s.D <= 16) k_a2c_grad<1><<<grid, block, 0, s>>>(d);
-    else if (d.s.D <= 32) k_a2c_grad<2><<<grid, block, 0, s>>>(d);
-    else if (d.s.D <= 64) k_a2c_grad<4><<<grid, block, 0, s>>>(d);
-    else k_a2c_grad<6><<<grid, block, 0, s>>>(d);
+    const dim3 grid((unsigned)d.s.G, 2);
+    XARM_TILE_LAUNCH(d.s.D, k_a2c_grad, grid, s, d);
     k_a2c_reduce<<<dim3((unsigned)d.s.NB), dim3(RED), 0, s>>>(d);
     k_a2c_apply<<<dim3((unsigned)d.s.NB), dim3(RED), 0, s>>>(d);
     return (int)hipGetLastError();

@@ -50,19 +50,6 @@ __global__ __launch_bounds__(256) void k_ppo_gae(Dev d) {
     }
 }
 
-// a block's sum of one double per thread: a fixed tree; every thread gets the sum
-__device__ __forceinline__ double block_sum(double *red, double x) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = x;
-    __syncthreads();
-    for (int s = RED / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(RED) void k_ppo_advstats(Dev d) {
     __shared__ double red[RED];
     const int tid = threadIdx.x;
@@ -77,8 +64,8 @@ __global__ __launch_bounds__(RED) void k_ppo_advstats(Dev d) {
         n += u;
         sa += (double)d.adv[r] * u;
     }
-    n = block_sum(red, n);
-    sa = block_sum(red, sa);
+    n = xa2c::block_sum(red, n);
+    sa = xa2c::block_sum(red, sa);
     const double mu = n > 0.0 ? sa / n : 0.0;
     for (int64_t i = tid; i < count; i += RED) {
         const int64_t r = row_of(d.perm[first + i], N);
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(RED) void k_ppo_advstats(Dev d) {
         const double u = d.use != nullptr ? (double)d.use[r] : 1.0, dd = (double)d.adv[r] - mu;
         sv += dd * dd * u;
     }
-    sv = block_sum(red, sv);
+    sv = xa2c::block_sum(red, sv);
     if (tid == 0) finish_stats(d.musig + (int64_t)blockIdx.x * NMS, n, mu, sv, d.h.normalize);
 }
 
@@ -98,7 +85,7 @@ struct PpoHead {
     const int *Rt;                      // LDS: the batch row of each tile slot, -1 for an empty one
     const double *ms;                   // the step's mu, sigma, normalise, n
     float (&dls)[MAX_ACT];
-    double (&sums)[5];                  // surrogate, value loss, use, kl, clipped
+    double (&sums)[NSCAL];              // the group's record: 0 surrogate, 1 value loss, 2 use, 19 kl, 20 clipped (3..18: dls, at the end)
     __device__ __forceinline__ int64_t row(int rr) const { return Rt[rr]; }
     __device__ __forceinline__ void deltas(int r, float *D3) {
         const int64_t n = Rt[r];
@@ -116,7 +103,7 @@ struct PpoHead {
             const float olp = d.old_logp != nullptr ? d.old_logp[n] : d.oldlp[n];
             const RowTerms t = surrogate(d.h, norm_adv(d.adv[n], ms), lp, olp, u);
             xa2c::pi_row<true>(A, D3, LS, act, d.w[12], t.q, D3, LS, dls);
-            sums[0] += (double)t.surr; sums[3] += (double)t.kl; sums[4] += (double)t.clipped;
+            sums[0] += (double)t.surr; sums[19] += (double)t.kl; sums[20] += (double)t.clipped;
             sums[2] += (double)u;
         } else {
             const float v = D3[0], rt = d.ret[n];
@@ -129,12 +116,9 @@ struct PpoHead {
 
 // JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
 template <int JW> __global__ __launch_bounds__(THREADS) void k_ppo_grad(Dev d, int step) {
-    __shared__ __attribute__((aligned(16))) float Xt[16 * JW * LS];
-    __shared__ __attribute__((aligned(16))) float H1t[HID * LS];
-    __shared__ __attribute__((aligned(16))) float H2t[HID * LS];
-    __shared__ __attribute__((aligned(16))) float D3t[MAX_ACT * LS];
+    XARM_TILE_LDS(JW);
     __shared__ int Rt[ROWS];
-    const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int t = threadIdx.x;
     const bool is_pi = blockIdx.y == 0;
     const Tower T = is_pi ? d.pi : d.vf;
     const xa2c::Shape &a = d.s.a;
@@ -148,9 +132,9 @@ template <int JW> __global__ __launch_bounds__(THREADS) void k_ppo_grad(Dev d, i
     float dls[MAX_ACT];
 #pragma unroll
     for (int c = 0; c < MAX_ACT; c++) dls[c] = 0.0f;
-    double sums[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    static_assert(3 + MAX_ACT <= 19 && 21 <= NSCAL, "a record holds the scalars");
+    double sums[NSCAL] = {};
     PpoHead head = {d, is_pi, Rt, d.musig + (int64_t)step * NMS, dls, sums};
-    const xa2c::TileLds L = {Xt, H1t, H2t, D3t};
 
     for (int64_t tile = g; tile < tiles; tile += G) {
         if (t < ROWS) {     // the gather: the tile's slots through perm (the previous tile ended on a barrier)
@@ -162,71 +146,28 @@ template <int JW> __global__ __launch_bounds__(THREADS) void k_ppo_grad(Dev d, i
     }
     acc.store(d.partial + ((int64_t)blockIdx.y * G + g) * a.pstride, D, nout);
 
-    // the scalars: lanes of wavefront 0 added in lane order (the loop above ended on a barrier; a workgroup without a tile meets none)
-    double *sc = (double *)H1t;
-    static_assert((5 + MAX_ACT) * 64 * sizeof(double) <= HID * LS * sizeof(float) && 21 <= NSCAL, "the scalars fit h1's tile");
-    if (wv == 0) {
+    // the scalars (a workgroup without a tile stores zeros)
 #pragma unroll
-        for (int i = 0; i < 5; i++) sc[i * 64 + r] = sums[i];
-#pragma unroll
-        for (int c = 0; c < MAX_ACT; c++) sc[(5 + c) * 64 + r] = (double)dls[c];
-    }
-    __syncthreads();
-    if (t < NSCAL) {
-        // slot t of the record <- LDS row: 0 surrogate, 1 value loss, 2 use, 3..18 log_std, 19 kl, 20 clipped
-        const int src = t < 3 ? t : (t < 3 + MAX_ACT ? t + 2 : (t == 19 ? 3 : (t == 20 ? 4 : -1)));
-        double sum = 0.0;
-        if (src >= 0)
-            for (int l = 0; l < 64; l++) sum += sc[src * 64 + l];
-        d.scal[((int64_t)blockIdx.y * G + g) * NSCAL + t] = sum;
-    }
+    for (int c = 0; c < MAX_ACT; c++) sums[3 + c] = (double)dls[c];
+    xa2c::store_scalars<NSCAL>(H1t, sums, d.scal + ((int64_t)blockIdx.y * G + g) * NSCAL);
 }
 
 __global__ __launch_bounds__(RED) void k_ppo_reduce(Dev d, int step) {
     __shared__ double red[RED];
     const xa2c::Shape &a = d.s.a;
-    const int tid = threadIdx.x, G = a.G;
-    const int64_t p = (int64_t)blockIdx.x * RED + tid;
-    double nuse = 0.0;
-    for (int g = 0; g < G; g++) nuse += d.scal[(int64_t)g * NSCAL + 2];
-    const double n_use = nuse > 1.0 ? nuse : 1.0;
-    double sq = 0.0;
-    if (p < a.P) {
-        double sum = 0.0;
-        const bool ls = p >= a.off[12];
-        if (ls) {
-            const int c = (int)(p - a.off[12]);
-            for (int g = 0; g < G; g++) sum += d.scal[(int64_t)g * NSCAL + 3 + c];
-        } else {
-            const int tower = p >= a.off[6] ? 1 : 0;
-            const float *base = d.partial + (int64_t)tower * G * a.pstride + (p - (tower ? a.off[6] : 0));
-            for (int g = 0; g < G; g++) sum += (double)base[(int64_t)g * a.pstride];
-        }
-        double v = sum / n_use;
-        if (ls) v -= d.h.ent_coef;
-        const float gf = (float)v;
-        d.grad[p] = gf;
-        if (step == 0 && d.out_grad != nullptr) d.out_grad[p] = gf;
-        sq = (double)gf * (double)gf;
-    }
-    red[tid] = sq;
-    __syncthreads();
-    for (int s = RED / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) d.normpart[blockIdx.x] = red[0];
-    if (blockIdx.x == 0 && tid == 0) {
+    const int G = a.G;
+    const double n_use = xa2c::reduce_block(a, d.partial, d.scal, NSCAL, d.h.ent_coef, d.grad, step == 0 ? d.out_grad : nullptr, red, d.normpart);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
         const int64_t t = d.step[0] + 1;
         d.step[0] = t;
-        adam_scalars(d.h, t, d.adam);
+        xopt::adam_scalars(d.h.adam, t, d.adam);
         if (d.out_stats != nullptr) {
-            double surr = 0.0, vloss = 0.0, kl = 0.0, clipped = 0.0, ent = 0.0;
+            double surr = 0.0, vloss = 0.0, kl = 0.0, clipped = 0.0;
             for (int g = 0; g < G; g++) {
                 const double *pi = d.scal + (int64_t)g * NSCAL, *vf = d.scal + ((int64_t)G + g) * NSCAL;
                 surr += pi[0]; kl += pi[19]; clipped += pi[20]; vloss += vf[1];
             }
-            for (int c = 0; c < a.A; c++) ent += (double)d.w[12][c] + 0.5 + 0.918938533204672742;
+            const double ent = xopt::gaussian_entropy(d.w[12], a.A);
             float *o = d.out_stats + (int64_t)step * 8;
             o[0] = (float)(-surr / n_use); o[1] = (float)(vloss / n_use); o[2] = (float)ent; o[4] = (float)n_use;
             o[5] = (float)(kl / n_use); o[6] = (float)(clipped / n_use); o[7] = 0.0f;
@@ -237,22 +178,18 @@ __global__ __launch_bounds__(RED) void k_ppo_reduce(Dev d, int step) {
 __global__ __launch_bounds__(RED) void k_ppo_apply(Dev d, int step) {
     const xa2c::Shape &a = d.s.a;
     const int64_t p = (int64_t)blockIdx.x * RED + threadIdx.x;
-    double sum2 = 0.0;
-    for (int b = 0; b < a.NB; b++) sum2 += d.normpart[b];
-    const float norm = (float)__builtin_sqrt(sum2), coef = xa2c::clip_coef(norm, d.h.max_norm);
+    float norm;
+    const float coef = xa2c::norm_and_clip(a, d.normpart, d.h.max_norm, norm);
     if (p == 0 && d.out_stats != nullptr) d.out_stats[(int64_t)step * 8 + 3] = norm;
     if (p >= a.P) return;
-    float *wp = d.w[0], *mp = d.m[0], *vp = d.v[0];
-    int64_t o = 0;
-#pragma unroll
-    for (int i = 1; i < NTENS; i++)
-        if (p >= a.off[i]) { wp = d.w[i]; mp = d.m[i]; vp = d.v[i]; o = a.off[i]; }
+    const int i = xopt::tensor_at<NTENS>(a.off, 0, p);
+    const int64_t e = p - a.off[i];
     const float sc[2] = {d.adam[0], d.adam[1]};
-    float m = mp[p - o], v = vp[p - o], w = wp[p - o];
-    adam(d.h, sc, d.grad[p] * coef, m, v, w);
-    mp[p - o] = m;
-    vp[p - o] = v;
-    wp[p - o] = w;
+    float m = d.m[i][e], v = d.v[i][e], w = d.w[i][e];
+    xopt::adam(d.h.adam, sc, d.grad[p] * coef, m, v, w);
+    d.m[i][e] = m;
+    d.v[i][e] = v;
+    d.w[i][e] = w;
 }
 
 int launch_update(const Dev &d, void *stream) {
@@ -268,12 +205,9 @@ int launch_update(const Dev &d, void *stream) {
     if (le != 0) return le;
     k_ppo_gae<<<dim3((unsigned)((sh.N + 255) / 256)), dim3(256), 0, s>>>(d);
     k_ppo_advstats<<<dim3((unsigned)d.s.S), dim3(RED), 0, s>>>(d);
-    const dim3 grid((unsigned)sh.G, 2), block(THREADS), rgrid((unsigned)sh.NB), rblock(RED);
+    const dim3 grid((unsigned)sh.G, 2), rgrid((unsigned)sh.NB), rblock(RED);
     for (int st = 0; st < (int)d.s.S; st++) {
-        if (sh.D <= 16) k_ppo_grad<1><<<grid, block, 0, s>>>(d, st);
-        else if (sh.D <= 32) k_ppo_grad<2><<<grid, block, 0, s>>>(d, st);
-        else if (sh.D <= 64) k_ppo_grad<4><<<grid, block, 0, s>>>(d, st);
-        else k_ppo_grad<6><<<grid, block, 0, s>>>(d, st);
+        XARM_TILE_LAUNCH(sh.D, k_ppo_grad, grid, s, d, st);
         k_ppo_reduce<<<rgrid, rblock, 0, s>>>(d, st);
         k_ppo_apply<<<rgrid, rblock, 0, s>>>(d, st);
     }

@@ -27,15 +27,8 @@ namespace xsac {
 
 using xa2c::LS;
 using xa2c::THREADS;
-using xa2c::TileLds;
+using xa2c::store_scalars;
 using xpol::MAX_ACT;
-
-#define XSAC_TILE_LDS(JW)                                                   \
-    __shared__ __attribute__((aligned(16))) float Xt[16 * JW * LS];         \
-    __shared__ __attribute__((aligned(16))) float H1t[HID * LS];            \
-    __shared__ __attribute__((aligned(16))) float H2t[HID * LS];            \
-    __shared__ __attribute__((aligned(16))) float D3t[MAX_ACT * LS];        \
-    const TileLds L = {Xt, H1t, H2t, D3t}
 
 // rows r0 .. r0 + 63 of x [B, W] to Xt's columns 0 .. W - 1, zeros in the slots past B and in the columns W .. 16 JW - 1
 template <int JW> __device__ __forceinline__ void load_rows(float *Xt, const float *x, int W, int64_t r0, int64_t B) {
@@ -62,39 +55,21 @@ __device__ __forceinline__ void row_noise(const Dev &d, const float *given, int6
     }
 }
 
-// the lanes of wavefront 0 hold NS float64 sums each; slot k of this workgroup's record <- the lanes added in lane order
-template <int NS> __device__ __forceinline__ void store_scalars(float *lds, const double (&sums)[NS], double *record) {
-    const int t = threadIdx.x;
-    double *sc = (double *)lds;
-    static_assert(NS * 64 * sizeof(double) <= HID * LS * sizeof(float), "the scalars fit h1's tile");
-    __syncthreads();
-    if (t < 64) {
-#pragma unroll
-        for (int i = 0; i < NS; i++) sc[i * 64 + t] = sums[i];
-    }
-    __syncthreads();
-    if (t < NS) {
-        double sum = 0.0;
-        for (int l = 0; l < 64; l++) sum += sc[t * 64 + l];
-        record[t] = sum;
-    }
-}
-
 __device__ __forceinline__ double n_use_of(const Dev &d) {
     double nuse = 0.0;
     for (int g = 0; g < d.s.G; g++) nuse += d.scal_rows[(int64_t)g * RS];
-    return nuse > 1.0 ? nuse : 1.0;
+    return xopt::n_use(nuse);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------ rows
 template <int JW> __global__ __launch_bounds__(THREADS) void k_sac_rows(Dev d) {
-    XSAC_TILE_LDS(JW);
+    XARM_TILE_LDS(JW);
     const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int D = d.s.D, A = d.s.A, Dq = d.s.Dq, G = d.s.G, g = blockIdx.x;
     const int64_t B = d.s.B, t0 = d.step[0];
     const float alpha = alpha_of(d.h, d.w[18]);
     if (g == 0 && t == 0) {
-        xppo::adam_scalars(d.h.adam, t0 + 1, d.hdr);
+        xopt::adam_scalars(d.h.adam, t0 + 1, d.hdr);
         d.hdr[2] = alpha;
         d.hdr[3] = 0.0f;
     }
@@ -176,7 +151,7 @@ struct CriticHead {
 };
 
 template <int JW> __global__ __launch_bounds__(THREADS) void k_sac_qgrad(Dev d) {
-    XSAC_TILE_LDS(JW);
+    XARM_TILE_LDS(JW);
     const int G = d.s.G, g = blockIdx.x;
     const Tower T = blockIdx.y == 0 ? d.q1 : d.q2;
     xa2c::TileGrad<JW> acc;
@@ -199,20 +174,13 @@ __global__ __launch_bounds__(RED) void k_sac_qapply(Dev d) {
     const double n_use = n_use_of(d);
     const int tower = p >= s.Pq ? 1 : 0;
     const int64_t local = p - tower * s.Pq;
-    const float *base = d.partial + (int64_t)tower * s.G * s.pstride + local;
-    double sum = 0.0;
-    for (int g = 0; g < s.G; g++) sum += (double)base[(int64_t)g * s.pstride];
-    const float gf = (float)(sum / n_use);
+    const float gf = (float)(xopt::slice_sum(d.partial + (int64_t)tower * s.G * s.pstride + local, s.G, s.pstride) / n_use);
     if (d.out_grad != nullptr) d.out_grad[s.Pa + p] = gf;
-    int i = 6 + 6 * tower;
-    int64_t o = s.off[i];
-#pragma unroll
-    for (int k = 1; k < 6; k++)
-        if (s.Pa + p >= s.off[6 + 6 * tower + k]) { i = 6 + 6 * tower + k; o = s.off[i]; }
-    const int64_t e = s.Pa + p - o;
+    const int i = xopt::tensor_at<6>(s.off, 6 + 6 * tower, s.Pa + p);
+    const int64_t e = s.Pa + p - s.off[i];
     const float sc[2] = {d.hdr[0], d.hdr[1]};
     float m = d.m[i][e], v = d.v[i][e], w = d.w[i][e];
-    xppo::adam(d.h.adam, sc, gf, m, v, w);
+    xopt::adam(d.h.adam, sc, gf, m, v, w);
     d.m[i][e] = m;
     d.v[i][e] = v;
     d.w[i][e] = w;
@@ -244,7 +212,7 @@ struct ActionGradHead {
 };
 
 template <int JW> __global__ __launch_bounds__(THREADS) void k_sac_dqda(Dev d) {
-    XSAC_TILE_LDS(JW);
+    XARM_TILE_LDS(JW);
     const int G = d.s.G, g = blockIdx.x;
     const Tower T = blockIdx.y == 0 ? d.q1 : d.q2;
     xa2c::TileGrad<JW> unused;
@@ -283,7 +251,7 @@ struct ActorHead {
 };
 
 template <int JW> __global__ __launch_bounds__(THREADS) void k_sac_pgrad(Dev d) {
-    XSAC_TILE_LDS(JW);
+    XARM_TILE_LDS(JW);
     const int G = d.s.G, g = blockIdx.x;
     xa2c::TileGrad<JW> acc;
     acc.zero();
@@ -306,21 +274,15 @@ __global__ __launch_bounds__(RED) void k_sac_papply(Dev d) {
     const double n_use = n_use_of(d);
     const float sc[2] = {d.hdr[0], d.hdr[1]};
     if (p < s.Pa) {
-        const float *base = d.partial + p;
-        double sum = 0.0;
-        for (int g = 0; g < G; g++) sum += (double)base[(int64_t)g * s.pstride];
-        const float gf = (float)(sum / n_use);
+        const float gf = (float)(xopt::slice_sum(d.partial + p, G, s.pstride) / n_use);
         if (d.out_grad != nullptr) d.out_grad[p] = gf;
-        int i = 0;
-        int64_t o = 0;
-#pragma unroll
-        for (int k = 1; k < 6; k++)
-            if (p >= s.off[k]) { i = k; o = s.off[k]; }
-        float m = d.m[i][p - o], v = d.v[i][p - o], w = d.w[i][p - o];
-        xppo::adam(d.h.adam, sc, gf, m, v, w);
-        d.m[i][p - o] = m;
-        d.v[i][p - o] = v;
-        d.w[i][p - o] = w;
+        const int i = xopt::tensor_at<6>(s.off, 0, p);
+        const int64_t e = p - s.off[i];
+        float m = d.m[i][e], v = d.v[i][e], w = d.w[i][e];
+        xopt::adam(d.h.adam, sc, gf, m, v, w);
+        d.m[i][e] = m;
+        d.v[i][e] = v;
+        d.w[i][e] = w;
         return;
     }
     double slp = 0.0, sent = 0.0, closs = 0.0, aloss = 0.0, sq = 0.0;
@@ -331,29 +293,13 @@ __global__ __launch_bounds__(RED) void k_sac_papply(Dev d) {
         aloss += d.scal_p[(int64_t)g * PS];
         sq += d.scal_p[(int64_t)g * PS + 1];
     }
-    const float log_alpha = d.w[18][0];
-    float gf = 0.0f;
-    if (d.h.auto_alpha) {
-        gf = (float)(-sent / n_use);
-        float m = d.m[18][0], v = d.v[18][0], w = log_alpha;
-        xppo::adam(d.h.adam, sc, gf, m, v, w);
-        d.m[18][0] = m;
-        d.v[18][0] = v;
-        d.w[18][0] = w;
-    }
-    if (d.out_grad != nullptr) d.out_grad[s.off[18]] = gf;
-    if (d.out_stats != nullptr) {
-        float *o = d.out_stats;
-        o[0] = (float)(0.5 * closs / n_use); o[1] = (float)(aloss / n_use);
-        o[2] = d.h.auto_alpha ? (float)(-(double)log_alpha * sent / n_use) : 0.0f; o[3] = d.hdr[2];
-        o[4] = (float)(slp / n_use); o[5] = (float)(sq / n_use); o[6] = (float)n_use; o[7] = 0.0f;
-    }
-    d.step[0] = d.step[0] + 1;
+    finish(d.h, sc, d.hdr[2], n_use, sent, closs, aloss, slp, sq, d.w[18], d.m[18], d.v[18],
+           d.out_grad != nullptr ? d.out_grad + s.off[18] : nullptr, d.out_stats, d.step);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- the act call
 template <int JW> __global__ __launch_bounds__(THREADS) void k_sac_act(Dev d) {
-    XSAC_TILE_LDS(JW);
+    XARM_TILE_LDS(JW);
     const int t = threadIdx.x, r = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), A = d.s.A;
     const int64_t r0 = (int64_t)blockIdx.x * ROWS, n = r0 + r;
     load_rows<JW>(Xt, d.obs, d.s.D, r0, d.s.B);
@@ -381,24 +327,15 @@ __global__ void k_sac_tick(int64_t *calls) {
     if (blockIdx.x == 0 && threadIdx.x == 0) calls[0] += 1;
 }
 
-// JW: 16 JW >= W columns in the tile
-#define XSAC_BY_WIDTH(W, KERNEL, GRID)                                           \
-    do {                                                                         \
-        if ((W) <= 16) KERNEL<1><<<GRID, dim3(THREADS), 0, s>>>(d);              \
-        else if ((W) <= 32) KERNEL<2><<<GRID, dim3(THREADS), 0, s>>>(d);         \
-        else if ((W) <= 64) KERNEL<4><<<GRID, dim3(THREADS), 0, s>>>(d);         \
-        else KERNEL<6><<<GRID, dim3(THREADS), 0, s>>>(d);                        \
-    } while (0)
-
 int launch_update(const Dev &d, void *stream) {
     const hipStream_t s = (hipStream_t)stream;
     const Shape &sh = d.s;
     const dim3 one((unsigned)sh.G), two((unsigned)sh.G, 2);
-    XSAC_BY_WIDTH(sh.Dq, k_sac_rows, one);
-    XSAC_BY_WIDTH(sh.Dq, k_sac_qgrad, two);
+    XARM_TILE_LAUNCH(sh.Dq, k_sac_rows, one, s, d);
+    XARM_TILE_LAUNCH(sh.Dq, k_sac_qgrad, two, s, d);
     k_sac_qapply<<<dim3((unsigned)sh.NBq), dim3(RED), 0, s>>>(d);
-    XSAC_BY_WIDTH(sh.Dq, k_sac_dqda, two);
-    XSAC_BY_WIDTH(sh.D, k_sac_pgrad, one);
+    XARM_TILE_LAUNCH(sh.Dq, k_sac_dqda, two, s, d);
+    XARM_TILE_LAUNCH(sh.D, k_sac_pgrad, one, s, d);
     k_sac_papply<<<dim3((unsigned)sh.NBp), dim3(RED), 0, s>>>(d);
     return (int)hipGetLastError();
 }
@@ -406,7 +343,7 @@ int launch_update(const Dev &d, void *stream) {
 int launch_act(const Dev &d, void *stream) {
     const hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)d.s.tiles);
-    XSAC_BY_WIDTH(d.s.D, k_sac_act, grid);
+    XARM_TILE_LAUNCH(d.s.D, k_sac_act, grid, s, d);
     if (!d.h.deterministic) k_sac_tick<<<dim3(1), dim3(1), 0, s>>>(d.calls);
     return (int)hipGetLastError();
 }

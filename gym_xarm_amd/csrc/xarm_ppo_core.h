@@ -20,8 +20,7 @@
 //              q = clipped ? 0 : -((A^ rho) use); from q on pi_row's deltas (dmean_c = q d_c iv_c, log_std_c: q (d_c d_c iv_c - 1));
 //              dvalue = 2 vf_coef ((value - ret) use); mean and value under the weights of the step
 //   gradient   g = (float)(sum / n_use), n_use = max(n, 1); log_std: - ent_coef on top; clip as in A2C
-//   Adam       t = ++step; m = m + (1 - b1)(g - m); v = b2 v + (1 - b2) g g; p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps);
-//              the powers by repeated squaring in float64 (ipow), the same operations in both builds
+//   Adam       t = ++step; xopt::adam_scalars and xopt::adam (xarm_opt_core.h)
 #pragma once
 #include <stdint.h>
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
@@ -50,8 +49,9 @@ struct Shape {
 };
 
 struct Hyper {
-    float gamma, gl, clip_lo, clip_hi, clip, b1, one_m_b1, b2, one_m_b2, eps, vf2, max_norm;
-    double lr, beta1, beta2, ent_coef;
+    float gamma, gl, clip_lo, clip_hi, clip, vf2, max_norm;
+    xopt::Adam adam;
+    double ent_coef;
     int normalize;
 };
 
@@ -82,9 +82,7 @@ inline const char *params_error(const xarm_ppo_params *p) {
     if (!(p->gamma >= 0.0 && p->gamma <= 1.0)) return "gamma must lie in [0, 1]";
     if (!(p->gae_lambda >= 0.0 && p->gae_lambda <= 1.0)) return "gae_lambda must lie in [0, 1]";
     if (!(p->clip_range > 0.0) || !(p->clip_range < 1e300)) return "clip_range must be finite and > 0";
-    if (!(p->lr >= 0.0) || !(p->lr < 1e300)) return "lr must be finite and >= 0";
-    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0) || !(p->beta2 >= 0.0 && p->beta2 < 1.0)) return "beta1 and beta2 must lie in [0, 1)";
-    if (!(p->eps > 0.0) || !(p->eps < 1e300)) return "eps must be finite and > 0";
+    if (const char *why = xopt::adam_error(p->lr, p->beta1, p->beta2, p->eps)) return why;
     if (!(p->max_grad_norm > 0.0)) return "max_grad_norm must be > 0";
     if (!(p->vf_coef > -1e300 && p->vf_coef < 1e300) || !(p->ent_coef > -1e300 && p->ent_coef < 1e300)) return "vf_coef and ent_coef must be finite";
     return nullptr;
@@ -124,9 +122,8 @@ inline void fill_shape(Shape &s, const xarm_ppo_layout *l) {
 inline void fill_hyper(Hyper &h, const xarm_ppo_params *p) {
     h.gamma = (float)p->gamma; h.gl = (float)(p->gamma * p->gae_lambda);
     h.clip = (float)p->clip_range; h.clip_lo = (float)(1.0 - p->clip_range); h.clip_hi = (float)(1.0 + p->clip_range);
-    h.b1 = (float)p->beta1; h.one_m_b1 = (float)(1.0 - p->beta1); h.b2 = (float)p->beta2; h.one_m_b2 = (float)(1.0 - p->beta2);
-    h.eps = (float)p->eps; h.vf2 = (float)(2.0 * p->vf_coef); h.max_norm = (float)p->max_grad_norm;
-    h.lr = p->lr; h.beta1 = p->beta1; h.beta2 = p->beta2; h.ent_coef = p->ent_coef; h.normalize = p->normalize_advantage != 0;
+    xopt::fill_adam(h.adam, p->lr, p->beta1, p->beta2, p->eps);
+    h.vf2 = (float)(2.0 * p->vf_coef); h.max_norm = (float)p->max_grad_norm; h.ent_coef = p->ent_coef; h.normalize = p->normalize_advantage != 0;
 }
 
 inline void fill_work(Work &k, const Shape &s) {
@@ -197,32 +194,6 @@ XARM_HD RowTerms surrogate(const Hyper &h, float ahat, float logp, float old_log
     t.kl = (rm1 - lr) * use;
     t.clipped = (__builtin_fabsf(rm1) > h.clip ? 1.0f : 0.0f) * use;
     return t;
-}
-
-XARM_HD double ipow(double b, int64_t t) {
-    double r = 1.0;
-    while (t > 0) {
-        if (t & 1) r = r * b;
-        b = b * b;
-        t >>= 1;
-    }
-    return r;
-}
-
-// the two float32 scalars of Adam's step t: lr / (1 - b1^t) and sqrt(1 - b2^t)
-XARM_HD void adam_scalars(const Hyper &h, int64_t t, float *out) {
-    out[0] = (float)(h.lr / (1.0 - ipow(h.beta1, t)));
-    out[1] = (float)__builtin_sqrt(1.0 - ipow(h.beta2, t));
-}
-
-XARM_HD void adam(const Hyper &h, const float *sc, float g, float &m, float &v, float &p) {
-    const float mn = m + h.one_m_b1 * (g - m);
-    const float gg = g * g;
-    const float vn = h.b2 * v + h.one_m_b2 * gg;
-    const float denom = __builtin_sqrtf(vn) / sc[1] + h.eps;
-    m = mn;
-    v = vn;
-    p = p - sc[0] * (mn / denom);
 }
 
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
@@ -309,16 +280,16 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
             }
             if ((i + 1) % ROWS == 0 || i + 1 == count) flush();
         }
-        const double n_use = n > 1.0 ? n : 1.0;
-        double sum2 = 0.0, ent = 0.0;
+        const double n_use = xopt::n_use(n);
+        double sum2 = 0.0;
         for (int64_t p = 0; p < a.P; p++) {
             double x = G[(size_t)p] / n_use;
             if (p >= a.off[12]) x -= h.ent_coef;
             g[(size_t)p] = (float)x;
             sum2 += (double)g[(size_t)p] * (double)g[(size_t)p];
         }
-        for (int c = 0; c < A; c++) ent += (double)log_std[c] + 0.5 + 0.918938533204672742;
-        const float norm = (float)__builtin_sqrt(sum2), coef = xa2c::clip_coef(norm, h.max_norm);
+        const double ent = xopt::gaussian_entropy(log_std, A);
+        const float norm = (float)__builtin_sqrt(sum2), coef = xopt::clip_coef(norm, h.max_norm);
         if (out_grad && st == 0)
             for (int64_t p = 0; p < a.P; p++) out_grad[p] = g[(size_t)p];
         if (out_stats) {
@@ -328,10 +299,10 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         }
         step[0] += 1;
         float sc[2];
-        adam_scalars(h, step[0], sc);
+        xopt::adam_scalars(h.adam, step[0], sc);
         for (int i = 0; i < NTENS; i++)
             for (int64_t p = a.off[i]; p < a.off[i + 1]; p++)
-                adam(h, sc, g[(size_t)p] * coef, m[i][p - a.off[i]], v[i][p - a.off[i]], w[i][p - a.off[i]]);
+                xopt::adam(h.adam, sc, g[(size_t)p] * coef, m[i][p - a.off[i]], v[i][p - a.off[i]], w[i][p - a.off[i]]);
     }
 }
 #endif

@@ -1,8 +1,8 @@
 // xarm_sac_core.h - device-resident SAC update: one call is one gradient step of stable-baselines3's SAC.train() on a
 // batch drawn from a replay buffer - the squashed-Gaussian actor on obs and next_obs, the entropy coefficient's step, the soft target,
 // the step of both critics, the actor's step through the stepped critics, the Polyak step of the targets - stream-ordered on the
-// module's own parameter tensors.  The kernels are in xarm_k_sac.hip; like xarm_ppo_core.h, whose Adam this reuses, it also compiles for
-// the host (g++ -DXARM_HOST_BUILD -ffp-contract=off, tests/hostbuild_sac/) for the CPU tests.  Everything a ROW gives - a, logp, y, q
+// module's own parameter tensors.  The kernels are in xarm_k_sac.hip; like xarm_a2c_core.h, whose host backward this reuses, it also
+// compiles for the host (g++ -DXARM_HOST_BUILD -ffp-contract=off, tests/hostbuild_sac/) for the CPU tests.  Everything a ROW gives - a, logp, y, q
 // and dq/da - is equal between the two builds bit for bit (the policy's chains and elementary functions, the backward's fmaf chains in
 // the tile's order); the sums over rows are not (each build is repeatable): the device adds a workgroup's rows in float32 and the
 // workgroups' partials in float64 in workgroup order, the host adds chunks of 64 rows in float32 and the chunks in float64.
@@ -20,13 +20,14 @@
 //   log_alpha g = (float)(-sum((logp_pi + target_entropy) use) / n_use) (auto only)
 //   flat      the 19 trained tensors one after the other: actor's 6, q1's 6, q2's 6, log_alpha: P floats
 //   noise     supplied, or Philox(seed; row, step at call start, TAG + 4 stream + column block), stream 0 = z_pi, 1 = z_next
-//   Adam      xppo::adam with t = step + 1 for all three optimisers; `step` is advanced by the call's last launch
+//   Adam      xopt::adam (xarm_opt_core.h) with t = step + 1 for all three optimisers
+//   finish    the call's last writes - log_alpha's step, its out_grad entry, the stats, step += 1 - are finish() below in both builds
 #pragma once
 #include <stdint.h>
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
 #include <vector>
 #endif
-#include "xarm_ppo_core.h"
+#include "xarm_a2c_core.h"
 
 namespace xsac {
 
@@ -52,7 +53,7 @@ struct Shape {
 };
 
 struct Hyper {
-    xppo::Hyper adam;               // b1, one_m_b1, b2, one_m_b2, eps, lr, beta1, beta2 (the rest is not read)
+    xopt::Adam adam;
     float gamma, tau, one_m_tau, alpha_fixed, target_entropy;
     int auto_alpha, deterministic;
     uint64_t seed;
@@ -77,12 +78,10 @@ inline const char *layout_error(const xarm_sac_layout *l) {
 inline const char *params_error(const xarm_sac_params *p) {
     if (!p) return "params is NULL";
     if (!(p->gamma >= 0.0 && p->gamma <= 1.0)) return "gamma must lie in [0, 1]";
-    if (!(p->lr >= 0.0) || !(p->lr < 1e300)) return "lr must be finite and >= 0";
+    if (const char *why = xopt::adam_error(p->lr, p->beta1, p->beta2, p->eps)) return why;
     if (!(p->tau >= 0.0 && p->tau <= 1.0)) return "tau must lie in [0, 1]";
     if (!(p->ent_coef >= 0.0) || !(p->ent_coef < 1e300)) return "ent_coef must be finite and >= 0";
     if (!(p->target_entropy > -1e300 && p->target_entropy < 1e300)) return "target_entropy must be finite";
-    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0) || !(p->beta2 >= 0.0 && p->beta2 < 1.0)) return "beta1 and beta2 must lie in [0, 1)";
-    if (!(p->eps > 0.0) || !(p->eps < 1e300)) return "eps must be finite and > 0";
     return nullptr;
 }
 
@@ -156,9 +155,7 @@ inline void fill_shape(Shape &s, const xarm_sac_layout *l) {
 }
 
 inline void fill_hyper(Hyper &h, const xarm_sac_params *p) {
-    h.adam = xppo::Hyper{};
-    h.adam.b1 = (float)p->beta1; h.adam.one_m_b1 = (float)(1.0 - p->beta1); h.adam.b2 = (float)p->beta2; h.adam.one_m_b2 = (float)(1.0 - p->beta2);
-    h.adam.eps = (float)p->eps; h.adam.lr = p->lr; h.adam.beta1 = p->beta1; h.adam.beta2 = p->beta2;
+    xopt::fill_adam(h.adam, p->lr, p->beta1, p->beta2, p->eps);
     h.gamma = (float)p->gamma; h.tau = (float)p->tau; h.one_m_tau = (float)(1.0 - p->tau); h.alpha_fixed = (float)p->ent_coef;
     h.target_entropy = (float)p->target_entropy; h.auto_alpha = p->auto_ent_coef != 0; h.deterministic = p->deterministic != 0; h.seed = p->seed;
 }
@@ -266,6 +263,31 @@ XARM_HD float polyak(const Hyper &h, float target, float w) {
     return keep + in;
 }
 
+// the call's last writes: log_alpha's Adam step (sc: Adam's two scalars of the step; w, m, v: log_alpha and its state), its entry of
+// out_grad (nullable), the stats row (nullable) and the step count.  sent, closs, aloss, slp, sq: the sums over rows of
+// (logp_pi + target_entropy) use, (q - y)^2 use of both critics, (alpha logp_pi - qmin) use, logp_pi use, qmin use
+XARM_HD void finish(const Hyper &h, const float *sc, float alpha, double n_use, double sent, double closs, double aloss, double slp, double sq,
+                    float *w, float *m, float *v, float *out_grad, float *out_stats, int64_t *step) {
+    const float log_alpha = w[0];
+    float gf = 0.0f;
+    if (h.auto_alpha) {
+        gf = (float)(-sent / n_use);
+        float mn = m[0], vn = v[0], wn = log_alpha;
+        xopt::adam(h.adam, sc, gf, mn, vn, wn);
+        m[0] = mn;
+        v[0] = vn;
+        w[0] = wn;
+    }
+    if (out_grad != nullptr) out_grad[0] = gf;
+    if (out_stats != nullptr) {
+        float *o = out_stats;
+        o[0] = (float)(0.5 * closs / n_use); o[1] = (float)(aloss / n_use);
+        o[2] = h.auto_alpha ? (float)(-(double)log_alpha * sent / n_use) : 0.0f; o[3] = alpha;
+        o[4] = (float)(slp / n_use); o[5] = (float)(sq / n_use); o[6] = (float)n_use; o[7] = 0.0f;
+    }
+    step[0] = step[0] + 1;
+}
+
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
 // ---- the host build: plain loops over the rows
 inline void host_noise(const Hyper &h, const float *given, int64_t n, int64_t counter, int stream, int A, float (&z)[MAX_A]) {
@@ -330,7 +352,7 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
     const Tower actor = tower_of(w), q1 = tower_of(w + 6), q2 = tower_of(w + 12), q1t = tower_of(tq), q2t = tower_of(tq + 6);
     const int D = s.D, A = s.A, Dq = s.Dq;
     const int64_t B = s.B, t0 = step[0];
-    const float alpha = alpha_of(h, w[18]), log_alpha = w[18][0];
+    const float alpha = alpha_of(h, w[18]);
     std::vector<float> y((size_t)B), lpv((size_t)B), zv((size_t)(B * A)), xq((size_t)(B * Dq)), xpi((size_t)(B * Dq)), g((size_t)s.P, 0.0f);
     std::vector<double> G((size_t)s.P);
     std::vector<float> chunk((size_t)s.P);
@@ -362,15 +384,15 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         sent += (double)((lp + h.target_entropy) * u);
         if (out_target) out_target[n] = y[(size_t)n];
     }
-    const double n_use = nuse > 1.0 ? nuse : 1.0;
+    const double n_use = xopt::n_use(nuse);
     float sc[2];
-    xppo::adam_scalars(h.adam, t0 + 1, sc);
+    xopt::adam_scalars(h.adam, t0 + 1, sc);
     auto zero_sums = [&]() { for (int64_t p = 0; p < s.P; p++) { G[(size_t)p] = 0.0; chunk[(size_t)p] = 0.0f; } };
     auto flush = [&]() { for (int64_t p = 0; p < s.P; p++) { G[(size_t)p] += (double)chunk[(size_t)p]; chunk[(size_t)p] = 0.0f; } };
-    auto finish = [&](int64_t p0, int64_t p1) { for (int64_t p = p0; p < p1; p++) g[(size_t)p] = (float)(G[(size_t)p] / n_use); };
+    auto mean_grad = [&](int64_t p0, int64_t p1) { for (int64_t p = p0; p < p1; p++) g[(size_t)p] = (float)(G[(size_t)p] / n_use); };
     auto apply = [&](int i0, int i1) {
         for (int i = i0; i < i1; i++)
-            for (int64_t p = s.off[i]; p < s.off[i + 1]; p++) xppo::adam(h.adam, sc, g[(size_t)p], m[i][p - s.off[i]], v[i][p - s.off[i]], w[i][p - s.off[i]]);
+            for (int64_t p = s.off[i]; p < s.off[i + 1]; p++) xopt::adam(h.adam, sc, g[(size_t)p], m[i][p - s.off[i]], v[i][p - s.off[i]], w[i][p - s.off[i]]);
     };
     // the critics
     zero_sums();
@@ -388,7 +410,7 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         }
         if ((n + 1) % ROWS == 0 || n + 1 == B) flush();
     }
-    finish(s.off[6], s.off[18]);
+    mean_grad(s.off[6], s.off[18]);
     apply(6, 18);
     for (int i = 0; i < 12; i++)
         for (int64_t p = 0; p < s.off[7 + i] - s.off[6 + i]; p++) tq[i][p] = polyak(h, tq[i][p], w[6 + i][p]);
@@ -412,18 +434,11 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
         sq += (double)(qm * u);
         if ((n + 1) % ROWS == 0 || n + 1 == B) flush();
     }
-    finish(0, s.off[6]);
-    g[(size_t)s.off[18]] = h.auto_alpha ? (float)(-sent / n_use) : 0.0f;
+    mean_grad(0, s.off[6]);
     apply(0, 6);
-    if (h.auto_alpha) apply(18, 19);
-    step[0] = t0 + 1;
     if (out_grad)
-        for (int64_t p = 0; p < s.P; p++) out_grad[p] = g[(size_t)p];
-    if (out_stats) {
-        out_stats[0] = (float)(0.5 * closs / n_use); out_stats[1] = (float)(aloss / n_use);
-        out_stats[2] = h.auto_alpha ? (float)(-(double)log_alpha * sent / n_use) : 0.0f; out_stats[3] = alpha;
-        out_stats[4] = (float)(slp / n_use); out_stats[5] = (float)(sq / n_use); out_stats[6] = (float)n_use; out_stats[7] = 0.0f;
-    }
+        for (int64_t p = 0; p < s.off[18]; p++) out_grad[p] = g[(size_t)p];
+    finish(h, sc, alpha, n_use, sent, closs, aloss, slp, sq, w[18], m[18], v[18], out_grad ? out_grad + s.off[18] : nullptr, out_stats, step);
 }
 #endif
 

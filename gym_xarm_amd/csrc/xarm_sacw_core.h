@@ -15,7 +15,7 @@
 //             i = K with x = 1.  Row ranges: the 64-row tiles dealt in order to S = min(16, tiles) contiguous ranges.
 //   reduce    g = (float)(sum over ranges, in range order, of (double) partial / n_use)
 //   scalars   a sum over rows is 256 float64 sums over the rows t, t + 256, ..., added in t order
-//   heads     xsac::actor_head, target_row, actor_deltas, polyak, noise4; xppo::adam: called, not copied
+//   heads     xsac::actor_head, target_row, actor_deltas, polyak, noise4; finish; xopt::adam, slice_sum, tensor_at (xarm_opt_core.h): called, not copied
 #pragma once
 #include "xarm_sac_core.h"
 
@@ -292,7 +292,7 @@ XARM_HD void head_row(const Dev &d, int64_t n, int64_t t0) {
 }
 
 XARM_HD void head_first(const Dev &d, int64_t t0) {
-    xppo::adam_scalars(d.h.adam, t0 + 1, d.hdr);
+    xopt::adam_scalars(d.h.adam, t0 + 1, d.hdr);
     d.hdr[2] = xsac::alpha_of(d.h, d.w[d.s.NT - 1]);
     d.hdr[3] = 0.0f;
 }
@@ -335,51 +335,29 @@ XARM_HD void pi_row(const Dev &d, int64_t n, double *sums) {
     sums[5] += (double)(qm * u);
 }
 
-XARM_HD double n_use_of(const Dev &d) { return d.scal[0] > 1.0 ? d.scal[0] : 1.0; }
+XARM_HD double n_use_of(const Dev &d) { return xopt::n_use(d.scal[0]); }
 
 // trained parameter p of the flat order, its ranges' partials at part[s pstride]: reduce, Adam, and with `targets` the Polyak step
 XARM_HD void apply_param(const Dev &d, int64_t p, const float *part, int64_t pstride, bool targets) {
     const Shape &s = d.s;
-    double sum = 0.0;
-    for (int k = 0; k < s.S; k++) sum += (double)part[(int64_t)k * pstride];
-    const float gf = (float)(sum / n_use_of(d));
+    const float gf = (float)(xopt::slice_sum(part, s.S, pstride) / n_use_of(d));
     if (d.out_grad != nullptr) d.out_grad[p] = gf;
-    int i = 0;
-    for (int k = 1; k < s.NT; k++)
-        if (p >= s.off[k]) i = k;
+    const int i = xopt::tensor_at(s.off, 0, s.NT, p);
     const int64_t e = p - s.off[i];
     const float sc[2] = {d.hdr[0], d.hdr[1]};
     float m = d.m[i][e], v = d.v[i][e], w = d.w[i][e];
-    xppo::adam(d.h.adam, sc, gf, m, v, w);
+    xopt::adam(d.h.adam, sc, gf, m, v, w);
     d.m[i][e] = m;
     d.v[i][e] = v;
     d.w[i][e] = w;
     if (targets) d.tq[i - s.tp][e] = xsac::polyak(d.h, d.tq[i - s.tp][e], w);
 }
 
-// the call's last writes: log_alpha's step, the stats, the step count
+// the call's last writes: xsac::finish on this step's sums
 XARM_HD void finish(const Dev &d) {
     const int la = d.s.NT - 1;
-    const double n_use = n_use_of(d), sent = d.scal[2];
-    const float sc[2] = {d.hdr[0], d.hdr[1]};
-    const float log_alpha = d.w[la][0];
-    float gf = 0.0f;
-    if (d.h.auto_alpha) {
-        gf = (float)(-sent / n_use);
-        float m = d.m[la][0], v = d.v[la][0], w = log_alpha;
-        xppo::adam(d.h.adam, sc, gf, m, v, w);
-        d.m[la][0] = m;
-        d.v[la][0] = v;
-        d.w[la][0] = w;
-    }
-    if (d.out_grad != nullptr) d.out_grad[d.s.P - 1] = gf;
-    if (d.out_stats != nullptr) {
-        float *o = d.out_stats;
-        o[0] = (float)(0.5 * d.scal[3] / n_use); o[1] = (float)(d.scal[4] / n_use);
-        o[2] = d.h.auto_alpha ? (float)(-(double)log_alpha * sent / n_use) : 0.0f; o[3] = d.hdr[2];
-        o[4] = (float)(d.scal[1] / n_use); o[5] = (float)(d.scal[5] / n_use); o[6] = (float)n_use; o[7] = 0.0f;
-    }
-    d.step[0] = d.step[0] + 1;
+    xsac::finish(d.h, d.hdr, d.hdr[2], n_use_of(d), d.scal[2], d.scal[3], d.scal[4], d.scal[1], d.scal[5], d.w[la], d.m[la], d.v[la],
+                 d.out_grad != nullptr ? d.out_grad + (d.s.P - 1) : nullptr, d.out_stats, d.step);
 }
 
 // the act call's row: noise as xarm_sac_act draws it

@@ -26,7 +26,7 @@ _refs = {}
 def sources():
     csrc = os.path.join(ROOT, "gym_xarm_amd", "csrc")
     return [os.path.join(DIR, "a2c_host.cpp"), os.path.join(ROOT, "include", "xarm_hip.h")] + \
-        [os.path.join(csrc, h) for h in ("xarm_a2c_core.h", "xarm_policy_core.h", "xarm_norm_core.h", "xarm_core.h")]
+        [os.path.join(csrc, h) for h in ("xarm_a2c_core.h", "xarm_opt_core.h", "xarm_policy_core.h", "xarm_norm_core.h", "xarm_core.h")]
 
 
 def lib():

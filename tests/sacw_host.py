@@ -48,7 +48,7 @@ def case_id(c):
 def sources():
     csrc = os.path.join(ROOT, "gym_xarm_amd", "csrc")
     return [os.path.join(DIR, "sacw_host.cpp"), os.path.join(ROOT, "include", "xarm_hip.h")] + \
-        [os.path.join(csrc, h) for h in ("xarm_sacw_core.h", "xarm_sac_core.h", "xarm_ppo_core.h", "xarm_a2c_core.h", "xarm_policy_core.h",
+        [os.path.join(csrc, h) for h in ("xarm_sacw_core.h", "xarm_sac_core.h", "xarm_opt_core.h", "xarm_a2c_core.h", "xarm_policy_core.h",
                                          "xarm_norm_core.h", "xarm_core.h")]
 
 
