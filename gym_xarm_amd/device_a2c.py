@@ -1,16 +1,18 @@
-"""Device-resident A2C update: the update block of train.py - bootstrap value, n-step returns, the backward of both towers,
+"""Device-resident A2C update: train.a2c_update - bootstrap value, n-step returns, the backward of both towers,
 `clip_grad_norm_` and `RMSprop.step` - as one stream-ordered call of six HIP launches (csrc/xarm_k_a2c.hip).
 
 The torch update of train.py runs on the order of a hundred small launches per update: a second forward of both towers over
-n_steps x num_envs rows under autograd, the backward, the clip and the optimiser.  `DeviceA2C` keeps the rollout in preallocated
-buffers and updates the module's own parameter tensors in place, so a `DevicePolicy` on the same module (or the module itself)
-sees the new weights in its next call.  The torch update stays as it is and is the checker (tests/test_a2c_host.py,
+n_steps x num_envs rows under autograd, the backward, the clip and the optimiser.  `DeviceA2C` keeps the rollout in the buffers
+`train.TorchA2C` uses and updates the module's own parameter tensors in place, so a `DevicePolicy` on the same module (or the
+module itself) sees the new weights in its next call.  The checker is train.a2c_loss / a2c_update, the functions train() itself
+runs without device_update: tests/a2c_host.py calls them on float64 and float32 copies of the model (tests/test_a2c_host.py,
 tests/test_a2c_gpu.py)."""
 import ctypes as C
 
 import torch
 
 from . import _native
+from .train import rollout_buffers, store_rollout  # noqa: F401  (store_rollout is re-exported)
 
 HYPER = ("gamma", "lr", "alpha", "eps", "vf_coef", "ent_coef", "max_grad_norm")
 
@@ -48,31 +50,6 @@ def export_square_avg(square_avg, opt, params):
             else:
                 st["step"] = torch.zeros((), dtype=torch.float32)
                 st["square_avg"] = s.detach().clone()
-
-
-def rollout_buffers(T, E, D, A, dev, workspace_bytes):
-    """the rollout storage of the device updates (DeviceA2C, DevicePPO): obs [T, E, D], action [T, E, A], reward / done / use [T, E]
-    and the call's workspace"""
-    return {"obs": torch.zeros(T, E, D, device=dev), "action": torch.zeros(T, E, A, device=dev), "reward": torch.zeros(T, E, device=dev),
-            "done": torch.zeros(T, E, device=dev), "use": torch.ones(T, E, device=dev),
-            "workspace": torch.zeros(max(int(workspace_bytes), 16) // 4, dtype=torch.float32, device=dev)}
-
-
-def store_rollout(b, k, obs, action, reward, done, resetting=None):
-    """slot k of the rollout buffers `b`, as train.py's loop forms it: reward (1 - resetting), max(done, resetting),
-    use = 1 - resetting.  action None: the action is already in b["action"][k]."""
-    b["obs"][k].copy_(obs)
-    if action is not None:
-        b["action"][k].copy_(action)
-    if resetting is None:
-        b["reward"][k].copy_(reward)
-        b["done"][k].copy_(done)
-        b["use"][k].fill_(1.0)
-    else:
-        r = resetting.float()
-        b["reward"][k].copy_(reward * (1.0 - r))
-        b["done"][k].copy_(torch.maximum(done.float(), r))
-        b["use"][k].copy_(1.0 - r)
 
 
 def policy_weights(tensors, device, who):
@@ -122,8 +99,7 @@ class DeviceA2C:
         return policy_weights(tensors, self.device, "DeviceA2C")
 
     def store(self, k, obs, action, reward, done, resetting=None):
-        """slot k of the rollout, as train.py's loop forms it: reward (1 - resetting), max(done, resetting), use = 1 - resetting.
-        action None: the action is already in buffers["action"][k]."""
+        """slot k of the rollout (train.store_rollout)"""
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
 
     def _call(self, weights, square_avg, last_obs, hyper, out_returns, out_grad, out_stats):

@@ -4,14 +4,16 @@ minibatches, per-minibatch advantage normalisation, the clipped surrogate, the b
 
 A torch PPO update is S times the launch chain of an A2C update (forward of both towers under autograd, backward, clip, optimiser);
 `DevicePPO` keeps the rollout in the buffers `DeviceA2C` uses and updates the module's own parameter tensors in place, so a
-`DevicePolicy` on the same module (or the module itself) sees the new weights in its next call.  The torch PPO block of train.py
-stays as it is and is the checker (tests/test_ppo_host.py, tests/test_ppo_gpu.py)."""
+`DevicePolicy` on the same module (or the module itself) sees the new weights in its next call.  The checker is the torch PPO block of
+train.py - ppo_prepare, ppo_minibatch_loss and optimizer_step, which train() itself runs through ppo_update without device_update:
+tests/ppo_host.py calls them on float64 and float32 copies of the model (tests/test_ppo_host.py, tests/test_ppo_gpu.py)."""
 import ctypes as C
 
 import torch
 
 from . import _native
-from .device_a2c import module_params, policy_weights, rollout_buffers, store_rollout
+from .device_a2c import module_params, policy_weights
+from .train import rollout_buffers, store_rollout
 
 
 def _check_adam(opt):
@@ -104,7 +106,7 @@ class DevicePPO:
         return module_params(self.model)
 
     def store(self, k, obs, action, reward, done, resetting=None):
-        """slot k of the rollout (device_a2c.store_rollout)"""
+        """slot k of the rollout (train.store_rollout)"""
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
 
     def shuffle(self):

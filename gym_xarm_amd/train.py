@@ -9,6 +9,7 @@ out in ~60 lines of torch.
 """
 import argparse
 import json
+import math
 import os
 import time
 
@@ -250,6 +251,166 @@ class ActorCritic(nn.Module):
         return self.vf(x).squeeze(-1)
 
 
+# ---- the rollout every learner keeps (TorchA2C, TorchPPO, device_a2c.DeviceA2C, device_ppo.DevicePPO)
+def rollout_buffers(T, E, D, A, dev, workspace_bytes=None):
+    """obs [T, E, D], action [T, E, A], reward / done / use [T, E]; workspace_bytes: a device update's call workspace as well"""
+    b = {"obs": torch.zeros(T, E, D, device=dev), "action": torch.zeros(T, E, A, device=dev), "reward": torch.zeros(T, E, device=dev),
+         "done": torch.zeros(T, E, device=dev), "use": torch.ones(T, E, device=dev)}
+    if workspace_bytes is not None:
+        b["workspace"] = torch.zeros(max(int(workspace_bytes), 16) // 4, dtype=torch.float32, device=dev)
+    return b
+
+
+def store_rollout(b, k, obs, action, reward, done, resetting=None):
+    """slot k of the rollout buffers `b`.  A row that spends the call on a lazy-reset tick (`resetting`) carries no reward and no
+    gradient and cuts the return like an episode end: reward (1 - resetting), max(done, resetting), use = 1 - resetting.
+    action None: the action is already in b["action"][k]."""
+    b["obs"][k].copy_(obs)
+    if action is not None:
+        b["action"][k].copy_(action)
+    if resetting is None:
+        b["reward"][k].copy_(reward)
+        b["done"][k].copy_(done)
+        b["use"][k].fill_(1.0)
+    else:
+        r = resetting.float()
+        b["reward"][k].copy_(reward * (1.0 - r))
+        b["done"][k].copy_(torch.maximum(done.float(), r))
+        b["use"][k].copy_(1.0 - r)
+
+
+# ---- the torch updates: what train() runs without device_update and what the HIP learners are checked against.  Plain functions of
+# a rollout dict (the tensors above, in the model's dtype) and last_obs [E, D], the observation after the rollout's last step.
+def _entropy_term(model, loss, ent_coef):
+    """(loss - ent_coef entropy, entropy) of the state-independent Gaussian; at ent_coef 0 the term stays out of the graph"""
+    entropy = (model.log_std + 0.5 + 0.5 * math.log(2.0 * math.pi)).sum()
+    return (loss - ent_coef * entropy if ent_coef != 0.0 else loss), entropy
+
+
+def a2c_loss(model, rollout, last_obs, gamma=0.99, vf_coef=0.5, ent_coef=0.0):
+    """(loss, returns [T, E], terms): n-step returns from the bootstrap value, then policy_loss + vf_coef value_loss - ent_coef entropy
+    over the used rows.  terms: policy_loss, value_loss, entropy, n_use and the rows' adv, logp, use, as tensors."""
+    O, A, U, rew, done = (rollout[k] for k in ("obs", "action", "use", "reward", "done"))
+    with torch.no_grad():
+        ret = model.value(last_obs)
+        rets = []
+        for k in reversed(range(O.shape[0])):
+            ret = rew[k] + gamma * ret * (1.0 - done[k])
+            rets.append(ret)
+        rets = torch.stack(rets[::-1])
+    values = model.value(O)
+    adv = rets - values.detach()
+    logp = model.dist(O).log_prob(A).sum(-1)
+    n_use = U.sum().clamp(min=1.0)
+    policy_loss, value_sum = -(adv * logp * U).sum() / n_use, (((rets - values) ** 2) * U).sum()
+    loss, entropy = _entropy_term(model, policy_loss + vf_coef * value_sum / n_use, ent_coef)
+    return loss, rets, {"policy_loss": policy_loss, "value_loss": value_sum / n_use, "entropy": entropy, "n_use": n_use, "adv": adv, "logp": logp, "use": U}
+
+
+def optimizer_step(model, opt, loss, max_grad_norm=0.5):
+    opt.zero_grad(set_to_none=True)
+    loss.backward()
+    nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+    opt.step()
+
+
+def a2c_update(model, opt, rollout, last_obs, gamma=0.99, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5):
+    optimizer_step(model, opt, a2c_loss(model, rollout, last_obs, gamma, vf_coef, ent_coef)[0], max_grad_norm)
+
+
+def ppo_prepare(model, rollout, last_obs, gamma=0.99, gae_lambda=0.95, old_logp=None):
+    """flat [N] (adv, ret, old_logp, use) under the model as it is: GAE(gae_lambda) from the rollout's values, ret = adv + value.
+    old_logp [T, E]: used in place of the stored actions' log-probabilities."""
+    O, A, rew, done = (rollout[k] for k in ("obs", "action", "reward", "done"))
+    with torch.no_grad():
+        values = model.value(O)
+        if old_logp is None:
+            old_logp = model.dist(O.flatten(0, 1)).log_prob(A.flatten(0, 1)).sum(-1)
+        next_value, next_adv, advs = model.value(last_obs), torch.zeros_like(rew[0]), []
+        for k in reversed(range(O.shape[0])):
+            keep = 1.0 - done[k]
+            delta = rew[k] + gamma * keep * next_value - values[k]
+            next_adv = delta + gamma * gae_lambda * keep * next_adv
+            next_value = values[k]
+            advs.append(next_adv)
+        adv = torch.stack(advs[::-1])
+    return adv.flatten(), (adv + values).flatten(), old_logp.flatten(), rollout["use"].flatten()
+
+
+def ppo_minibatch_loss(model, rollout, prep, idx, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True, diagnostics=False):
+    """(loss, terms) of the rows idx of ppo_prepare's `prep`: the advantage normalised over the minibatch's used rows (unless switched
+    off, or fewer than two are used), the surrogate clipped at clip_range, value loss and entropy.  terms: the rows' rho, log_ratio,
+    a_hat, use, surr and policy_loss, value_loss, entropy, n_use; diagnostics: approx_kl and clip_fraction as well."""
+    adv, ret, old_logp, use = prep
+    o, a = rollout["obs"].flatten(0, 1)[idx], rollout["action"].flatten(0, 1)[idx]
+    u, a_hat = use[idx], adv[idx]
+    n = u.sum()
+    n_use = n.clamp(min=1.0)
+    if normalize_advantage:
+        mu = (a_hat * u).sum() / n_use
+        sigma = ((((a_hat - mu) ** 2) * u).sum() / (n - 1.0).clamp(min=1.0)).sqrt()
+        a_hat = torch.where(n > 1.0, (a_hat - mu) / (sigma + 1e-8), a_hat)
+    log_ratio = model.dist(o).log_prob(a).sum(-1) - old_logp[idx]
+    rho = log_ratio.exp()
+    surr = torch.min(rho * a_hat, rho.clamp(1.0 - clip_range, 1.0 + clip_range) * a_hat)
+    policy_loss, value_sum = -(surr * u).sum() / n_use, (((ret[idx] - model.value(o)) ** 2) * u).sum()
+    loss, entropy = _entropy_term(model, policy_loss + vf_coef * value_sum / n_use, ent_coef)
+    terms = {"policy_loss": policy_loss, "value_loss": value_sum / n_use, "entropy": entropy, "n_use": n_use, "rho": rho, "log_ratio": log_ratio,
+             "a_hat": a_hat, "use": u, "surr": surr}
+    if diagnostics:
+        with torch.no_grad():
+            terms["approx_kl"] = (((rho - 1.0) - log_ratio) * u).sum() / n_use
+            terms["clip_fraction"] = (((rho - 1.0).abs() > clip_range).to(u.dtype) * u).sum() / n_use
+    return loss, terms
+
+
+def ppo_update(model, opt, rollout, last_obs, n_epochs, batch_size, gamma=0.99, gae_lambda=0.95, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
+               max_grad_norm=0.5, normalize_advantage=True):
+    """stable-baselines3's PPO.train() on one rollout: n_epochs passes over minibatches of batch_size rows, a torch.randperm from the
+    global generator per pass"""
+    prep = ppo_prepare(model, rollout, last_obs, gamma, gae_lambda)
+    n_rows = prep[0].numel()
+    for _ in range(n_epochs):
+        perm = torch.randperm(n_rows, device=last_obs.device)
+        for m in range(0, n_rows, batch_size):
+            loss, _ = ppo_minibatch_loss(model, rollout, prep, perm[m:m + batch_size], clip_range, vf_coef, ent_coef, normalize_advantage)
+            optimizer_step(model, opt, loss, max_grad_norm)
+
+
+class _TorchLearner:
+    """the device learners' interface (`buffers`, `store`, `update`) around a torch optimiser `opt`, on the model's device"""
+
+    def __init__(self, model, num_envs, n_steps, opt, **hyper):
+        self.model, self.opt, self.hyper = model, opt, hyper
+        self.buffers = rollout_buffers(n_steps, num_envs, model.pi[0].in_features, model.pi[4].out_features, model.log_std.device)
+
+    def store(self, k, obs, action, reward, done, resetting=None):
+        store_rollout(self.buffers, k, obs, action, reward, done, resetting)
+
+
+class TorchA2C(_TorchLearner):
+    def __init__(self, model, num_envs, n_steps=5, gamma=0.99, lr=7e-4, alpha=0.99, eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5):
+        super().__init__(model, num_envs, n_steps, torch.optim.RMSprop(model.parameters(), lr=lr, alpha=alpha, eps=eps),
+                         gamma=gamma, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm)
+
+    def update(self, last_obs):
+        a2c_update(self.model, self.opt, self.buffers, last_obs, **self.hyper)
+
+
+class TorchPPO(_TorchLearner):
+    """batch_size None: ceil(N / 4)"""
+
+    def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
+                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True):
+        super().__init__(model, num_envs, n_steps, torch.optim.Adam(model.parameters(), lr=lr, betas=betas, eps=eps),
+                         n_epochs=n_epochs, batch_size=max(1, -(-n_steps * num_envs // 4)) if batch_size is None else int(batch_size), gamma=gamma,
+                         gae_lambda=gae_lambda, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
+                         normalize_advantage=normalize_advantage)
+
+    def update(self, last_obs):
+        ppo_update(self.model, self.opt, self.buffers, last_obs, **self.hyper)
+
+
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
           device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2):
@@ -263,12 +424,11 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     `model.dist(obs).sample().clamp(-1, 1)`; the update is unchanged and recomputes log-probabilities and values with autograd
     from the stored actions.
     device_update: the update itself - bootstrap value, returns, backward, clip_grad_norm_ and RMSprop - in HIP kernels on the
-    model's own parameters (gym_xarm_amd/device_a2c.py DeviceA2C) instead of the autograd block below; the rollout is stored in its
-    buffers and no torch optimiser is created.
+    model's own parameters (gym_xarm_amd/device_a2c.py DeviceA2C) instead of TorchA2C's a2c_update; no torch optimiser is created.
     algo: "a2c" (n_steps 5, lr 7e-4: the reference's learner) or "ppo" (n_steps 16, lr 3e-4): stable-baselines3's PPO.train() on each
-    rollout - GAE(gae_lambda) from the rollout's values, n_epochs passes over shuffled minibatches of batch_size rows (None: a quarter
-    of the rollout), per-minibatch advantage normalisation over the used rows, the surrogate clipped at clip_range, clip_grad_norm_
-    and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO)."""
+    rollout (ppo_update) - GAE(gae_lambda) from the rollout's values, n_epochs passes over shuffled minibatches of batch_size rows (None:
+    a quarter of the rollout), per-minibatch advantage normalisation over the used rows, the surrogate clipped at clip_range,
+    clip_grad_norm_ and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO)."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
     ppo = algo == "ppo"
@@ -291,107 +451,46 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     model = ActorCritic(venv.dim, env.act_dim).to(dev)
     n_rows = n_steps * num_envs
     batch_size = max(1, -(-n_rows // 4)) if batch_size is None else min(int(batch_size), n_rows)
+    hyper = dict(n_steps=n_steps, gamma=gamma, lr=lr, eps=1e-5)
+    if ppo:
+        hyper.update(n_epochs=n_epochs, batch_size=batch_size, gae_lambda=gae_lambda, clip_range=clip_range)
     if device_update and ppo:
         from .device_ppo import DevicePPO
-        a2c = DevicePPO(model, num_envs, n_steps=n_steps, n_epochs=n_epochs, batch_size=batch_size, gamma=gamma, gae_lambda=gae_lambda,
-                        clip_range=clip_range, lr=lr, eps=1e-5, seed=seed)
-        env_action = torch.empty(num_envs, env.act_dim, device=dev)
+        learner = DevicePPO(model, num_envs, seed=seed, **hyper)
     elif device_update:
         from .device_a2c import DeviceA2C
-        a2c = DeviceA2C(model, num_envs, n_steps=n_steps, gamma=gamma, lr=lr, alpha=0.99, eps=1e-5)
-        env_action = torch.empty(num_envs, env.act_dim, device=dev)
-    elif ppo:
-        opt = torch.optim.Adam(model.parameters(), lr=lr, eps=1e-5)
+        learner = DeviceA2C(model, num_envs, **hyper)
     else:
-        opt = torch.optim.RMSprop(model.parameters(), lr=lr, alpha=0.99, eps=1e-5)
+        learner = (TorchPPO if ppo else TorchA2C)(model, num_envs, **hyper)
     if device_policy:
         from .device_policy import DevicePolicy
         policy = DevicePolicy(model, seed=seed, row_offset=int(getattr(env, "_env_id_offset", 0)))
+        env_action = torch.empty(num_envs, env.act_dim, device=dev)
     obs = venv.reset()
     hist, t0 = [], time.perf_counter()
     succ_sum, done_sum, raw_sum = torch.zeros((), device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)
     for it in range(1, updates + 1):
-        obs_buf, act_buf, rew_buf, done_buf, use_buf = [], [], [], [], []
         for k in range(n_steps):
-            if device_policy and device_update:
+            if device_policy:
                 # the sample lands in its slot of the rollout; env.step has read env_action when the next act_into rewrites it
-                out = policy.act_into({"action": a2c.buffers["action"][k], "env_action": env_action}, obs)
-                a, a_env = None, out["env_action"]
-            elif device_policy:
-                # fresh tensors every step: the buffers below keep `a`, and the update reads it
-                out = policy.act_into({"action": torch.empty(num_envs, env.act_dim, device=dev),
-                                       "env_action": torch.empty(num_envs, env.act_dim, device=dev)}, obs)
-                a, a_env = out["action"], out["env_action"]
+                policy.act_into({"action": learner.buffers["action"][k], "env_action": env_action}, obs)
+                a, a_env = None, env_action
             else:
                 with torch.no_grad():
                     a = model.dist(obs).sample()
                 a_env = a.clamp(-1, 1)
             nobs, nrew, done, info, raw = venv.step(a_env)
-            resetting = info["resetting"].float() if "resetting" in info else torch.zeros_like(nrew)
+            resetting = info["resetting"] if "resetting" in info else None
             if not device_normalize:
-                monitor.update(raw, done, ~info["resetting"] if "resetting" in info else None)
+                monitor.update(raw, done, None if resetting is None else ~resetting)
             if callback is not None:
                 callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (k + 1) * num_envs)
-            if device_update:
-                a2c.store(k, obs, a, nrew, done, info["resetting"] if "resetting" in info else None)
-            else:
-                obs_buf.append(obs); act_buf.append(a); rew_buf.append(nrew * (1.0 - resetting))
-                done_buf.append(torch.maximum(done.float(), resetting)); use_buf.append(1.0 - resetting)
+            learner.store(k, obs, a, nrew, done, resetting)
             succ_sum += (info["is_success"].float() * done.float()).sum()
             done_sum += done.float().sum()
             raw_sum += raw.mean()
             obs = nobs
-        if device_update:
-            a2c.update(obs)
-        elif ppo:
-            O, A, U = torch.stack(obs_buf).flatten(0, 1), torch.stack(act_buf).flatten(0, 1), torch.stack(use_buf).flatten()
-            with torch.no_grad():
-                values = model.value(torch.stack(obs_buf))
-                old_logp = model.dist(O).log_prob(A).sum(-1)
-                next_value, next_adv, advs = model.value(obs), torch.zeros(num_envs, device=dev), []
-                for k in reversed(range(n_steps)):
-                    keep = 1.0 - done_buf[k]
-                    delta = rew_buf[k] + gamma * keep * next_value - values[k]
-                    next_adv = delta + gamma * gae_lambda * keep * next_adv
-                    next_value = values[k]
-                    advs.append(next_adv)
-                adv = torch.stack(advs[::-1])
-                rets, adv = (adv + values).flatten(), adv.flatten()
-            for _ in range(n_epochs):
-                perm = torch.randperm(n_rows, device=dev)
-                for m in range(0, n_rows, batch_size):
-                    idx = perm[m:m + batch_size]
-                    u, a_mb = U[idx], adv[idx]
-                    n = u.sum()
-                    n_use = n.clamp(min=1.0)
-                    mu = (a_mb * u).sum() / n_use
-                    sigma = ((((a_mb - mu) ** 2) * u).sum() / (n - 1.0).clamp(min=1.0)).sqrt()
-                    a_hat = torch.where(n > 1.0, (a_mb - mu) / (sigma + 1e-8), a_mb)
-                    ratio = (model.dist(O[idx]).log_prob(A[idx]).sum(-1) - old_logp[idx]).exp()
-                    surr = torch.min(ratio * a_hat, ratio.clamp(1.0 - clip_range, 1.0 + clip_range) * a_hat)
-                    loss = -(surr * u).sum() / n_use + 0.5 * (((rets[idx] - model.value(O[idx])) ** 2) * u).sum() / n_use
-                    opt.zero_grad(set_to_none=True)
-                    loss.backward()
-                    nn.utils.clip_grad_norm_(model.parameters(), 0.5)
-                    opt.step()
-        else:
-            with torch.no_grad():
-                ret = model.value(obs)
-                rets = []
-                for k in reversed(range(n_steps)):
-                    ret = rew_buf[k] + gamma * ret * (1.0 - done_buf[k])
-                    rets.append(ret)
-                rets = torch.stack(rets[::-1])
-            O, A, U = torch.stack(obs_buf), torch.stack(act_buf), torch.stack(use_buf)
-            values = model.value(O)
-            adv = rets - values.detach()
-            logp = model.dist(O).log_prob(A).sum(-1)
-            n_use = U.sum().clamp(min=1.0)
-            loss = -(adv * logp * U).sum() / n_use + 0.5 * (((rets - values) ** 2) * U).sum() / n_use
-            opt.zero_grad(set_to_none=True)
-            loss.backward()
-            nn.utils.clip_grad_norm_(model.parameters(), 0.5)
-            opt.step()
+        learner.update(obs)
         if it % log_every == 0 or it == updates:
             if dev.type == "cuda":
                 torch.cuda.synchronize()

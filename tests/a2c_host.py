@@ -1,17 +1,16 @@
 """ctypes view of tests/hostbuild_a2c (g++ -ffp-contract=off build of csrc/xarm_a2c_core.h) - CPU-side tests only - with the batches,
-the torch restatement of train.py's update block (float32 and float64) and the tolerance rule that the host and GPU tests of the
-A2C update share.  Models and rows come from policy_host.case."""
+the torch reference - train.py's a2c_loss and a2c_update on float32 and float64 copies of the model - and the tolerance rule that the
+host and GPU tests of the A2C update share.  Models and rows come from policy_host.case."""
 import copy
 import ctypes as C
-import math
 import os
 import subprocess
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 import policy_host as PH
+from gym_xarm_amd import train as TR
 
 ROOT = PH.ROOT
 DIR = os.path.join(ROOT, "tests", "hostbuild_a2c")
@@ -128,29 +127,21 @@ def host_update(w, sq, b, h):
     return rc, out
 
 
-# ---- torch: train.py's update block (lines 305-321) with the entropy term, in the model's dtype
-def torch_loss(model, b, h):
-    dt = model.log_std.dtype
+# ---- torch: train.py's own update functions on the batch, in the model's dtype
+def rollout_of(b, dt):
+    """(the rollout dict of train.py's update functions, last_obs) of a NumPy batch"""
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dt)
-    O, A_, rew, done, last = t(b["obs"]), t(b["action"]), t(b["reward"]), t(b["done"]), t(b["last_obs"])
-    U = torch.ones_like(rew) if b["use"] is None else t(b["use"])
-    n_steps, gamma = O.shape[0], h["gamma"]
-    with torch.no_grad():
-        ret = model.value(last)
-        rets = []
-        for k in reversed(range(n_steps)):
-            ret = rew[k] + gamma * ret * (1.0 - done[k])
-            rets.append(ret)
-        rets = torch.stack(rets[::-1])
-    values = model.value(O)
-    adv = rets - values.detach()
-    logp = model.dist(O).log_prob(A_).sum(-1)
-    n_use = U.sum().clamp(min=1.0)
-    ploss, vloss = -(adv * logp * U).sum() / n_use, (((rets - values) ** 2) * U).sum() / n_use
-    ent = (model.log_std + 0.5 + 0.5 * math.log(2.0 * math.pi)).sum()
-    loss = ploss + h["vf_coef"] * vloss - h["ent_coef"] * ent
-    f = lambda x: float(x.detach())
-    return loss, rets, {"policy_loss": f(ploss), "value_loss": f(vloss), "entropy": f(ent), "n_use": f(n_use), "policy_abs": f((adv * logp * U).abs().sum() / n_use)}
+    r = {k: t(b[k]) for k in ("obs", "action", "reward", "done")}
+    r["use"] = torch.ones_like(r["reward"]) if b["use"] is None else t(b["use"])
+    return r, t(b["last_obs"])
+
+
+def torch_loss(model, b, h):
+    rollout, last = rollout_of(b, model.log_std.dtype)
+    loss, rets, t = TR.a2c_loss(model, rollout, last, h["gamma"], h["vf_coef"], h["ent_coef"])
+    st = {k: float(t[k].detach()) for k in ("policy_loss", "value_loss", "entropy", "n_use")}
+    st["policy_abs"] = float((t["adv"] * t["logp"].detach() * t["use"]).abs().sum() / t["n_use"])
+    return loss, rets, st
 
 
 def torch_grad(model, b, h, dtype):
@@ -168,11 +159,7 @@ def torch_updates(model, batches, h, dtype):
     m = copy.deepcopy(model).to(dtype)
     opt = torch.optim.RMSprop(m.parameters(), lr=h["lr"], alpha=h["alpha"], eps=h["eps"])
     for b in batches:
-        loss, _, _ = torch_loss(m, b, h)
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        nn.utils.clip_grad_norm_(m.parameters(), h["max_grad_norm"])
-        opt.step()
+        TR.a2c_update(m, opt, *rollout_of(b, dtype), h["gamma"], h["vf_coef"], h["ent_coef"], h["max_grad_norm"])
     return m, opt
 
 

@@ -1,18 +1,18 @@
 """ctypes view of tests/hostbuild_ppo (g++ -ffp-contract=off build of csrc/xarm_ppo_core.h) - CPU-side tests only - with the batches,
-the permutations, the test old_logp and a torch restatement (float64 / float32) of the PPO update of DESIGN.md 22 that the host and
-GPU tests share.  Models, rows, the rule and the yardstick come from a2c_host / policy_host."""
+the permutations, the test old_logp and the torch reference - train.py's ppo_prepare, ppo_minibatch_loss and optimizer_step on float64 /
+float32 copies of the model - that the host and GPU tests share.  Models, rows, the rule and the yardstick come from a2c_host /
+policy_host."""
 import copy
 import ctypes as C
-import math
 import os
 import subprocess
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 import a2c_host as AH
 import policy_host as PH
+from gym_xarm_amd import train as TR
 
 ROOT = PH.ROOT
 DIR = os.path.join(ROOT, "tests", "hostbuild_ppo")
@@ -120,7 +120,7 @@ def host_update(w, m, v, step, b, h, perm, batch_size, old_logp=None):
     return rc, out
 
 
-# ---- torch: the update of DESIGN.md 22 in the model's dtype
+# ---- torch: train.py's own PPO functions on the batch, in the model's dtype
 def _t(a, dt):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dt)
 
@@ -128,50 +128,18 @@ def _t(a, dt):
 def torch_prepare(model, b, h, old_logp=None):
     """(adv, ret, old_logp, use), flat [N], from the model as it is (no gradient)"""
     dt = model.log_std.dtype
-    O, A_, rew, done, last = (_t(b[k], dt) for k in ("obs", "action", "reward", "done", "last_obs"))
-    U = torch.ones_like(rew) if b["use"] is None else _t(b["use"], dt)
-    T = O.shape[0]
-    with torch.no_grad():
-        values = model.value(O)
-        olp = model.dist(O).log_prob(A_).sum(-1) if old_logp is None else _t(old_logp, dt)
-        nv, na, advs = model.value(last), torch.zeros_like(rew[0]), []
-        for k in reversed(range(T)):
-            keep = (done[k] == 0).to(dt)
-            delta = rew[k] + h["gamma"] * keep * nv - values[k]
-            na = delta + h["gamma"] * h["gae_lambda"] * keep * na
-            nv = values[k]
-            advs.append(na)
-        adv = torch.stack(advs[::-1])
-    return adv.flatten(), (adv + values).flatten(), olp.flatten(), U.flatten()
+    return TR.ppo_prepare(model, *AH.rollout_of(b, dt), h["gamma"], h["gae_lambda"], None if old_logp is None else _t(old_logp, dt))
 
 
 def torch_step_loss(model, b, h, prep, idx):
     """the loss of one minibatch (idx: valid rows in position order) and what the tests read of it"""
-    dt = model.log_std.dtype
-    adv, ret, olp, U = prep
-    D, A = b["obs"].shape[2], b["action"].shape[2]
-    O, A_ = _t(b["obs"], dt).reshape(-1, D)[idx], _t(b["action"], dt).reshape(-1, A)[idx]
-    u, a = U[idx], adv[idx]
-    n = float(u.sum())
-    n_use = max(n, 1.0)
-    if h["normalize_advantage"] and n > 1.0:
-        mu = (a * u).sum() / n
-        a = (a - mu) / (((((a - mu) ** 2) * u).sum() / (n - 1.0)).sqrt() + 1e-8)
-    logp = model.dist(O).log_prob(A_).sum(-1)
-    lr = logp - olp[idx]
-    rho = lr.exp()
-    eps = h["clip_range"]
-    surr = torch.min(rho * a, rho.clamp(1.0 - eps, 1.0 + eps) * a)
-    value = model.value(O)
-    ploss, vloss = -(surr * u).sum() / n_use, (((ret[idx] - value) ** 2) * u).sum() / n_use
-    ent = (model.log_std + 0.5 + 0.5 * math.log(2.0 * math.pi)).sum()
-    loss = ploss + h["vf_coef"] * vloss - h["ent_coef"] * ent
-    f = lambda x: float(x.detach())
-    rd = rho.detach()
-    st = {"policy_loss": f(ploss), "value_loss": f(vloss), "entropy": f(ent), "n_use": n_use, "approx_kl": f((((rd - 1.0) - lr.detach()) * u).sum() / n_use),
-          "clip_fraction": f((((rd - 1.0).abs() > eps).to(dt) * u).sum() / n_use), "policy_abs": f((surr.detach().abs() * u).sum() / n_use),
-          "kl_abs": f((((rd - 1.0).abs() + lr.detach().abs()) * u).sum() / n_use),
-          "rho": rd.numpy().astype(np.float64), "ahat": a.detach().numpy().astype(np.float64), "use": u.numpy().astype(np.float64)}
+    loss, t = TR.ppo_minibatch_loss(model, AH.rollout_of(b, model.log_std.dtype)[0], prep, idx, h["clip_range"], h["vf_coef"], h["ent_coef"],
+                                    bool(h["normalize_advantage"]), diagnostics=True)
+    t = {k: v.detach() for k, v in t.items()}
+    st = {k: float(t[k]) for k in ("policy_loss", "value_loss", "entropy", "n_use", "approx_kl", "clip_fraction")}
+    st["policy_abs"] = float((t["surr"].abs() * t["use"]).sum() / t["n_use"])
+    st["kl_abs"] = float((((t["rho"] - 1.0).abs() + t["log_ratio"].abs()) * t["use"]).sum() / t["n_use"])
+    st.update(rho=t["rho"].numpy().astype(np.float64), ahat=t["a_hat"].numpy().astype(np.float64), use=t["use"].numpy().astype(np.float64))
     return loss, st
 
 
@@ -198,14 +166,11 @@ def torch_update(model, b, h, perm, batch_size, dtype, old_logp=None, n_steps=No
     recs = []
     for s in range(S if n_steps is None else min(S, n_steps)):
         loss, st = torch_step_loss(m, b, h, prep, step_rows(perm, N, batch_size, s))
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        g = np.concatenate([p.grad.detach().numpy().astype(np.float64).ravel() for p in PH.model_params(m)])
+        g = np.concatenate([x.numpy().astype(np.float64).ravel() for x in torch.autograd.grad(loss, PH.model_params(m), retain_graph=True)])
         st["grad_norm"] = float(np.sqrt((g * g).sum()))
         st["grad"] = g
         recs.append(st)
-        nn.utils.clip_grad_norm_(m.parameters(), h["max_grad_norm"])
-        opt.step()
+        TR.optimizer_step(m, opt, loss, h["max_grad_norm"])
     return m, opt, recs, prep
 
 

@@ -2,6 +2,7 @@
 (:74), best-model-on-mean-reward checkpoint (:16-47) and VecNormalize save / load (:107-108, display.py:22).  CPU tests on
 a scripted stand-in VecEnv (torch CPU tensors, same call surface as gym_xarm_amd's VecEnv); the GPU learning test in
 tests/test_reach.py runs the same code on the real env."""
+import copy
 import os
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 import torch
 
 from gym_xarm_amd.train import EpisodeMonitor, SaveOnBestTrainingRewardCallback, VecNormalize, ActorCritic, save_model, load_model, train
+from gym_xarm_amd.train import TorchA2C, TorchPPO, a2c_update, ppo_update
 
 
 class ScriptedEnv:
@@ -169,3 +171,39 @@ def test_best_model_window_covers_every_env():
     mon.update(rew, torch.ones(E, dtype=torch.uint8))      # all E envs finish in the same call
     assert abs(mon.mean_reward(100) - float(rew[-100:].mean())) < 1e-4      # the biased corner
     assert abs(mon.mean_reward(max(100, E)) - float(rew.mean())) < 1e-4
+
+
+@pytest.mark.parametrize("lazy", [False, True])
+@pytest.mark.parametrize("algo", ["a2c", "ppo"])
+def test_torch_learner_update_is_its_update_function_on_the_stacked_rollout(algo, lazy):
+    """TorchA2C / TorchPPO filled through store() over a scripted rollout, against a2c_update / ppo_update called directly on the
+    stacked rows of the same rollout (the lazy-reset mask formed here) from a twin of the model: the parameters agree bit for bit"""
+    E, T = 16, 8
+    env = ScriptedEnv(E, lazy=lazy)
+    venv = VecNormalize(env)
+    torch.manual_seed(3)
+    model = ActorCritic(venv.dim, env.act_dim)
+    twin, start = copy.deepcopy(model), copy.deepcopy(model)
+    if algo == "ppo":
+        learner, update, kw = TorchPPO(model, E, n_steps=T, n_epochs=2, batch_size=48), ppo_update, dict(n_epochs=2, batch_size=48)
+        opt = torch.optim.Adam(twin.parameters(), lr=3e-4, eps=1e-5)
+    else:
+        learner, update, kw = TorchA2C(model, E, n_steps=T), a2c_update, {}
+        opt = torch.optim.RMSprop(twin.parameters(), lr=7e-4, alpha=0.99, eps=1e-5)
+    obs, rows = venv.reset(), []
+    for k in range(T):
+        with torch.no_grad():
+            a = model.dist(obs).sample()
+        nobs, nrew, done, info, _ = venv.step(a.clamp(-1, 1))
+        learner.store(k, obs, a, nrew, done, info.get("resetting"))
+        r = info["resetting"].float() if lazy else torch.zeros(E)
+        rows.append((obs, a, nrew * (1.0 - r), torch.maximum(done.float(), r), 1.0 - r))
+        obs = nobs
+    rollout = {k: torch.stack(v) for k, v in zip(("obs", "action", "reward", "done", "use"), zip(*rows))}
+    assert (rollout["use"].sum() < T * E) == lazy and rollout["done"].sum() > 0
+    torch.manual_seed(11)
+    learner.update(obs)
+    torch.manual_seed(11)
+    update(twin, opt, rollout, obs, **kw)
+    for p, q, p0 in zip(model.parameters(), twin.parameters(), start.parameters()):
+        assert torch.equal(p, q) and not torch.equal(p, p0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the A2C update with device events: train.py's torch block - bootstrap value, return loop, the second forward under autograd,
+"""Time the A2C update with device events: train.py's a2c_update - bootstrap value, return loop, the second forward under autograd,
 backward, clip_grad_norm_ and RMSprop.step - against device_a2c.py's DeviceA2C.update (six HIP launches).  Median of 3 warmed
 windows of 50 updates per leg.
 
@@ -18,12 +18,11 @@ import os
 import sys
 
 import torch
-import torch.nn as nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gym_xarm_amd.device_a2c import DeviceA2C  # noqa: E402
-from gym_xarm_amd.train import ActorCritic, train  # noqa: E402
+from gym_xarm_amd.train import ActorCritic, a2c_update, train  # noqa: E402
 
 CALLS = 50
 WIDTHS = {"XarmReach-v0": 14, "XarmPDPickAndPlace-v0": 30}
@@ -79,27 +78,10 @@ def main():
             b["reward"].normal_()
             b["done"].copy_((torch.rand(N_STEPS, E, device="cuda") < 0.04).float())
             last = (torch.rand(E, D, device="cuda") * 2 - 1) * 3
-            obs_buf, act_buf, rew_buf, done_buf, use_buf = [[b[k][i].clone() for i in range(N_STEPS)] for k in ("obs", "action", "reward", "done", "use")]
+            rollout = {k: b[k].clone() for k in ("obs", "action", "reward", "done", "use")}
 
             def torch_call():
-                # gym_xarm_amd/train.py, the update block of train(), as it stands
-                with torch.no_grad():
-                    ret = model_t.value(last)
-                    rets = []
-                    for k in reversed(range(N_STEPS)):
-                        ret = rew_buf[k] + GAMMA * ret * (1.0 - done_buf[k])
-                        rets.append(ret)
-                    rets = torch.stack(rets[::-1])
-                O, A, U = torch.stack(obs_buf), torch.stack(act_buf), torch.stack(use_buf)
-                values = model_t.value(O)
-                adv = rets - values.detach()
-                logp = model_t.dist(O).log_prob(A).sum(-1)
-                n_use = U.sum().clamp(min=1.0)
-                loss = -(adv * logp * U).sum() / n_use + 0.5 * (((rets - values) ** 2) * U).sum() / n_use
-                opt.zero_grad(set_to_none=True)
-                loss.backward()
-                nn.utils.clip_grad_norm_(model_t.parameters(), 0.5)
-                opt.step()
+                a2c_update(model_t, opt, rollout, last, GAMMA)       # what train() runs per update without device_update
 
             def hip_call():
                 a2c.update(last)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the PPO update with device events: train.py's torch PPO block - values and old log-probabilities, the GAE loop, and per
+"""Time the PPO update with device events: train.py's ppo_update - values and old log-probabilities, the GAE loop, and per
 minibatch the forward under autograd, the normalised clipped surrogate, backward, clip_grad_norm_ and Adam.step - against
 device_ppo.py's DevicePPO.update (4 + 3 S HIP launches).  Median of 3 warmed windows of 10 updates per leg.
 
@@ -19,12 +19,11 @@ import os
 import sys
 
 import torch
-import torch.nn as nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gym_xarm_amd.device_ppo import DevicePPO  # noqa: E402
-from gym_xarm_amd.train import ActorCritic  # noqa: E402
+from gym_xarm_amd.train import ActorCritic, ppo_update  # noqa: E402
 
 CALLS = 10
 WIDTHS = {"XarmReach-v0": 14, "XarmPDPickAndPlace-v0": 30}
@@ -84,40 +83,11 @@ def main():
             b["reward"].normal_()
             b["done"].copy_((torch.rand(N_STEPS, E, device="cuda") < 0.04).float())
             last = (torch.rand(E, D, device="cuda") * 2 - 1) * 3
-            obs_buf, act_buf, rew_buf, done_buf, use_buf = [[b[k][i].clone() for i in range(N_STEPS)] for k in ("obs", "action", "reward", "done", "use")]
+            rollout = {k: b[k].clone() for k in ("obs", "action", "reward", "done", "use")}
 
             def torch_call():
-                # gym_xarm_amd/train.py, the PPO update block of train(), as it stands
-                O, A, U = torch.stack(obs_buf).flatten(0, 1), torch.stack(act_buf).flatten(0, 1), torch.stack(use_buf).flatten()
-                with torch.no_grad():
-                    values = model_t.value(torch.stack(obs_buf))
-                    old_logp = model_t.dist(O).log_prob(A).sum(-1)
-                    next_value, next_adv, advs = model_t.value(last), torch.zeros(E, device="cuda"), []
-                    for k in reversed(range(N_STEPS)):
-                        keep = 1.0 - done_buf[k]
-                        delta = rew_buf[k] + GAMMA * keep * next_value - values[k]
-                        next_adv = delta + GAMMA * LAMBDA * keep * next_adv
-                        next_value = values[k]
-                        advs.append(next_adv)
-                    adv = torch.stack(advs[::-1])
-                    rets, adv = (adv + values).flatten(), adv.flatten()
-                for _ in range(N_EPOCHS):
-                    perm = torch.randperm(n_rows, device="cuda")
-                    for m in range(0, n_rows, batch_size):
-                        idx = perm[m:m + batch_size]
-                        u, a_mb = U[idx], adv[idx]
-                        n = u.sum()
-                        n_use = n.clamp(min=1.0)
-                        mu = (a_mb * u).sum() / n_use
-                        sigma = ((((a_mb - mu) ** 2) * u).sum() / (n - 1.0).clamp(min=1.0)).sqrt()
-                        a_hat = torch.where(n > 1.0, (a_mb - mu) / (sigma + 1e-8), a_mb)
-                        ratio = (model_t.dist(O[idx]).log_prob(A[idx]).sum(-1) - old_logp[idx]).exp()
-                        surr = torch.min(ratio * a_hat, ratio.clamp(1.0 - CLIP, 1.0 + CLIP) * a_hat)
-                        loss = -(surr * u).sum() / n_use + 0.5 * (((rets[idx] - model_t.value(O[idx])) ** 2) * u).sum() / n_use
-                        opt.zero_grad(set_to_none=True)
-                        loss.backward()
-                        nn.utils.clip_grad_norm_(model_t.parameters(), 0.5)
-                        opt.step()
+                # what train(algo="ppo") runs per update without device_update
+                ppo_update(model_t, opt, rollout, last, N_EPOCHS, batch_size, GAMMA, LAMBDA, CLIP)
 
             def hip_call():
                 ppo.update(last)
