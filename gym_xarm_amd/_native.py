@@ -24,7 +24,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
            "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update",
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
-           "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update"]
+           "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update",
+           "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -154,6 +155,21 @@ class XarmSACWWeights(C.Structure):
     _fields_ = [(k, C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))) for k in SAC_TOWERS] + [("log_alpha", C.c_void_p)]
 
 
+class XarmACWLayout(C.Structure):
+    """include/xarm_hip.h xarm_acw_layout (40 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("num_rows", "obs_dim", "goal_dim", "act_dim", "hidden", "n_hidden", "activation")] + [("row_offset", C.c_int64)]
+
+
+class XarmACWWeights(C.Structure):
+    """include/xarm_hip.h xarm_acw_weights (17 device pointers): pi and vf as W1, b1, ..., W_out, b_out (eight slots each) and log_std"""
+    _fields_ = [("pi", C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))), ("vf", C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))), ("log_std", C.c_void_p)]
+
+
+class XarmPPOWLayout(C.Structure):
+    """include/xarm_hip.h xarm_ppow_layout (36 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("num_envs", "n_steps", "obs_dim", "act_dim", "hidden", "n_hidden", "activation", "n_epochs", "batch_size")]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -222,6 +238,12 @@ def load(path=None):
     L.xarm_sacw_workspace_bytes.argtypes = [wl, C.POINTER(C.c_int64)]
     L.xarm_sacw_act.argtypes = [wl, sp, ww] + [vp] * 6
     L.xarm_sacw_update.argtypes = [wl, sp, ww, ww, ww] + [vp] * 16
+    cl = C.POINTER(XarmACWLayout)
+    L.xarm_acw_workspace_bytes.argtypes = [cl, C.POINTER(C.c_int64)]
+    L.xarm_acw_act.argtypes = [cl, C.POINTER(XarmPolicyParams), C.POINTER(XarmACWWeights)] + [vp] * 11
+    ql, cw = C.POINTER(XarmPPOWLayout), C.POINTER(XarmACWWeights)
+    L.xarm_ppow_workspace_bytes.argtypes = [ql, C.POINTER(C.c_int64)]
+    L.xarm_ppow_update.argtypes = [ql, C.POINTER(XarmPPOParams), cw, cw, cw] + [vp] * 15
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

@@ -38,6 +38,8 @@
 #include "xarm_ppo_core.h"
 #include "xarm_sac_core.h"
 #include "xarm_sacw_core.h"
+#include "xarm_acw_core.h"
+#include "xarm_ppow_core.h"
 
 using namespace xd;
 
@@ -1199,6 +1201,68 @@ int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *para
     d.out_grad = out_grad; d.out_dqda = out_dqda; d.out_target = out_target; d.out_stats = out_stats; d.out_q = out_q;
     const int le = xsacw::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sacw_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ wide MlpPolicy (xarm_k_acw.hip)
+int xarm_acw_workspace_bytes(const xarm_acw_layout *layout, int64_t *bytes) {
+    if (const char *why = xacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_acw_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_acw_workspace_bytes: NULL pointer");
+    xacw::Dev d = {};
+    xacw::fill_shape(d, layout);
+    *bytes = xacw::fill_work(d, nullptr);
+    return XARM_OK;
+}
+
+int xarm_acw_act(const xarm_acw_layout *layout, const xarm_policy_params *params, const xarm_acw_weights *weights, const double *stats,
+                 int64_t *calls_i64, const float *obs, const float *achieved_goal, const float *desired_goal, void *workspace, float *out_action,
+                 float *out_env_action, float *out_logp, float *out_value, void *stream) {
+    if (const char *why = xacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_acw_act: %s", why);
+    if (const char *why = xpol::params_error(params, stats != nullptr)) return fail(nullptr, XARM_E_INVALID, "xarm_acw_act: %s", why);
+    if (!weights) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_acw_act: weights is NULL");
+    if (layout->num_rows == 0) return XARM_OK;
+    if (const char *why = xacw::pointer_error(layout, params, weights, calls_i64, obs, achieved_goal, desired_goal, workspace, out_value))
+        return fail(nullptr, XARM_E_INVALID, "xarm_acw_act: %s", why);
+    xacw::Dev d = {};
+    xacw::fill_dev(d, layout, params, weights, stats, calls_i64, obs, achieved_goal, desired_goal, workspace, out_action, out_env_action, out_logp,
+                   out_value);
+    const int le = xacw::launch_act(d, calls_i64, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_acw_act: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ wide PPO update (xarm_k_ppow.hip)
+int xarm_ppow_workspace_bytes(const xarm_ppow_layout *layout, int64_t *bytes) {
+    if (const char *why = xppow::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppow_workspace_bytes: NULL pointer");
+    xppow::Dev d = {};
+    xppow::fill_shape(d, layout);
+    *bytes = xppow::fill_work(d, nullptr);
+    return XARM_OK;
+}
+
+int xarm_ppow_update(const xarm_ppow_layout *layout, const xarm_ppo_params *params, const xarm_acw_weights *weights, const xarm_acw_weights *exp_avg,
+                     const xarm_acw_weights *exp_avg_sq, int64_t *step_i64, const float *obs, const float *action, const float *reward,
+                     const float *done, const float *use, const float *last_obs, const float *old_logp, const int32_t *perm, void *workspace,
+                     float *out_adv, float *out_returns, float *out_grad, float *out_stats, void *stream) {
+    if (const char *why = xppow::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
+    if (const char *why = xppo::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
+    if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppow_update: weights / exp_avg / exp_avg_sq is NULL");
+    if (layout->num_envs == 0) return XARM_OK;
+    if (const char *why = xppow::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, last_obs, perm, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
+    xppow::Dev d = {};
+    xppow::fill_shape(d, layout);
+    xppo::fill_hyper(d.h, params);
+    xppow::tensors_of(d, weights, d.w);
+    xppow::tensors_of(d, exp_avg, d.m);
+    xppow::tensors_of(d, exp_avg_sq, d.v);
+    xppow::fill_work(d, workspace);
+    d.step = step_i64;
+    d.obs = obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.last_obs = last_obs; d.old_logp = old_logp; d.perm = perm;
+    d.out_adv = out_adv; d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
+    const int le = xppow::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_ppow_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -102,6 +102,16 @@ inline const char *pointer_error(const xarm_sacw_layout *l, const xarm_sacw_weig
 inline int in_of(const Shape &s, int l, int Din) { return l == 0 ? Din : s.H; }
 inline int out_of(const Shape &s, int l, int nout) { return l == s.NL - 1 ? nout : s.H; }
 
+// the row ranges of a weight gradient over s.B rows: the 64-row tiles dealt in order to S = min(16, tiles) contiguous ranges
+inline void fill_ranges(Shape &s) {
+    const int64_t tiles = (s.B + SPLIT_ROWS - 1) / SPLIT_ROWS;
+    s.S = (int)(tiles < MAX_SPLIT ? (tiles > 0 ? tiles : 1) : MAX_SPLIT);
+    for (int k = 0; k <= MAX_SPLIT; k++) {
+        const int64_t r = k >= s.S ? s.B : (tiles * k / s.S) * SPLIT_ROWS;
+        s.rows[k] = r < s.B ? r : s.B;
+    }
+}
+
 inline void fill_shape(Shape &s, const xarm_sacw_layout *l) {
     s.B = l->batch_size; s.D = l->obs_dim; s.A = l->act_dim; s.Dq = s.D + s.A; s.H = l->hidden; s.L = l->n_hidden; s.NL = s.L + 1;
     s.act = l->activation; s.row_offset = l->row_offset; s.tp = 2 * s.NL; s.NT = 3 * s.tp + 1; s.BH = s.B * s.H;
@@ -115,12 +125,7 @@ inline void fill_shape(Shape &s, const xarm_sacw_layout *l) {
         }
     s.off[s.NT] = s.off[s.NT - 1] + 1;
     s.Pa = s.off[s.tp]; s.Pq = s.off[2 * s.tp] - s.off[s.tp]; s.P = s.off[s.NT];
-    const int64_t tiles = (s.B + SPLIT_ROWS - 1) / SPLIT_ROWS;
-    s.S = (int)(tiles < MAX_SPLIT ? (tiles > 0 ? tiles : 1) : MAX_SPLIT);
-    for (int k = 0; k <= MAX_SPLIT; k++) {
-        const int64_t r = k >= s.S ? s.B : (tiles * k / s.S) * SPLIT_ROWS;
-        s.rows[k] = r < s.B ? r : s.B;
-    }
+    fill_ranges(s);
 }
 
 // the trained tensors of a weights struct in the flat order; tq: the 2 tp target tensors
@@ -228,11 +233,10 @@ template <class X> void bd_pass(const Shape &s, X &ex, int nj, const TowerRef *T
 }
 
 // every layer's weight and bias gradient of towers T[j] in one launch; tower j's slice starts at base[j] of a range's partial
-template <class X> void wg_pass(const Dev &d, X &ex, int nj, const TowerRef *T, const float *const *in, const float *const *dO, float *const *hid,
-                                float *const *dH, const int64_t *base, const int *t0, int64_t pstride) {
-    const Shape &s = d.s;
+template <class X> void wg_pass(const Shape &s, float *partial, X &ex, int nj, const TowerRef *T, const float *const *in, const float *const *dO,
+                                float *const *hid, float *const *dH, const int64_t *base, const int *t0, int64_t pstride) {
     Wg f = {};
-    f.S = s.S; f.pstride = pstride; f.partial = d.partial;
+    f.S = s.S; f.pstride = pstride; f.partial = partial;
     for (int k = 0; k <= MAX_SPLIT; k++) f.rows[k] = s.rows[k];
     for (int j = 0; j < nj; j++)
         for (int l = 0; l < s.NL; l++) {
@@ -417,7 +421,7 @@ template <class X> void run_update(const Dev &d, X &ex) {
         const int64_t base[2] = {0, s.Pq};
         const int t0[2] = {tp, 2 * tp};
         bd_pass(s, ex, 2, T, dO, hid, dh);
-        wg_pass(d, ex, 2, T, in, dO, hid, dh, base, t0, 2 * s.Pq);
+        wg_pass(s, d.partial, ex, 2, T, in, dO, hid, dh, base, t0, 2 * s.Pq);
     }
     ex.apply(d, s.Pa, 2 * s.Pq, 2 * s.Pq, true, false);
     {
@@ -443,7 +447,7 @@ template <class X> void run_update(const Dev &d, X &ex) {
         const int64_t base[1] = {0};
         const int t0[1] = {0};
         bd_pass(s, ex, 1, T, dO, hid, dh);
-        wg_pass(d, ex, 1, T, in, dO, hid, dh, base, t0, s.Pa);
+        wg_pass(s, d.partial, ex, 1, T, in, dO, hid, dh, base, t0, s.Pa);
     }
     ex.apply(d, 0, s.Pa, s.Pa, false, true);
 }

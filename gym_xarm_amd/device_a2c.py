@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from . import _native
+from .device_policy import is_tile64, tower_shape
 from .train import rollout_buffers, store_rollout  # noqa: F401  (store_rollout is re-exported)
 
 HYPER = ("gamma", "lr", "alpha", "eps", "vf_coef", "ent_coef", "max_grad_norm")
@@ -75,9 +76,10 @@ class DeviceA2C:
         self.model, self.num_envs, self.n_steps = model, int(num_envs), int(n_steps)
         self.hyper = dict(gamma=gamma, lr=lr, alpha=alpha, eps=eps, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm)
         self.obs_width = int(model.pi[0].in_features)
-        self.act_dim = int(model.pi[4].out_features)
-        if int(model.pi[0].out_features) != _native.POLICY_HIDDEN or int(model.pi[2].out_features) != _native.POLICY_HIDDEN:
-            raise ValueError("DeviceA2C updates 64-64 towers (XARM_POLICY_HIDDEN)")
+        self.act_dim = int(model.pi[-1].out_features)
+        if not is_tile64(model):
+            raise ValueError("DeviceA2C updates 64-64 tanh towers (XARM_POLICY_HIDDEN), not %s %s; train.a2c_update is the torch "
+                             "implementation for every other shape" % tuple(map(str, tower_shape(model))))
         self.device = model.log_std.device
         if self.device.type != "cuda":
             raise ValueError("DeviceA2C runs the update with HIP kernels on the model's GPU: the model is on '%s'.  There is no host "

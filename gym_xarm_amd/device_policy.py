@@ -14,8 +14,36 @@ import torch
 from . import _native
 
 
+def tower_shape(model):
+    """(hidden widths, activation) of a train.ActorCritic, read off `pi`'s Linear layers and the recorded `activation`"""
+    linears = [m for m in model.pi if isinstance(m, torch.nn.Linear)]
+    return tuple(int(m.out_features) for m in linears[:-1]), str(getattr(model, "activation", "tanh"))
+
+
+def is_tile64(model):
+    """the 64-64 tanh shape of the fused kernels (xarm_policy_act, xarm_a2c_update, xarm_ppo_update)"""
+    return tower_shape(model) == ((_native.POLICY_HIDDEN, _native.POLICY_HIDDEN), "tanh")
+
+
+def wide_supported(model):
+    widths, activation = tower_shape(model)
+    return (len(widths) in (2, _native.SACW_MAX_LAYERS) and len(set(widths)) == 1 and widths[0] in _native.SACW_WIDTHS
+            and activation in _native.SACW_ACTIVATIONS)
+
+
+def tower_params(model):
+    """(pi's tensors W1, b1, ..., W_out, b_out; vf's) of a train.ActorCritic of any depth"""
+    return tuple(tuple(t for m in tower if isinstance(m, torch.nn.Linear) for t in (m.weight, m.bias)) for tower in (model.pi, model.vf))
+
+
 class DevicePolicy:
     """`ActorCritic`'s inference on the device: `act`, `act_into`, `predict`.
+
+    `backend`: "tile64" - the fused kernel of DESIGN.md 20, one launch, for a 64-64 tanh model - or "wide" - a layer-by-layer forward on
+    the f32 MFMA GEMM kernel of the wide SAC (csrc/xarm_k_acw.hip), n_hidden + 3 launches, for equal widths of 64, 128,
+    192 or 256 units in two or three layers, tanh or ReLU.  wide None: "tile64" for a 64-64 tanh model and "wide" for every other
+    supported shape; wide=True forces "wide".  act_rows: the most rows a call will carry on the wide backend (default 0: the first call
+    sizes it) - its activations live in ONE workspace tensor; `reserve_act(rows)` sizes it before a capture.
 
     model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors.  Their `data_ptr()`s are read on every
     call, so an in-place optimiser step or `load_state_dict` is seen by the next call with no repacking.  A captured
@@ -28,19 +56,28 @@ class DevicePolicy:
 
     `act_into(out, obs)` runs with no allocation and no host read on the current stream and can be captured."""
 
-    def __init__(self, model, seed=0, row_offset=0):
+    def __init__(self, model, seed=0, row_offset=0, wide=None, act_rows=None):
         self.model, self.seed, self.row_offset = model, int(seed), int(row_offset)
         self.obs_width = int(model.pi[0].in_features)
-        self.act_dim = int(model.pi[4].out_features)
-        if int(model.pi[0].out_features) != _native.POLICY_HIDDEN or int(model.pi[2].out_features) != _native.POLICY_HIDDEN:
-            raise ValueError("DevicePolicy evaluates 64-64 towers (XARM_POLICY_HIDDEN)")
+        self.act_dim = int(model.pi[-1].out_features)
+        self.widths, self.activation = tower_shape(model)
+        if wide is False and not is_tile64(model):
+            raise ValueError("DevicePolicy: the fused kernel (wide=False) evaluates 64-64 tanh towers (XARM_POLICY_HIDDEN), not %s %s"
+                             % (list(self.widths), self.activation))
+        self.backend = "tile64" if is_tile64(model) and not wide else "wide"
+        if self.backend == "wide" and not wide_supported(model):
+            raise ValueError("DevicePolicy evaluates 64-64 tanh towers (the fused kernel) and equal-width towers of 2 or 3 hidden layers of 64, 128, 192 or 256 units, tanh or relu, "
+                             "not %s %s; ActorCritic.dist is the torch implementation for every other shape" % (list(self.widths), self.activation))
         if self.obs_width > _native.POLICY_MAX_DIM or not 1 <= self.act_dim <= _native.POLICY_MAX_ACT:
             raise ValueError("DevicePolicy: observation width %d (<= %d) / action width %d (1..%d) out of range"
                              % (self.obs_width, _native.POLICY_MAX_DIM, self.act_dim, _native.POLICY_MAX_ACT))
         self.device = model.log_std.device
-        self._L = self.calls = None
+        self._L = self.calls = self._act_work = None
+        self._act_rows = 0
         if self.device.type == "cuda":
             self._lib()
+            if self.backend == "wide" and act_rows:
+                self.reserve_act(act_rows)
 
     def _lib(self):
         if self._L is None:
@@ -52,9 +89,33 @@ class DevicePolicy:
         return self._L
 
     def _params(self):
-        m = self.model
-        return (m.pi[0].weight, m.pi[0].bias, m.pi[2].weight, m.pi[2].bias, m.pi[4].weight, m.pi[4].bias,
-                m.vf[0].weight, m.vf[0].bias, m.vf[2].weight, m.vf[2].bias, m.vf[4].weight, m.vf[4].bias, m.log_std)
+        pi, vf = tower_params(self.model)
+        return pi + vf + (self.model.log_std,)
+
+    def _wide_layout(self, rows, od, gd):
+        return _native.XarmACWLayout(int(rows), od, gd, self.act_dim, self.widths[0], len(self.widths), _native.SACW_ACTIVATIONS[self.activation],
+                                     self.row_offset)
+
+    def reserve_act(self, rows):
+        """wide backend: make the act call's workspace hold `rows` rows (one tensor, kept; a call with more rows than it holds grows it,
+        which allocates - reserve before a capture)"""
+        if self.backend != "wide" or int(rows) <= self._act_rows:
+            return
+        L, nbytes = self._lib(), C.c_int64(0)
+        _native.check(L, None, L.xarm_acw_workspace_bytes(C.byref(self._wide_layout(rows, self.obs_width, 0)), C.byref(nbytes)), "xarm_acw_workspace_bytes")
+        self._act_work = torch.zeros(max(nbytes.value, 16) // 4, dtype=torch.float32, device=self.device)
+        self._act_rows = int(rows)
+
+    def _wide_weights(self):
+        pi, vf = tower_params(self.model)
+        w = _native.XarmACWWeights()
+        for name, ts in (("pi", pi), ("vf", vf)):
+            for i, t in enumerate(ts):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("DevicePolicy needs contiguous float32 parameters on %s (%s[%d])" % (self.device, name, i))
+                getattr(w, name)[i] = t.data_ptr()
+        w.log_std = self.model.log_std.data_ptr()
+        return w
 
     def _weights(self):
         w = _native.XarmPolicyWeights()
@@ -83,7 +144,7 @@ class DevicePolicy:
                 "logp": torch.empty(E, device=dev), "value": torch.empty(E, device=dev)}
 
     def act_into(self, out, obs, deterministic=False, normalize=None):
-        """One launch (plus the counter tick of a stochastic call) on the current stream: out["action"] [E, A], out["env_action"]
+        """One launch (n_hidden + 3 on the wide backend; plus the counter tick of a stochastic call) on the current stream: out["action"] [E, A], out["env_action"]
         (clamped to [-1, 1]: what env.step takes), and, where the dict has them, out["logp"] [E] and out["value"] [E] (leave
         "value" out and the value tower is not evaluated).  obs: the env's dict, the flat tensor of a 'NoGoal' env, or an
         already normalised [E, D] tensor.  normalize: a DeviceVecNormalize whose statistics, frozen, normalise the raw
@@ -94,7 +155,6 @@ class DevicePolicy:
         for k, shape in (("action", (E, A)), ("env_action", (E, A)), ("logp", (E,)), ("value", (E,))):
             if k in out:
                 assert out[k].dtype == torch.float32 and out[k].is_contiguous() and out[k].shape == shape and out[k].device == self.device, k
-        layout = _native.XarmPolicyLayout(E, od, gd, A, _native.POLICY_HIDDEN, self.row_offset)
         stats, clip, eps = None, 10.0, 1e-8
         if normalize is not None:
             if int(normalize.dim) != self.obs_width or normalize.stats.device != self.device:
@@ -102,6 +162,14 @@ class DevicePolicy:
             stats, clip, eps = C.c_void_p(normalize.stats.data_ptr()), float(normalize.clip_obs), float(normalize.eps)
         params = _native.XarmPolicyParams(self.seed, clip, eps, 1 if deterministic else 0)
         p = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
+        if self.backend == "wide":
+            self.reserve_act(E)
+            rc = L.xarm_acw_act(C.byref(self._wide_layout(E, od, gd)), C.byref(params), C.byref(self._wide_weights()), stats,
+                                C.c_void_p(self.calls.data_ptr()), *parts, C.c_void_p(self._act_work.data_ptr()), p("action"), p("env_action"),
+                                p("logp"), p("value"), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            _native.check(L, None, rc, "xarm_acw_act")
+            return out
+        layout = _native.XarmPolicyLayout(E, od, gd, A, _native.POLICY_HIDDEN, self.row_offset)
         rc = L.xarm_policy_act(C.byref(layout), C.byref(params), C.byref(self._weights()), stats, C.c_void_p(self.calls.data_ptr()),
                                *parts, p("action"), p("env_action"), p("logp"), p("value"),
                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))

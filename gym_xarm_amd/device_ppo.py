@@ -13,6 +13,7 @@ import torch
 
 from . import _native
 from .device_a2c import module_params, policy_weights
+from .device_policy import is_tile64, tower_params, tower_shape, wide_supported
 from .train import rollout_buffers, store_rollout
 
 
@@ -66,10 +67,17 @@ class DevicePPO:
     model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors; they are read and written in place.
     `buffers` and `store(k, ...)` are DeviceA2C's.  `exp_avg`, `exp_avg_sq` (13 tensors each) and `step` (int64 [1]) are Adam's state,
     `perm` (int32 [n_epochs, N]) the minibatch order: all device tensors.  `stats` [S, 8]: one row per optimiser step of the last update,
-    policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, 0.  batch_size None: ceil(N / 4)."""
+    policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, 0.  batch_size None: ceil(N / 4).
+
+    `backend`: "tile64" - the fused 64-row tile of DESIGN.md 22, 4 + 3 S launches, for a 64-64 tanh model - or "wide" - the per-layer MFMA
+    GEMM chain of DESIGN.md 25 (csrc/xarm_k_ppow.hip) for equal widths of 64, 128, 192 or 256 units in two or three layers, tanh or ReLU,
+    the reference's [256, 256, 256] among them.  wide None: "tile64" for a 64-64 tanh model and "wide" for every other supported shape;
+    wide=True forces "wide".  `exp_avg` / `exp_avg_sq` hold one tensor per parameter in the order of `params()`: pi's tensors, vf's,
+    log_std.  `launches`: the kernels of one update - 4 + 3 S, or on the wide backend c (L + 1) + 2 + S (2 L + 6) with L hidden layers and
+    c = M + ceil(E / B) call-start forward chunks."""
 
     def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
-                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0):
+                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0, wide=None):
         self.model, self.num_envs, self.n_steps, self.n_epochs = model, int(num_envs), int(n_steps), int(n_epochs)
         N = self.num_envs * self.n_steps
         self.batch_size = int(batch_size) if batch_size is not None else max(1, -(-N // 4))
@@ -77,21 +85,34 @@ class DevicePPO:
                           ent_coef=ent_coef, max_grad_norm=max_grad_norm)
         self.normalize_advantage = bool(normalize_advantage)
         self.obs_width = int(model.pi[0].in_features)
-        self.act_dim = int(model.pi[4].out_features)
-        if int(model.pi[0].out_features) != _native.POLICY_HIDDEN or int(model.pi[2].out_features) != _native.POLICY_HIDDEN:
-            raise ValueError("DevicePPO updates 64-64 towers (XARM_POLICY_HIDDEN)")
+        self.act_dim = int(model.pi[-1].out_features)
+        self.widths, self.activation = tower_shape(model)
+        if wide is False and not is_tile64(model):
+            raise ValueError("DevicePPO: the fused tile (wide=False) updates 64-64 tanh towers (XARM_POLICY_HIDDEN), not %s %s"
+                             % (list(self.widths), self.activation))
+        self.backend = "tile64" if is_tile64(model) and not wide else "wide"
+        if self.backend == "wide" and not wide_supported(model):
+            raise ValueError("DevicePPO updates 64-64 tanh towers (the fused tile) and equal-width towers of 2 or 3 hidden layers of 64, 128, 192 or 256 units, tanh or relu, not "
+                             "%s %s; train.ppo_update is the torch implementation for every other shape" % (list(self.widths), self.activation))
         self.device = model.log_std.device
         if self.device.type != "cuda":
             raise ValueError("DevicePPO runs the update with HIP kernels on the model's GPU: the model is on '%s'.  There is no host "
                              "path; the torch PPO block of train.py (autograd, clip_grad_norm_, Adam) is the host implementation." % self.device)
         self._L = _native.load()
         T, E, D, A, dev = self.n_steps, self.num_envs, self.obs_width, self.act_dim, self.device
-        self._layout = _native.XarmPPOLayout(E, T, D, A, _native.POLICY_HIDDEN, self.n_epochs, self.batch_size)
         nbytes = C.c_int64(0)
-        _native.check(self._L, None, self._L.xarm_ppo_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_ppo_workspace_bytes")
         self.minibatches = -(-N // min(self.batch_size, N)) if N > 0 else 0
         self.num_steps = self.n_epochs * self.minibatches
-        self.launches = 4 + 3 * self.num_steps
+        if self.backend == "wide":
+            L = len(self.widths)
+            self._layout = _native.XarmPPOWLayout(E, T, D, A, self.widths[0], L, _native.SACW_ACTIVATIONS[self.activation], self.n_epochs, self.batch_size)
+            _native.check(self._L, None, self._L.xarm_ppow_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_ppow_workspace_bytes")
+            chunks = self.minibatches + (-(-E // min(self.batch_size, N)) if N > 0 else 0)
+            self.launches = chunks * (L + 1) + 2 + self.num_steps * (2 * L + 6)
+        else:
+            self._layout = _native.XarmPPOLayout(E, T, D, A, _native.POLICY_HIDDEN, self.n_epochs, self.batch_size)
+            _native.check(self._L, None, self._L.xarm_ppo_workspace_bytes(C.byref(self._layout), C.byref(nbytes)), "xarm_ppo_workspace_bytes")
+            self.launches = 4 + 3 * self.num_steps
         self.buffers = rollout_buffers(T, E, D, A, dev, nbytes.value)
         self.exp_avg = [torch.zeros_like(p) for p in self.params()]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params()]
@@ -103,7 +124,23 @@ class DevicePPO:
         self._gen.manual_seed(int(seed))
 
     def params(self):
+        """the trained tensors in the flat order of out_grad: pi's W1, b1, ..., vf's, log_std (the 13 of xarm_policy_weights on "tile64")"""
+        if self.backend == "wide":
+            pi, vf = tower_params(self.model)
+            return pi + vf + (self.model.log_std,)
         return module_params(self.model)
+
+    def _wide_weights(self, tensors):
+        tp = (len(tensors) - 1) // 2
+        w = _native.XarmACWWeights()
+        for i, t in enumerate(tensors):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("DevicePPO needs contiguous float32 tensors on %s (tensor %d)" % (self.device, i))
+            if i == 2 * tp:
+                w.log_std = t.data_ptr()
+            else:
+                (w.pi if i < tp else w.vf)[i % tp] = t.data_ptr()
+        return w
 
     def store(self, k, obs, action, reward, done, resetting=None):
         """slot k of the rollout (train.store_rollout)"""
@@ -125,6 +162,13 @@ class DevicePPO:
         b = self.buffers
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         params = _native.XarmPPOParams(*([float(hyper[k]) for k in _native.PPO_HYPER] + [int(self.normalize_advantage)]))
+        args = (p(step), p(b["obs"]), p(b["action"]), p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(old_logp), p(self.perm), p(b["workspace"]),
+                p(out_adv), p(out_returns), p(out_grad), p(out_stats), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if self.backend == "wide":
+            ws = [self._wide_weights(ts) for ts in (weights, exp_avg, exp_avg_sq)]        # held until the call has returned
+            rc = self._L.xarm_ppow_update(C.byref(self._layout), C.byref(params), *[C.byref(x) for x in ws], *args)
+            _native.check(self._L, None, rc, "xarm_ppow_update")
+            return
         W = lambda ts: C.byref(policy_weights(ts, self.device, "DevicePPO"))
         rc = self._L.xarm_ppo_update(C.byref(self._layout), C.byref(params), W(weights), W(exp_avg), W(exp_avg_sq), p(step), p(b["obs"]), p(b["action"]),
                                      p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(old_logp), p(self.perm), p(b["workspace"]), p(out_adv),

@@ -219,8 +219,8 @@ def save_model(path, model, venv):
     from safetensors.torch import save_file
     sd = {"policy." + k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}
     sd.update({"vecnormalize." + k: v.detach().cpu().contiguous() for k, v in venv.state_dict().items()})
-    # a module that records its shape (sac.SacPolicy) has it written beside the tensors, in the file's metadata: the tensors' keys are
-    # the state_dict's for every shape, and sac.load_checkpoint rebuilds the module from the two entries
+    # a module that records its shape (ActorCritic, sac.SacPolicy) has it written beside the tensors, in the file's metadata: the tensors' keys are
+    # the state_dict's for every shape, and load_checkpoint / sac.load_checkpoint rebuild the module from the two entries
     meta = None
     if hasattr(model, "net_arch") and hasattr(model, "activation"):
         meta = {"net_arch": ",".join(str(int(n)) for n in model.net_arch), "activation": str(model.activation)}
@@ -234,13 +234,43 @@ def load_model(path, model, venv):
     venv.load_state_dict({k[len("vecnormalize."):]: v for k, v in sd.items() if k.startswith("vecnormalize.")})
 
 
-class ActorCritic(nn.Module):
-    """SB3 'MlpPolicy': separate 64-64 tanh towers for policy and value, state-independent log-std"""
+def load_checkpoint(path):
+    """(ActorCritic, vecnormalize state) of a checkpoint written by save_model: the module is rebuilt from the metadata entries `net_arch`
+    ("256,256,256") and `activation` (a file without them is the 64-64 tanh shape) before its state_dict is loaded; obs_dim and act_dim
+    are read off the first and the last layer of `pi`.  sac.load_checkpoint is the same for a SacPolicy."""
+    from safetensors import safe_open
+    from safetensors.torch import load_file
+    with safe_open(path, framework="pt") as f:
+        meta = f.metadata() or {}
+    sd = load_file(path)
+    pol = {k[len("policy."):]: v for k, v in sd.items() if k.startswith("policy.")}
+    arch = tuple(int(n) for n in meta["net_arch"].split(",")) if "net_arch" in meta else (64, 64)
+    model = ActorCritic(pol["pi.0.weight"].shape[1], pol["pi.%d.bias" % (2 * len(arch))].shape[0], arch, meta.get("activation", "tanh"))
+    model.load_state_dict(pol)
+    return model, {k[len("vecnormalize."):]: v for k, v in sd.items() if k.startswith("vecnormalize.")}
 
-    def __init__(self, obs_dim, act_dim):
+
+ACTIVATIONS = {"tanh": nn.Tanh, "relu": nn.ReLU}
+
+
+class ActorCritic(nn.Module):
+    """SB3 'MlpPolicy': separate towers for policy and value, `pi` and `vf`, of len(net_arch) hidden layers each (default: 64-64 tanh),
+    and a state-independent log-std.  net_arch: the hidden widths; activation: "tanh" or "relu".  Both are kept as attributes and
+    written into a checkpoint's metadata (save_model, load_checkpoint)."""
+
+    def __init__(self, obs_dim, act_dim, net_arch=(64, 64), activation="tanh"):
         super().__init__()
+        self.net_arch, self.activation = tuple(int(n) for n in net_arch), str(activation)
+        if not self.net_arch or min(self.net_arch) < 1:
+            raise ValueError("net_arch must name at least one hidden layer of at least one unit")
+        if self.activation not in ACTIVATIONS:
+            raise ValueError("activation must be 'tanh' or 'relu', not %r" % (activation,))
         def tower(out):
-            return nn.Sequential(nn.Linear(obs_dim, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh(), nn.Linear(64, out))
+            layers, last = [], obs_dim
+            for width in self.net_arch:
+                layers += [nn.Linear(last, width), ACTIVATIONS[self.activation]()]
+                last = width
+            return nn.Sequential(*layers, nn.Linear(last, out))
         self.pi, self.vf = tower(act_dim), tower(1)
         self.log_std = nn.Parameter(torch.zeros(act_dim))
 
@@ -382,7 +412,7 @@ class _TorchLearner:
 
     def __init__(self, model, num_envs, n_steps, opt, **hyper):
         self.model, self.opt, self.hyper = model, opt, hyper
-        self.buffers = rollout_buffers(n_steps, num_envs, model.pi[0].in_features, model.pi[4].out_features, model.log_std.device)
+        self.buffers = rollout_buffers(n_steps, num_envs, model.pi[0].in_features, model.pi[-1].out_features, model.log_std.device)
 
     def store(self, k, obs, action, reward, done, resetting=None):
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
@@ -413,7 +443,7 @@ class TorchPPO(_TorchLearner):
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
-          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2):
+          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -428,7 +458,10 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     algo: "a2c" (n_steps 5, lr 7e-4: the reference's learner) or "ppo" (n_steps 16, lr 3e-4): stable-baselines3's PPO.train() on each
     rollout (ppo_update) - GAE(gae_lambda) from the rollout's values, n_epochs passes over shuffled minibatches of batch_size rows (None:
     a quarter of the rollout), per-minibatch advantage normalisation over the used rows, the surrogate clipped at clip_range,
-    clip_grad_norm_ and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO)."""
+    clip_grad_norm_ and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO).
+    net_arch / activation: ActorCritic's hidden widths and "tanh" / "relu" (None: 64-64 tanh), for either algo.  device_policy and the PPO
+    device_update run equal widths of 64, 128, 192 or 256 units in two or three layers on their "wide" backends; the A2C
+    device_update is the 64-64 tanh shape's and raises ValueError for any other."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
     ppo = algo == "ppo"
@@ -448,7 +481,7 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
         venv = VecNormalize(env, gamma=gamma)
         monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
-    model = ActorCritic(venv.dim, env.act_dim).to(dev)
+    model = ActorCritic(venv.dim, env.act_dim, (64, 64) if net_arch is None else tuple(net_arch), activation or "tanh").to(dev)
     n_rows = n_steps * num_envs
     batch_size = max(1, -(-n_rows // 4)) if batch_size is None else min(int(batch_size), n_rows)
     hyper = dict(n_steps=n_steps, gamma=gamma, lr=lr, eps=1e-5)
@@ -531,8 +564,8 @@ def main(argv=None):
     ap.add_argument("--n-epochs", type=int, default=4, help="ppo: passes over a rollout")
     ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout); sac: rows per step (256)")
     ap.add_argument("--gradient-steps", type=int, default=1, help="sac: SAC steps per training env step")
-    ap.add_argument("--net-arch", type=int, nargs="+", default=None, help="sac: hidden widths (default 64 64; the reference's sparse branch: 256 256 256)")
-    ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="sac: tanh (default) or relu (stable-baselines3's SAC default)")
+    ap.add_argument("--net-arch", type=int, nargs="+", default=None, help="hidden widths of every tower (default 64 64; the reference's sparse branch: 256 256 256)")
+    ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="tanh (default) or relu (stable-baselines3's SAC default)")
     args = ap.parse_args(argv)
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
@@ -549,7 +582,8 @@ def main(argv=None):
     model, venv, hist = train(args.env, args.num_envs, args.updates, config=cfg, auto_reset="lazy" if args.lazy_reset else True,
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
                               device_policy=args.device_policy, device_update=args.device_update, algo=args.algo, n_steps=args.n_steps,
-                              n_epochs=args.n_epochs, batch_size=args.batch_size)
+                              n_epochs=args.n_epochs, batch_size=args.batch_size, net_arch=None if args.net_arch is None else tuple(args.net_arch),
+                              activation=args.activation)
     if args.save:
         save_model(args.save, model, venv)
 

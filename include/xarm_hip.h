@@ -686,6 +686,79 @@ int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *para
                      float *out_dqda /* may be NULL */, float *out_target /* may be NULL */, float *out_stats /* may be NULL */,
                      float *out_q /* may be NULL */, void *stream);
 
+/* ---- wide device-resident MlpPolicy (gym_xarm_amd/csrc/xarm_acw_core.h, xarm_k_acw.hip): xarm_policy_act's contract for
+ * gym_xarm_amd/train.py's ActorCritic(net_arch, activation) with equal-width towers of n_hidden = 2 or 3 hidden layers of hidden = 64,
+ * 128, 192 or 256 units, tanh or ReLU (XARM_SACW_TANH / XARM_SACW_RELU).  Rows, stats, calls, the noise and the four outputs mean what
+ * they mean in xarm_policy_act, except that EVERY output may be NULL (a NULL out_value skips the value tower).  A tower is 2 (n_hidden + 1)
+ * pointers W1, b1, ..., W_out, b_out (nn.Linear's [out, in] layout) in arrays of eight, the unused tail ignored.  The forward runs layer
+ * by layer on xarm_sacw's f32 MFMA GEMM kernel with the activations in `workspace`: one launch writes the row observation |
+ * achieved_goal | desired_goal (normalised when stats is set) there, n_hidden + 1 launches run both towers, one launch per row draws the
+ * noise and writes the outputs, and a stochastic call ends with the one-thread launch that advances `calls` - n_hidden + 3 (+ 1) launches
+ * for every row count.  Every dot product is a float32 fmaf chain from the bias over k ascending (an odd K padded with one zero operand):
+ * a row's result depends on that row, the weights, seed, row_offset + row and *calls alone.  No allocation, no host read, no atomics, no
+ * side stream; num_rows == 0 launches nothing. */
+typedef struct xarm_acw_layout {
+    int32_t num_rows;
+    int32_t obs_dim;
+    int32_t goal_dim;           /* 0: `obs` is the whole row */
+    int32_t act_dim;            /* 1 .. XARM_POLICY_MAX_ACT */
+    int32_t hidden;             /* 64, 128, 192 or 256 */
+    int32_t n_hidden;           /* 2 or 3 */
+    int32_t activation;         /* XARM_SACW_TANH or XARM_SACW_RELU */
+    int64_t row_offset;         /* global index of row 0 (>= 0) */
+} xarm_acw_layout;              /* 40 bytes (4 bytes of padding before row_offset) */
+typedef struct xarm_acw_weights {
+    const float *pi[2 * (XARM_SACW_MAX_LAYERS + 1)];        /* W1 [H, D], b1 [H], W2 [H, H], b2 [H], (W3, b3,) W_out [A, H], b_out [A] */
+    const float *vf[2 * (XARM_SACW_MAX_LAYERS + 1)];        /* ..., W_out [1, H], b_out [1]; read only when out_value is set */
+    const float *log_std;       /* [A] */
+} xarm_acw_weights;             /* 17 device pointers */
+/* *bytes = size of xarm_acw_act's `workspace` for this layout: (D + 2 n_hidden hidden + A + 1) floats per row, each part rounded up to
+ * 16 bytes.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_acw_workspace_bytes(const xarm_acw_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: NULL layout / params / weights, num_rows < 0, obs_dim < 1, goal_dim < 0, D > XARM_POLICY_MAX_DIM, act_dim outside
+ * [1, XARM_POLICY_MAX_ACT], hidden outside {64, 128, 192, 256}, n_hidden outside {2, 3}, activation outside {XARM_SACW_TANH,
+ * XARM_SACW_RELU}, row_offset < 0, with stats an eps that is not finite and > 0 or a clip_obs <= 0, or with num_rows > 0 a NULL policy
+ * tensor, log_std or obs, a NULL achieved_goal / desired_goal with goal_dim > 0, a NULL value tensor with out_value set, a tensor from
+ * b1 to W_out (of a tower that is read) that is not 16-byte aligned, a NULL or not 16-byte aligned workspace, a NULL calls with
+ * deterministic == 0. */
+int xarm_acw_act(const xarm_acw_layout *layout, const xarm_policy_params *params, const xarm_acw_weights *weights,
+                 const double *stats /* may be NULL */, int64_t *calls_i64, const float *obs, const float *achieved_goal,
+                 const float *desired_goal, void *workspace, float *out_action /* may be NULL */, float *out_env_action /* may be NULL */,
+                 float *out_logp /* may be NULL */, float *out_value /* may be NULL */, void *stream);
+
+/* ---- wide device-resident PPO update (gym_xarm_amd/csrc/xarm_ppow_core.h, xarm_k_ppow.hip): xarm_ppo_update for the towers
+ * of xarm_acw_act.  Arguments and every meaning are xarm_ppo_update's - obs [T, E, D], action, reward, done, use (may be NULL), last_obs,
+ * old_logp (may be NULL), perm int32 [n_epochs, N], out_adv / out_returns [T, E], out_grad [P] (step 0, before the clip), out_stats
+ * [S, 8] - with the layout naming hidden, n_hidden and activation and the weights, exp_avg and exp_avg_sq as three xarm_acw_weights.
+ * out_grad's flat order: pi's 2 (n_hidden + 1) tensors, vf's, log_std.  With L = n_hidden, B = min(batch_size, N), M = ceil(N / B),
+ * S = n_epochs M and c = M + ceil(E / B) (the call-start forward runs the rollout in M chunks of at most B rows and last_obs in
+ * launches of its own) a call is c (L + 1) + 2 + S (2 L + 6) launches: the workspace grows with B, not with N, apart from N (A + 4) + E
+ * floats of per-row results.  No allocation, no host read, no atomics, no side stream; sums run in a fixed order (xarm_sacw's for the
+ * weight gradients, 256 float64 partials added in order for sums over rows): the same inputs and perm give the same bits.
+ * Out of scope: unequal widths, a shared trunk, target_kl, clip_range_vf, schedules.  num_envs == 0 launches nothing. */
+typedef struct xarm_ppow_layout {
+    int32_t num_envs;           /* E >= 0 */
+    int32_t n_steps;            /* T >= 1, T E < 2^31 */
+    int32_t obs_dim;            /* D: 1 .. XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_POLICY_MAX_ACT */
+    int32_t hidden;             /* 64, 128, 192 or 256 */
+    int32_t n_hidden;           /* 2 or 3 */
+    int32_t activation;         /* XARM_SACW_TANH or XARM_SACW_RELU */
+    int32_t n_epochs;           /* >= 1 */
+    int32_t batch_size;         /* >= 1; n_epochs ceil(T E / batch_size) <= 4096 */
+} xarm_ppow_layout;             /* 36 bytes */
+/* *bytes = size of `workspace` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_ppow_workspace_bytes(const xarm_ppow_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: what xarm_ppo_update refuses, with hidden outside {64, 128, 192, 256}, n_hidden outside {2, 3} or activation outside
+ * {XARM_SACW_TANH, XARM_SACW_RELU} in place of hidden != 64; with num_envs > 0 a NULL tensor of either tower, of log_std or of the two
+ * states, a weight tensor from b1 to W_out that is not 16-byte aligned, a NULL or not 16-byte aligned workspace. */
+int xarm_ppow_update(const xarm_ppow_layout *layout, const xarm_ppo_params *params, const xarm_acw_weights *weights,
+                     const xarm_acw_weights *exp_avg, const xarm_acw_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                     const float *action, const float *reward, const float *done, const float *use /* may be NULL */,
+                     const float *last_obs, const float *old_logp /* may be NULL */, const int32_t *perm, void *workspace,
+                     float *out_adv /* may be NULL */, float *out_returns /* may be NULL */, float *out_grad /* may be NULL */,
+                     float *out_stats /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
