@@ -25,7 +25,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update",
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
            "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update",
-           "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update"]
+           "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update",
+           "xarm_a2cw_workspace_bytes", "xarm_a2cw_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -170,6 +171,11 @@ class XarmPPOWLayout(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("num_envs", "n_steps", "obs_dim", "act_dim", "hidden", "n_hidden", "activation", "n_epochs", "batch_size")]
 
 
+class XarmA2CWLayout(C.Structure):
+    """include/xarm_hip.h xarm_a2cw_layout (28 bytes)"""
+    _fields_ = [(k, C.c_int32) for k in ("num_envs", "n_steps", "obs_dim", "act_dim", "hidden", "n_hidden", "activation")]
+
+
 class XarmNativeError(RuntimeError):
     pass
 
@@ -244,6 +250,9 @@ def load(path=None):
     ql, cw = C.POINTER(XarmPPOWLayout), C.POINTER(XarmACWWeights)
     L.xarm_ppow_workspace_bytes.argtypes = [ql, C.POINTER(C.c_int64)]
     L.xarm_ppow_update.argtypes = [ql, C.POINTER(XarmPPOParams), cw, cw, cw] + [vp] * 15
+    wa = C.POINTER(XarmA2CWLayout)
+    L.xarm_a2cw_workspace_bytes.argtypes = [wa, C.POINTER(C.c_int64)]
+    L.xarm_a2cw_update.argtypes = [wa, C.POINTER(XarmA2CParams), cw, cw] + [vp] * 11
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

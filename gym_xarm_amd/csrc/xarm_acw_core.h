@@ -37,9 +37,7 @@ inline const char *layout_error(const xarm_acw_layout *l) {
     if (!l) return "layout is NULL";
     const xarm_policy_layout p = policy_layout_of(l);
     if (const char *why = xpol::layout_error(&p)) return why;       // num_rows is the policy ABI's num_envs
-    if (l->hidden != 64 && l->hidden != 128 && l->hidden != 192 && l->hidden != 256) return "hidden must be 64, 128, 192 or 256";
-    if (l->n_hidden != 2 && l->n_hidden != 3) return "n_hidden must be 2 or 3";
-    if (l->activation != xsacw::ACT_TANH && l->activation != xsacw::ACT_RELU) return "activation must be XARM_SACW_TANH or XARM_SACW_RELU";
+    if (const char *why = xsacw::towers_error(l->hidden, l->n_hidden, l->activation)) return why;
     return nullptr;
 }
 

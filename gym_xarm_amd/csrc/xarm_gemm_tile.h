@@ -1,5 +1,6 @@
-// xarm_gemm_tile.h - the three f32 MFMA GEMM kernels of the wide learners (DESIGN.md 24, 25) and the executor part that launches them.
-// Device-only; included by xarm_k_sacw.hip and xarm_k_acw.hip, each of which gets its own (internal) copy of the kernels it launches.
+// xarm_gemm_tile.h - the three f32 MFMA GEMM kernels of the wide learners (DESIGN.md 24, 25, 26) and the executor part that launches them.
+// Device-only; included by xarm_k_sacw.hip, xarm_k_acw.hip, xarm_k_ppow.hip and xarm_k_a2cw.hip, each of which gets its own (internal) copy of
+// the kernels it launches.
 // The jobs (Fwd, Bd, Wg), the passes that fill them and the host build's loops over the same jobs are in xarm_sacw_core.h.
 //
 // A kernel runs one wavefront per workgroup on one 32 x 32 accumulator tile of v_mfma_f32_32x32x2_f32: the A operand's lane l & 31 is the

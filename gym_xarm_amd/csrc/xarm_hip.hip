@@ -40,6 +40,7 @@
 #include "xarm_sacw_core.h"
 #include "xarm_acw_core.h"
 #include "xarm_ppow_core.h"
+#include "xarm_a2cw_core.h"
 
 using namespace xd;
 
@@ -1263,6 +1264,39 @@ int xarm_ppow_update(const xarm_ppow_layout *layout, const xarm_ppo_params *para
     d.out_adv = out_adv; d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
     const int le = xppow::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_ppow_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ wide A2C update (xarm_k_a2cw.hip)
+int xarm_a2cw_workspace_bytes(const xarm_a2cw_layout *layout, int64_t *bytes) {
+    if (const char *why = xa2cw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_a2cw_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_a2cw_workspace_bytes: NULL pointer");
+    xa2cw::Dev d = {};
+    xa2cw::fill_shape(d, layout);
+    *bytes = xa2cw::fill_work(d, nullptr);
+    return XARM_OK;
+}
+
+int xarm_a2cw_update(const xarm_a2cw_layout *layout, const xarm_a2c_params *params, const xarm_acw_weights *weights,
+                     const xarm_acw_weights *square_avg, const float *obs, const float *action, const float *reward, const float *done,
+                     const float *use, const float *last_obs, void *workspace, float *out_returns, float *out_grad, float *out_stats,
+                     void *stream) {
+    if (const char *why = xa2cw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_a2cw_update: %s", why);
+    if (const char *why = xa2c::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_a2cw_update: %s", why);
+    if (!weights || !square_avg) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_a2cw_update: weights / square_avg is NULL");
+    if (layout->num_envs == 0) return XARM_OK;
+    if (const char *why = xa2cw::pointer_error(layout, weights, square_avg, obs, action, reward, done, last_obs, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_a2cw_update: %s", why);
+    xa2cw::Dev d = {};
+    xa2cw::fill_shape(d, layout);
+    xa2c::fill_hyper(d.h, params);
+    xppow::tensors_of(d, weights, d.w);
+    xppow::tensors_of(d, square_avg, d.sq);
+    xa2cw::fill_work(d, workspace);
+    d.obs = obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.last_obs = last_obs;
+    d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
+    const int le = xa2cw::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_a2cw_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -65,9 +65,7 @@ inline const char *layout_error(const xarm_ppow_layout *l) {
     if (!l) return "layout is NULL";
     const xarm_ppo_layout p = ppo_layout_of(l);
     if (const char *why = xppo::layout_error(&p)) return why;
-    if (l->hidden != 64 && l->hidden != 128 && l->hidden != 192 && l->hidden != 256) return "hidden must be 64, 128, 192 or 256";
-    if (l->n_hidden != 2 && l->n_hidden != 3) return "n_hidden must be 2 or 3";
-    if (l->activation != xsacw::ACT_TANH && l->activation != xsacw::ACT_RELU) return "activation must be XARM_SACW_TANH or XARM_SACW_RELU";
+    if (const char *why = xsacw::towers_error(l->hidden, l->n_hidden, l->activation)) return why;
     return nullptr;
 }
 
@@ -92,11 +90,10 @@ inline const char *pointer_error(const xarm_ppow_layout *l, const xarm_acw_weigh
     return xsacw::workspace_error(workspace);
 }
 
-inline void fill_shape(Dev &d, const xarm_ppow_layout *l) {
-    const xarm_ppo_layout pl = ppo_layout_of(l);
-    xppo::fill_shape(d.p, &pl);                 // E, N, T, D, A, B, M, S; the 64-64 parameter count is replaced below
-    xsacw::Shape &g = d.g;
-    g.B = d.p.B; g.D = l->obs_dim; g.A = l->act_dim; g.H = l->hidden; g.L = l->n_hidden; g.NL = g.L + 1; g.act = l->activation;
+// the GEMM shape of an actor-critic of two towers over B rows: the flat offsets of pi's tensors, vf's and log_std, the row ranges; Ppi and
+// Ptow: pi's parameters and both towers'.  Shared with the wide A2C update (xarm_a2cw_core.h)
+inline void fill_towers(xsacw::Shape &g, int64_t B, int obs_dim, int act_dim, int hidden, int n_hidden, int activation, int64_t &Ppi, int64_t &Ptow) {
+    g.B = B; g.D = obs_dim; g.A = act_dim; g.H = hidden; g.L = n_hidden; g.NL = g.L + 1; g.act = activation;
     g.tp = 2 * g.NL; g.NT = 2 * g.tp + 1; g.BH = g.B * g.H;
     g.off[0] = 0;
     for (int t = 0; t < 2; t++)
@@ -108,15 +105,22 @@ inline void fill_shape(Dev &d, const xarm_ppow_layout *l) {
         }
     g.off[g.NT] = g.off[g.NT - 1] + g.A;
     g.P = g.off[g.NT];
-    d.Ppi = g.off[g.tp]; d.Ptow = g.off[2 * g.tp];
+    Ppi = g.off[g.tp]; Ptow = g.off[2 * g.tp];
     xsacw::fill_ranges(g);
+}
+
+inline void fill_shape(Dev &d, const xarm_ppow_layout *l) {
+    const xarm_ppo_layout pl = ppo_layout_of(l);
+    xppo::fill_shape(d.p, &pl);                 // E, N, T, D, A, B, M, S; the 64-64 parameter count is replaced below
+    xsacw::Shape &g = d.g;
+    fill_towers(g, d.p.B, l->obs_dim, l->act_dim, l->hidden, l->n_hidden, l->activation, d.Ppi, d.Ptow);
     d.p.a.P = g.P;
     d.p.a.NB = (int)((g.P + RED - 1) / RED);
     d.CN = d.p.M;
     d.CE = g.B > 0 ? (d.p.a.E + g.B - 1) / g.B : 0;
 }
 
-inline void tensors_of(const Dev &d, const xarm_acw_weights *w, float **t) {
+template <class D> inline void tensors_of(const D &d, const xarm_acw_weights *w, float **t) {
     for (int i = 0; i < d.g.tp; i++) { t[i] = const_cast<float *>(w->pi[i]); t[d.g.tp + i] = const_cast<float *>(w->vf[i]); }
     t[2 * d.g.tp] = const_cast<float *>(w->log_std);
 }
@@ -226,15 +230,18 @@ XARM_HD void head_row(const Dev &d, int64_t i, double *sums) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ the parameters' parts
-XARM_HD double n_use_of(const Dev &d) { return xopt::n_use(d.scal[2]); }
+// (these are templates over the learner's Dev - g, Ptow, partial, scal with slot 2 the sum of use and slots 3 + c log_std's sums, h.ent_coef,
+// grad, normpart, out_grad - so that the wide A2C update states none of them again)
+template <class D> XARM_HD double n_use_of(const D &d) { return xopt::n_use(d.scal[2]); }
 
-// the step's gradient of flat parameter p, before the clip
-XARM_HD float param_grad(const Dev &d, int64_t p) {
+// the step's gradient of flat parameter p, before the clip; scal: the step's sums over rows (d.scal, or a workgroup's copy of them)
+template <class D> XARM_HD float param_grad(const D &d, const double *scal, int64_t p) {
     const bool ls = p >= d.Ptow;
-    double v = (ls ? d.scal[3 + (p - d.Ptow)] : xopt::slice_sum(d.partial + p, d.g.S, d.Ptow)) / n_use_of(d);
+    double v = (ls ? scal[3 + (p - d.Ptow)] : xopt::slice_sum(d.partial + p, d.g.S, d.Ptow)) / xopt::n_use(scal[2]);
     if (ls) v -= d.h.ent_coef;
     return (float)v;
 }
+template <class D> XARM_HD float param_grad(const D &d, int64_t p) { return param_grad(d, d.scal, p); }
 
 // one thread per step, in the reduce launch: step++, Adam's scalars, the stats row (slot 3, the norm, is the apply launch's)
 XARM_HD void finish_step(const Dev &d, int64_t st) {
@@ -248,13 +255,14 @@ XARM_HD void finish_step(const Dev &d, int64_t st) {
     o[5] = (float)(d.scal[19] / n_use); o[6] = (float)(d.scal[20] / n_use); o[7] = 0.0f;
 }
 
-// the norm from normpart in block order; returns the clip coefficient
-XARM_HD float clip_of(const Dev &d, float &norm) {
+// the norm from normpart's NB blocks in block order; returns the clip coefficient
+template <class D> XARM_HD float clip_of(const D &d, int NB, float &norm) {
     double sum2 = 0.0;
-    for (int b = 0; b < d.p.a.NB; b++) sum2 += d.normpart[b];
+    for (int b = 0; b < NB; b++) sum2 += d.normpart[b];
     norm = (float)__builtin_sqrt(sum2);
     return xopt::clip_coef(norm, d.h.max_norm);
 }
+XARM_HD float clip_of(const Dev &d, float &norm) { return clip_of(d, d.p.a.NB, norm); }
 
 XARM_HD void apply_param(const Dev &d, int64_t p, float coef) {
     const int i = xopt::tensor_at(d.g.off, 0, d.g.NT, p);
@@ -306,6 +314,27 @@ template <class X> void run_update(const Dev &d, X &ex) {
 }
 
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
+// the reduce launch as loops: a block's RED parameters through param_grad into grad (and out_grad when `keep`), the block's squares by the
+// device's tree into normpart
+template <class D> void host_reduce_blocks(const D &d, int NB, bool keep) {
+    for (int b = 0; b < NB; b++) {
+        double red[RED];
+        for (int t = 0; t < RED; t++) {
+            const int64_t p = (int64_t)b * RED + t;
+            red[t] = 0.0;
+            if (p < d.g.P) {
+                const float gf = param_grad(d, p);
+                d.grad[p] = gf;
+                if (keep && d.out_grad != nullptr) d.out_grad[p] = gf;
+                red[t] = (double)gf * (double)gf;
+            }
+        }
+        for (int s = RED / 2; s > 0; s >>= 1)       // the device's block tree
+            for (int t = 0; t < s; t++) red[t] += red[t + s];
+        d.normpart[b] = red[0];
+    }
+}
+
 // ---- the host build: the GEMM jobs through xsacw::HostExec's loops, the rest with the device's thread and block structure as loops
 struct HostExec : xsacw::HostExec {
     void gae(const Dev &d) {
@@ -339,22 +368,7 @@ struct HostExec : xsacw::HostExec {
         for (int k = 0; k < NSCAL; k++) d.scal[k] = tot[k];
     }
     void reduce(const Dev &d, int64_t st) {
-        for (int b = 0; b < d.p.a.NB; b++) {
-            double red[RED];
-            for (int t = 0; t < RED; t++) {
-                const int64_t p = (int64_t)b * RED + t;
-                red[t] = 0.0;
-                if (p < d.g.P) {
-                    const float gf = param_grad(d, p);
-                    d.grad[p] = gf;
-                    if (st == 0 && d.out_grad != nullptr) d.out_grad[p] = gf;
-                    red[t] = (double)gf * (double)gf;
-                }
-            }
-            for (int s = RED / 2; s > 0; s >>= 1)       // the device's block tree
-                for (int t = 0; t < s; t++) red[t] += red[t + s];
-            d.normpart[b] = red[0];
-        }
+        host_reduce_blocks(d, d.p.a.NB, st == 0);
         finish_step(d, st);
     }
     void apply(const Dev &d, int64_t st) {

@@ -40,15 +40,21 @@ struct Shape {
     int64_t rows[MAX_SPLIT + 1];                // range s is rows [rows[s], rows[s + 1])
 };
 
+// the tower shapes every wide unit accepts
+inline const char *towers_error(int hidden, int n_hidden, int activation) {
+    if (hidden != 64 && hidden != 128 && hidden != 192 && hidden != 256) return "hidden must be 64, 128, 192 or 256";
+    if (n_hidden != 2 && n_hidden != 3) return "n_hidden must be 2 or 3";
+    if (activation != ACT_TANH && activation != ACT_RELU) return "activation must be XARM_SACW_TANH or XARM_SACW_RELU";
+    return nullptr;
+}
+
 inline const char *layout_error(const xarm_sacw_layout *l) {
     if (!l) return "layout is NULL";
     if (l->batch_size < 0) return "batch_size must be >= 0 (and < 2^31)";
     if (l->obs_dim < 1) return "obs_dim must be >= 1";
     if (l->act_dim < 1 || l->act_dim > MAX_A) return "act_dim must lie in [1, XARM_SAC_MAX_ACT (8)]";
     if (l->obs_dim > xpol::MAX_DIM || l->obs_dim + l->act_dim > xpol::MAX_DIM) return "obs_dim + act_dim must be <= XARM_POLICY_MAX_DIM (96)";
-    if (l->hidden != 64 && l->hidden != 128 && l->hidden != 192 && l->hidden != 256) return "hidden must be 64, 128, 192 or 256";
-    if (l->n_hidden != 2 && l->n_hidden != 3) return "n_hidden must be 2 or 3";
-    if (l->activation != ACT_TANH && l->activation != ACT_RELU) return "activation must be XARM_SACW_TANH or XARM_SACW_RELU";
+    if (const char *why = towers_error(l->hidden, l->n_hidden, l->activation)) return why;
     if (l->row_offset < 0) return "row_offset must be >= 0";
     return nullptr;
 }

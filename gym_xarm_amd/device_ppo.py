@@ -12,7 +12,7 @@ import ctypes as C
 import torch
 
 from . import _native
-from .device_a2c import module_params, policy_weights
+from .device_a2c import acw_weights, module_params, policy_weights
 from .device_policy import is_tile64, tower_params, tower_shape, wide_supported
 from .train import rollout_buffers, store_rollout
 
@@ -131,16 +131,7 @@ class DevicePPO:
         return module_params(self.model)
 
     def _wide_weights(self, tensors):
-        tp = (len(tensors) - 1) // 2
-        w = _native.XarmACWWeights()
-        for i, t in enumerate(tensors):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
-                raise ValueError("DevicePPO needs contiguous float32 tensors on %s (tensor %d)" % (self.device, i))
-            if i == 2 * tp:
-                w.log_std = t.data_ptr()
-            else:
-                (w.pi if i < tp else w.vf)[i % tp] = t.data_ptr()
-        return w
+        return acw_weights(tensors, self.device, "DevicePPO")
 
     def store(self, k, obs, action, reward, done, resetting=None):
         """slot k of the rollout (train.store_rollout)"""

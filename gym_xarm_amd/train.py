@@ -443,7 +443,7 @@ class TorchPPO(_TorchLearner):
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
-          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None):
+          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None, wide=None):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -461,7 +461,9 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     clip_grad_norm_ and Adam(eps=1e-5).  With device_update the PPO update runs in HIP kernels too (gym_xarm_amd/device_ppo.py DevicePPO).
     net_arch / activation: ActorCritic's hidden widths and "tanh" / "relu" (None: 64-64 tanh), for either algo.  device_policy and the PPO
     device_update run equal widths of 64, 128, 192 or 256 units in two or three layers on their "wide" backends; the A2C
-    device_update is the 64-64 tanh shape's and raises ValueError for any other."""
+    device_update runs them on its "wide" backend when wide=True, and without it is the 64-64 tanh shape's and raises
+    ValueError for any other.
+    wide: handed to DeviceA2C / DevicePPO and to DevicePolicy as their `wide`; None leaves each class its default."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
     ppo = algo == "ppo"
@@ -489,15 +491,15 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
         hyper.update(n_epochs=n_epochs, batch_size=batch_size, gae_lambda=gae_lambda, clip_range=clip_range)
     if device_update and ppo:
         from .device_ppo import DevicePPO
-        learner = DevicePPO(model, num_envs, seed=seed, **hyper)
+        learner = DevicePPO(model, num_envs, seed=seed, wide=wide, **hyper)
     elif device_update:
         from .device_a2c import DeviceA2C
-        learner = DeviceA2C(model, num_envs, **hyper)
+        learner = DeviceA2C(model, num_envs, wide=wide, **hyper)
     else:
         learner = (TorchPPO if ppo else TorchA2C)(model, num_envs, **hyper)
     if device_policy:
         from .device_policy import DevicePolicy
-        policy = DevicePolicy(model, seed=seed, row_offset=int(getattr(env, "_env_id_offset", 0)))
+        policy = DevicePolicy(model, seed=seed, row_offset=int(getattr(env, "_env_id_offset", 0)), wide=wide)
         env_action = torch.empty(num_envs, env.act_dim, device=dev)
     obs = venv.reset()
     hist, t0 = [], time.perf_counter()
@@ -566,7 +568,11 @@ def main(argv=None):
     ap.add_argument("--gradient-steps", type=int, default=1, help="sac: SAC steps per training env step")
     ap.add_argument("--net-arch", type=int, nargs="+", default=None, help="hidden widths of every tower (default 64 64; the reference's sparse branch: 256 256 256)")
     ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="tanh (default) or relu (stable-baselines3's SAC default)")
+    ap.add_argument("--wide", action="store_true", help="a2c / ppo: the per-layer GEMM chain for --device-update and --device-policy whatever the shape "
+                                                        "(a2c: needed for any shape but 64 64 tanh)")
     args = ap.parse_args(argv)
+    if args.wide and args.algo == "sac":
+        ap.error("--wide is for --algo a2c / ppo: the SAC device update selects its backend by shape")
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
@@ -583,7 +589,7 @@ def main(argv=None):
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
                               device_policy=args.device_policy, device_update=args.device_update, algo=args.algo, n_steps=args.n_steps,
                               n_epochs=args.n_epochs, batch_size=args.batch_size, net_arch=None if args.net_arch is None else tuple(args.net_arch),
-                              activation=args.activation)
+                              activation=args.activation, wide=True if args.wide else None)
     if args.save:
         save_model(args.save, model, venv)
 

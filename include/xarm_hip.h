@@ -759,6 +759,38 @@ int xarm_ppow_update(const xarm_ppow_layout *layout, const xarm_ppo_params *para
                      float *out_adv /* may be NULL */, float *out_returns /* may be NULL */, float *out_grad /* may be NULL */,
                      float *out_stats /* may be NULL */, void *stream);
 
+/* ---- wide device-resident A2C update (gym_xarm_amd/csrc/xarm_a2cw_core.h, xarm_k_a2cw.hip): xarm_a2c_update for the towers
+ * of xarm_acw_act.  Arguments and every meaning are xarm_a2c_update's - obs [T, E, D], action, reward, done, use (may be NULL), last_obs,
+ * out_returns [T, E], out_grad [P] (before the clip), out_stats [8] = policy_loss, value_loss, entropy, grad_norm, n_use, 0, 0, 0 - with
+ * the layout naming hidden, n_hidden and activation and the weights and square_avg as two xarm_acw_weights (READ AND WRITTEN in place).
+ * Flat order of out_grad and square_avg: pi's 2 (n_hidden + 1) tensors, vf's, log_std.  It is xarm_ppow_update's chain with one optimiser
+ * step over all N = T E rows in their stored order: with L = n_hidden, L + 1 forward launches of vf over last_obs, one launch for the
+ * returns, L + 1 forward launches of both towers over the rollout (read from obs in place), the head on min(64, ceil(N / 256)) workgroups,
+ * L delta launches, one weight-gradient launch, reduce and apply - 3 L + 7 launches for every row count.  The workspace holds every
+ * layer's activations and deltas of all N rows (4 L N hidden floats and N (2 act_dim + 3) + E of per-row results, at most 16 gradient
+ * partials, the head's records) and nothing between calls.  No allocation, no host read, no atomics, no side stream; sums run in a fixed
+ * order (xarm_sacw's for the weight gradients; for sums over rows 256 float64 partials per head workgroup added in thread order, the
+ * workgroups' records in workgroup order): the same inputs give the same bits.  Out of scope: unequal widths, a shared trunk, chunked
+ * batches.  num_envs == 0 launches nothing. */
+typedef struct xarm_a2cw_layout {
+    int32_t num_envs;           /* E >= 0 */
+    int32_t n_steps;            /* T >= 1, T E < 2^31 */
+    int32_t obs_dim;            /* D: 1 .. XARM_POLICY_MAX_DIM */
+    int32_t act_dim;            /* 1 .. XARM_POLICY_MAX_ACT */
+    int32_t hidden;             /* 64, 128, 192 or 256 */
+    int32_t n_hidden;           /* 2 or 3 */
+    int32_t activation;         /* XARM_SACW_TANH or XARM_SACW_RELU */
+} xarm_a2cw_layout;             /* 28 bytes */
+/* *bytes = size of `workspace` for this layout.  XARM_E_INVALID: NULL argument or unusable layout (below). */
+int xarm_a2cw_workspace_bytes(const xarm_a2cw_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: what xarm_a2c_update refuses, with hidden outside {64, 128, 192, 256}, n_hidden outside {2, 3} or activation outside
+ * {XARM_SACW_TANH, XARM_SACW_RELU} in place of hidden != 64; with num_envs > 0 a NULL tensor of either tower, of log_std or of square_avg,
+ * a weight tensor from b1 to W_out that is not 16-byte aligned, a NULL or not 16-byte aligned workspace. */
+int xarm_a2cw_update(const xarm_a2cw_layout *layout, const xarm_a2c_params *params, const xarm_acw_weights *weights,
+                     const xarm_acw_weights *square_avg, const float *obs, const float *action, const float *reward, const float *done,
+                     const float *use /* may be NULL */, const float *last_obs, void *workspace, float *out_returns /* may be NULL */,
+                     float *out_grad /* may be NULL */, float *out_stats /* may be NULL */, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
