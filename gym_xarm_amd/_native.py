@@ -22,10 +22,10 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
-           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update",
+           "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update", "xarm_ppo_update_opt",
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
            "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update",
-           "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update",
+           "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update", "xarm_ppow_update_opt",
            "xarm_a2cw_workspace_bytes", "xarm_a2cw_update"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
@@ -119,6 +119,11 @@ class XarmPPOLayout(C.Structure):
 class XarmPPOParams(C.Structure):
     """include/xarm_hip.h xarm_ppo_params (88 bytes)"""
     _fields_ = [(k, C.c_double) for k in PPO_HYPER] + [("normalize_advantage", C.c_int32)]
+
+
+class XarmPPOOptions(C.Structure):
+    """include/xarm_hip.h xarm_ppo_options (16 bytes); 0 = off"""
+    _fields_ = [("clip_range_vf", C.c_double), ("target_kl", C.c_double)]
 
 
 SAC_MAX_ACT = 8             # XARM_SAC_MAX_ACT
@@ -236,6 +241,7 @@ def load(path=None):
     pl = C.POINTER(XarmPPOLayout)
     L.xarm_ppo_workspace_bytes.argtypes = [pl, C.POINTER(C.c_int64)]
     L.xarm_ppo_update.argtypes = [pl, C.POINTER(XarmPPOParams)] + [C.POINTER(XarmPolicyWeights)] * 3 + [vp] * 15
+    L.xarm_ppo_update_opt.argtypes = [pl, C.POINTER(XarmPPOParams)] + [C.POINTER(XarmPolicyWeights)] * 3 + [vp] * 14 + [C.POINTER(XarmPPOOptions), vp]
     sl, sp, sw = C.POINTER(XarmSACLayout), C.POINTER(XarmSACParams), C.POINTER(XarmSACWeights)
     L.xarm_sac_workspace_bytes.argtypes = [sl, C.POINTER(C.c_int64)]
     L.xarm_sac_act.argtypes = [sl, sp, sw] + [vp] * 5
@@ -250,6 +256,7 @@ def load(path=None):
     ql, cw = C.POINTER(XarmPPOWLayout), C.POINTER(XarmACWWeights)
     L.xarm_ppow_workspace_bytes.argtypes = [ql, C.POINTER(C.c_int64)]
     L.xarm_ppow_update.argtypes = [ql, C.POINTER(XarmPPOParams), cw, cw, cw] + [vp] * 15
+    L.xarm_ppow_update_opt.argtypes = [ql, C.POINTER(XarmPPOParams), cw, cw, cw] + [vp] * 14 + [C.POINTER(XarmPPOOptions), vp]
     wa = C.POINTER(XarmA2CWLayout)
     L.xarm_a2cw_workspace_bytes.argtypes = [wa, C.POINTER(C.c_int64)]
     L.xarm_a2cw_update.argtypes = [wa, C.POINTER(XarmA2CParams), cw, cw] + [vp] * 11

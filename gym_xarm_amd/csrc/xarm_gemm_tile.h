@@ -13,6 +13,8 @@
 //   k_sacw_bd      grid (row tiles, column blocks, jobs).  A = d (row n), B = W[k][c0 + i] (coalesced along i); epilogue pre * act'(h).
 //   k_sacw_wg      grid (input blocks, unit blocks, jobs x row ranges).  A = d^T (unit j), B = x (input i; i = K is the bias column of
 //                  ones), both coalesced; k runs over the range's rows.  A range's tile goes to the range's partial gradient.
+// Each kernel has a GATED instantiation that starts with its header's gate (xarm_sacw_core.h Gate); the executor launches it only for a
+// header whose gate is set - the wide PPO update with target_kl on.  Every other launch runs the instantiation without the read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "xarm_sacw_core.h"
@@ -48,7 +50,8 @@ __device__ __forceinline__ f32x16 dot_rows(const float *ar, const float *br, int
     return acc;
 }
 
-static __global__ __launch_bounds__(64) void k_sacw_fwd(Fwd f) {
+template <bool GATED> static __global__ __launch_bounds__(64) void k_sacw_fwd(Fwd f) {
+    if (GATED && gate_shut(f.gate)) return;
     const FwdJob &a = f.j[blockIdx.z];
     if ((int)blockIdx.y * TILE >= a.N) return;
     const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
@@ -68,7 +71,8 @@ static __global__ __launch_bounds__(64) void k_sacw_fwd(Fwd f) {
     }
 }
 
-static __global__ __launch_bounds__(64) void k_sacw_bd(Bd f) {
+template <bool GATED> static __global__ __launch_bounds__(64) void k_sacw_bd(Bd f) {
+    if (GATED && gate_shut(f.gate)) return;
     const BdJob &a = f.j[blockIdx.z];
     if ((int)blockIdx.y * TILE >= a.N) return;
     const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
@@ -112,7 +116,8 @@ static __global__ __launch_bounds__(64) void k_sacw_bd(Bd f) {
     }
 }
 
-static __global__ __launch_bounds__(64) void k_sacw_wg(Wg f) {
+template <bool GATED> static __global__ __launch_bounds__(64) void k_sacw_wg(Wg f) {
+    if (GATED && gate_shut(f.gate)) return;
     const int jn = blockIdx.z / f.S, sp = blockIdx.z - jn * f.S;
     const WgJob &a = f.j[jn];
     if ((int)blockIdx.x * TILE > a.K || (int)blockIdx.y * TILE >= a.N) return;
@@ -155,9 +160,24 @@ struct GemmExec {
     hipStream_t st;
     int count;
     static unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-    void fwd(const Fwd &f) { k_sacw_fwd<<<dim3(blocks(f.B, TILE), blocks(f.maxN, TILE), f.nj), dim3(64), 0, st>>>(f); count++; }
-    void bd(const Bd &f) { k_sacw_bd<<<dim3(blocks(f.B, TILE), blocks(f.maxN, TILE), f.nj), dim3(64), 0, st>>>(f); count++; }
-    void wg(const Wg &f) { k_sacw_wg<<<dim3(blocks(f.maxK + 1, TILE), blocks(f.maxN, TILE), f.nj * f.S), dim3(64), 0, st>>>(f); count++; }
+    void fwd(const Fwd &f) {
+        const dim3 grid(blocks(f.B, TILE), blocks(f.maxN, TILE), f.nj);
+        if (f.gate.stop != nullptr) k_sacw_fwd<true><<<grid, dim3(64), 0, st>>>(f);
+        else k_sacw_fwd<false><<<grid, dim3(64), 0, st>>>(f);
+        count++;
+    }
+    void bd(const Bd &f) {
+        const dim3 grid(blocks(f.B, TILE), blocks(f.maxN, TILE), f.nj);
+        if (f.gate.stop != nullptr) k_sacw_bd<true><<<grid, dim3(64), 0, st>>>(f);
+        else k_sacw_bd<false><<<grid, dim3(64), 0, st>>>(f);
+        count++;
+    }
+    void wg(const Wg &f) {
+        const dim3 grid(blocks(f.maxK + 1, TILE), blocks(f.maxN, TILE), f.nj * f.S);
+        if (f.gate.stop != nullptr) k_sacw_wg<true><<<grid, dim3(64), 0, st>>>(f);
+        else k_sacw_wg<false><<<grid, dim3(64), 0, st>>>(f);
+        count++;
+    }
 };
 
 }  // namespace xsacw

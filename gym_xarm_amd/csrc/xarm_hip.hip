@@ -1052,8 +1052,18 @@ int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params
                     const float *action, const float *reward, const float *done, const float *use, const float *last_obs,
                     const float *old_logp, const int32_t *perm, void *workspace, float *out_adv, float *out_returns, float *out_grad,
                     float *out_stats, void *stream) {
+    return xarm_ppo_update_opt(layout, params, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, use, last_obs, old_logp, perm,
+                               workspace, out_adv, out_returns, out_grad, out_stats, nullptr, stream);
+}
+
+int xarm_ppo_update_opt(const xarm_ppo_layout *layout, const xarm_ppo_params *params, const xarm_policy_weights *weights,
+                        const xarm_policy_weights *exp_avg, const xarm_policy_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                        const float *action, const float *reward, const float *done, const float *use, const float *last_obs,
+                        const float *old_logp, const int32_t *perm, void *workspace, float *out_adv, float *out_returns, float *out_grad,
+                        float *out_stats, const xarm_ppo_options *options, void *stream) {
     if (const char *why = xppo::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
     if (const char *why = xppo::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
+    if (const char *why = xppo::options_error(options)) return fail(nullptr, XARM_E_INVALID, "xarm_ppo_update: %s", why);
     if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppo_update: weights / exp_avg / exp_avg_sq is NULL");
     if (layout->num_envs == 0) return XARM_OK;
     if (const char *why = xppo::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, last_obs, perm, workspace))
@@ -1061,7 +1071,7 @@ int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params
     xppo::Dev d = {};
     xppo::Work k;
     xppo::fill_shape(d.s, layout);
-    xppo::fill_hyper(d.h, params);
+    xppo::fill_hyper(d.h, params, options);
     xppo::fill_work(k, d.s);
     xa2c::tensors_of(weights, d.w);
     xa2c::tensors_of(exp_avg, d.m);
@@ -1074,7 +1084,7 @@ int xarm_ppo_update(const xarm_ppo_layout *layout, const xarm_ppo_params *params
     d.boot = (float *)(base + k.boot); d.mean = (float *)(base + k.mean); d.env = (float *)(base + k.env); d.value = (float *)(base + k.value);
     d.adv = (float *)(base + k.adv); d.ret = (float *)(base + k.ret); d.oldlp = (float *)(base + k.oldlp); d.musig = (double *)(base + k.musig);
     d.partial = (float *)(base + k.partial); d.scal = (double *)(base + k.scal); d.grad = (float *)(base + k.grad);
-    d.normpart = (double *)(base + k.normpart); d.adam = (float *)(base + k.adam);
+    d.normpart = (double *)(base + k.normpart); d.adam = (float *)(base + k.adam); d.stop = (int *)(d.adam + 2);
     d.out_adv = out_adv; d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
     const int le = xppo::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_ppo_update: %s", hipGetErrorString((hipError_t)le));
@@ -1246,15 +1256,25 @@ int xarm_ppow_update(const xarm_ppow_layout *layout, const xarm_ppo_params *para
                      const xarm_acw_weights *exp_avg_sq, int64_t *step_i64, const float *obs, const float *action, const float *reward,
                      const float *done, const float *use, const float *last_obs, const float *old_logp, const int32_t *perm, void *workspace,
                      float *out_adv, float *out_returns, float *out_grad, float *out_stats, void *stream) {
+    return xarm_ppow_update_opt(layout, params, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, use, last_obs, old_logp, perm,
+                                workspace, out_adv, out_returns, out_grad, out_stats, nullptr, stream);
+}
+
+int xarm_ppow_update_opt(const xarm_ppow_layout *layout, const xarm_ppo_params *params, const xarm_acw_weights *weights,
+                         const xarm_acw_weights *exp_avg, const xarm_acw_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                         const float *action, const float *reward, const float *done, const float *use, const float *last_obs,
+                         const float *old_logp, const int32_t *perm, void *workspace, float *out_adv, float *out_returns, float *out_grad,
+                         float *out_stats, const xarm_ppo_options *options, void *stream) {
     if (const char *why = xppow::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
     if (const char *why = xppo::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
+    if (const char *why = xppo::options_error(options)) return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
     if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_ppow_update: weights / exp_avg / exp_avg_sq is NULL");
     if (layout->num_envs == 0) return XARM_OK;
     if (const char *why = xppow::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, action, reward, done, last_obs, perm, workspace))
         return fail(nullptr, XARM_E_INVALID, "xarm_ppow_update: %s", why);
     xppow::Dev d = {};
     xppow::fill_shape(d, layout);
-    xppo::fill_hyper(d.h, params);
+    xppo::fill_hyper(d.h, params, options);
     xppow::tensors_of(d, weights, d.w);
     xppow::tensors_of(d, exp_avg, d.m);
     xppow::tensors_of(d, exp_avg_sq, d.v);

@@ -17,6 +17,8 @@
 //                   gradient; a block's sum of squares to normpart; block 0's thread 0 writes the step's stats row, advances `step`
 //                   (every read of the old value - the previous step's k_ppo_apply - lies behind a kernel boundary) and Adam's scalars
 //   k_ppo_apply     one thread per parameter: norm from normpart in block order, the clip, Adam
+// With target_kl on (xarm_ppo_core.h, options) k_ppo_gae's first thread clears the stop flag, k_ppo_reduce's stats thread sets it, and
+// a stopped step's three launches return after one uniform read of it (its reduce writes the stopped stats row first).
 // No atomics anywhere: the same inputs and perm give the same bits.
 #include <hip/hip_runtime.h>
 #include "xarm_ppo_core.h"
@@ -31,6 +33,7 @@ __global__ __launch_bounds__(256) void k_ppo_gae(Dev d) {
     const xa2c::Shape &a = d.s.a;
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= a.N) return;
+    if (n == 0 && d.h.kl_limit > 0.0) d.stop[0] = 0;
     if (d.old_logp == nullptr) {
         float nodls[MAX_ACT];
         d.oldlp[n] = xa2c::pi_row<false>(a.A, d.mean + n * a.A, 1, d.action + n * a.A, d.w[12], 0.0f, nullptr, 0, nodls);
@@ -107,8 +110,9 @@ struct PpoHead {
             sums[2] += (double)u;
         } else {
             const float v = D3[0], rt = d.ret[n];
-            D3[0] = xa2c::value_delta(d.h.vf2, v, rt, u);
-            sums[1] += (double)((rt - v) * (rt - v) * u);
+            const ValueTerms vt = value_terms(d.h, v, d.h.vclip > 0.0f ? d.value[n] : v, rt, u);
+            D3[0] = vt.dvalue;
+            sums[1] += (double)vt.loss;
             sums[2] += (double)u;
         }
     }
@@ -116,6 +120,7 @@ struct PpoHead {
 
 // JW: columns of dW1 per thread; the tile holds 16 JW >= D columns
 template <int JW> __global__ __launch_bounds__(THREADS) void k_ppo_grad(Dev d, int step) {
+    if (stopped_before(d.h, d.stop, step)) return;
     XARM_TILE_LDS(JW);
     __shared__ int Rt[ROWS];
     const int t = threadIdx.x;
@@ -153,29 +158,41 @@ template <int JW> __global__ __launch_bounds__(THREADS) void k_ppo_grad(Dev d, i
 }
 
 __global__ __launch_bounds__(RED) void k_ppo_reduce(Dev d, int step) {
+    if (stopped_before(d.h, d.stop, step)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && d.out_stats != nullptr) stopped_row(d.out_stats + (int64_t)step * 8);
+        return;
+    }
     __shared__ double red[RED];
     const xa2c::Shape &a = d.s.a;
     const int G = a.G;
     const double n_use = xa2c::reduce_block(a, d.partial, d.scal, NSCAL, d.h.ent_coef, d.grad, step == 0 ? d.out_grad : nullptr, red, d.normpart);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int64_t t = d.step[0] + 1;
-        d.step[0] = t;
-        xopt::adam_scalars(d.h.adam, t, d.adam);
-        if (d.out_stats != nullptr) {
-            double surr = 0.0, vloss = 0.0, kl = 0.0, clipped = 0.0;
+        double surr = 0.0, vloss = 0.0, kl = 0.0, clipped = 0.0;
+        if (d.out_stats != nullptr || d.h.kl_limit > 0.0)
             for (int g = 0; g < G; g++) {
                 const double *pi = d.scal + (int64_t)g * NSCAL, *vf = d.scal + ((int64_t)G + g) * NSCAL;
                 surr += pi[0]; kl += pi[19]; clipped += pi[20]; vloss += vf[1];
             }
+        const bool trips = kl_trips(d.h, (float)(kl / n_use));
+        if (trips) {
+            d.stop[0] = step + 1;
+        } else {
+            const int64_t t = d.step[0] + 1;
+            d.step[0] = t;
+            xopt::adam_scalars(d.h.adam, t, d.adam);
+        }
+        if (d.out_stats != nullptr) {
             const double ent = xopt::gaussian_entropy(d.w[12], a.A);
             float *o = d.out_stats + (int64_t)step * 8;
             o[0] = (float)(-surr / n_use); o[1] = (float)(vloss / n_use); o[2] = (float)ent; o[4] = (float)n_use;
-            o[5] = (float)(kl / n_use); o[6] = (float)(clipped / n_use); o[7] = 0.0f;
+            o[5] = (float)(kl / n_use); o[6] = (float)(clipped / n_use); o[7] = trips ? 1.0f : 0.0f;
+            if (trips) o[3] = 0.0f;
         }
     }
 }
 
 __global__ __launch_bounds__(RED) void k_ppo_apply(Dev d, int step) {
+    if (stopped_at(d.h, d.stop)) return;
     const xa2c::Shape &a = d.s.a;
     const int64_t p = (int64_t)blockIdx.x * RED + threadIdx.x;
     float norm;

@@ -21,6 +21,12 @@
 //              dvalue = 2 vf_coef ((value - ret) use); mean and value under the weights of the step
 //   gradient   g = (float)(sum / n_use), n_use = max(n, 1); log_std: - ent_coef on top; clip as in A2C
 //   Adam       t = ++step; xopt::adam_scalars and xopt::adam (xarm_opt_core.h)
+//   options    (xarm_ppo_options; both off: every launch, grid and bit as without them)
+//              clip_range_vf: value_terms() below, against the row's call-start value v0
+//              target_kl: kl_trips() on the float32 approx_kl of the step's stats row.  The workspace holds one int, `stop`: 0, or
+//              1 + the step that tripped.  The call-start launch clears it, the step's reduce sets it, and with stop != 0 the launches
+//              of every later step (stopped_before) and the apply launch of the tripping step itself (stopped_at) return after one read
+//              of it; a stopped step's reduce writes the stats row stopped_row() first.  `step` advances by the applied steps
 #pragma once
 #include <stdint.h>
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
@@ -53,6 +59,8 @@ struct Hyper {
     xopt::Adam adam;
     double ent_coef;
     int normalize;
+    float vclip;                    // (float)clip_range_vf; 0: off
+    double kl_limit;                // 1.5 target_kl; 0: off
 };
 
 // byte offsets of the parts of the workspace (each 16-byte aligned)
@@ -119,11 +127,20 @@ inline void fill_shape(Shape &s, const xarm_ppo_layout *l) {
     s.a.G = (int)(s.a.tiles < xa2c::MAX_GROUPS ? s.a.tiles : xa2c::MAX_GROUPS);
 }
 
-inline void fill_hyper(Hyper &h, const xarm_ppo_params *p) {
+inline const char *options_error(const xarm_ppo_options *o) {
+    if (!o) return nullptr;
+    if (!(o->clip_range_vf >= 0.0) || !(o->clip_range_vf < 1e300)) return "clip_range_vf must be finite and >= 0 (0 = off)";
+    if (!(o->target_kl >= 0.0) || !(o->target_kl < 1e300)) return "target_kl must be finite and >= 0 (0 = off)";
+    return nullptr;
+}
+
+inline void fill_hyper(Hyper &h, const xarm_ppo_params *p, const xarm_ppo_options *o = nullptr) {
     h.gamma = (float)p->gamma; h.gl = (float)(p->gamma * p->gae_lambda);
     h.clip = (float)p->clip_range; h.clip_lo = (float)(1.0 - p->clip_range); h.clip_hi = (float)(1.0 + p->clip_range);
     xopt::fill_adam(h.adam, p->lr, p->beta1, p->beta2, p->eps);
     h.vf2 = (float)(2.0 * p->vf_coef); h.max_norm = (float)p->max_grad_norm; h.ent_coef = p->ent_coef; h.normalize = p->normalize_advantage != 0;
+    h.vclip = o ? (float)o->clip_range_vf : 0.0f;
+    h.kl_limit = o ? 1.5 * o->target_kl : 0.0;
 }
 
 inline void fill_work(Work &k, const Shape &s) {
@@ -142,7 +159,7 @@ inline void fill_work(Work &k, const Shape &s) {
     k.scal = take(2 * (int64_t)a.G * NSCAL * 8);
     k.grad = take(a.P * 4);
     k.normpart = take((int64_t)a.NB * 8);
-    k.adam = take(16);
+    k.adam = take(16);              // Adam's two scalars; the third word is the KL stop's flag
     k.total = at;
 }
 
@@ -196,6 +213,40 @@ XARM_HD RowTerms surrogate(const Hyper &h, float ahat, float logp, float old_log
     return t;
 }
 
+// the value head of a row: its output delta and its term of the value loss.  v: the value under the step's weights, v0: at call start (read
+// only with clip_range_vf on).  Inside the range the terms are those of the update without the option, from v itself.  ON = false: for a
+// kernel instantiated for calls with the option off (the wide head: its row loop then stays the one basic block it was)
+struct ValueTerms {
+    float dvalue, loss;
+};
+
+template <bool ON = true> XARM_HD ValueTerms value_terms(const Hyper &h, float v, float v0, float ret, float use) {
+    ValueTerms t;
+    t.dvalue = xa2c::value_delta(h.vf2, v, ret, use);
+    t.loss = (ret - v) * (ret - v) * use;
+    if (ON && h.vclip > 0.0f && !(__builtin_fabsf(v - v0) <= h.vclip)) {
+        const float vp = v > v0 ? v0 + h.vclip : v0 - h.vclip;
+        t.dvalue = 0.0f;
+        t.loss = (ret - vp) * (ret - vp) * use;
+    }
+    return t;
+}
+
+// the KL stop.  kl: the float32 approx_kl of the step's stats row
+XARM_HD bool kl_trips(const Hyper &h, float kl) { return h.kl_limit > 0.0 && (double)kl > h.kl_limit; }
+// stop: the workspace's flag, 0 or 1 + the step that tripped.  A launch reads it only with target_kl on
+XARM_HD bool stopped_before(const Hyper &h, const int *stop, int64_t st) {
+    if (!(h.kl_limit > 0.0)) return false;
+    const int f = stop[0];
+    return f != 0 && (int64_t)f <= st;
+}
+XARM_HD bool stopped_at(const Hyper &h, const int *stop) { return h.kl_limit > 0.0 && stop[0] != 0; }
+// the stats row of a step behind the one that tripped
+XARM_HD void stopped_row(float *o) {
+    for (int k = 0; k < 7; k++) o[k] = 0.0f;
+    o[7] = 1.0f;
+}
+
 #if !defined(__HIPCC__) || defined(XARM_HOST_BUILD)
 // ---- the whole update as plain loops (the host build).  w / m / v: the 13 tensors.  out_old_logp [N] (host build only): the call-start
 // log-probabilities in use.
@@ -235,7 +286,12 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
 
     std::vector<double> G((size_t)a.P);
     std::vector<float> chunk((size_t)a.P), g((size_t)a.P);
+    int stop = 0;
     for (int64_t st = 0; st < s.S; st++) {
+        if (stopped_before(h, &stop, st)) {
+            if (out_stats) stopped_row(out_stats + st * 8);
+            continue;
+        }
         int64_t first, count;
         step_span(s, st, first, count);
         double ms[NMS], n = 0.0, sa = 0.0, sv = 0.0;
@@ -273,10 +329,10 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
                 xa2c::pi_row<true>(A, mean, 1, action + r * A, log_std, t.q, d3, 1, dls);
                 for (int c = 0; c < A; c++) chunk[(size_t)a.off[12] + c] += dls[c];
                 xa2c::host_backward(a, chunk.data(), pi, 0, x, h1, h2, d3, A);
-                const float dv = xa2c::value_delta(h.vf2, val_now, rt, u);
-                xa2c::host_backward(a, chunk.data(), vf, 6, x, g1, g2, &dv, 1);
+                const ValueTerms vt = value_terms(h, val_now, val[(size_t)r], rt, u);
+                xa2c::host_backward(a, chunk.data(), vf, 6, x, g1, g2, &vt.dvalue, 1);
                 surr += (double)t.surr; kl += (double)t.kl; clipped += (double)t.clipped;
-                vloss += (double)((rt - val_now) * (rt - val_now) * u);
+                vloss += (double)vt.loss;
             }
             if ((i + 1) % ROWS == 0 || i + 1 == count) flush();
         }
@@ -296,6 +352,11 @@ inline void host_update(const Shape &s, const Hyper &h, float *const *w, float *
             float *o = out_stats + st * 8;
             o[0] = (float)(-surr / n_use); o[1] = (float)(vloss / n_use); o[2] = (float)ent; o[3] = norm; o[4] = (float)n_use;
             o[5] = (float)(kl / n_use); o[6] = (float)(clipped / n_use); o[7] = 0.0f;
+        }
+        if (kl_trips(h, (float)(kl / n_use))) {
+            stop = (int)st + 1;
+            if (out_stats) { out_stats[st * 8 + 3] = 0.0f; out_stats[st * 8 + 7] = 1.0f; }
+            continue;
         }
         step[0] += 1;
         float sc[2];
@@ -317,6 +378,7 @@ struct Dev {
     const float *obs, *action, *reward, *done, *use, *last_obs, *old_logp;
     const int32_t *perm;
     float *boot, *mean, *env, *value, *adv, *ret, *oldlp, *partial, *grad, *adam;
+    int *stop;                      // the KL stop's flag (adam + 2)
     double *musig, *scal, *normpart;
     float *out_adv, *out_returns, *out_grad, *out_stats;
 };

@@ -21,6 +21,12 @@
 //   sums         over rows: thread t of 256 walks rows t, t + 256, ... in float64, the 256 partials are added in t order.  Over a
 //                gradient's rows: sacw's - float32 fmaf chains within one of at most 16 ranges of whole 64-row tiles, the ranges
 //                added in float64 in range order, / n_use, rounded once.  The squares of a block of 256 parameters: a fixed tree.
+//   options      xarm_ppo_core.h's, through its functions.  clip_range_vf: the gather carries value[r] as one more column, gv0, which
+//                lies in dOvf (written by the gather, read and then overwritten by the head of the same row: no workspace is added).
+//                target_kl: the stop flag is the third word of adam; gae's row 0 clears it, finish_step sets it, and the gather, head,
+//                reduce and apply of a stopped step return on it.  So do the step's GEMM launches, through the job header's gate
+//                (xsacw::Gate; null with target_kl off and for every other user of the GEMM kernels): ungated, an update stopped at
+//                step 1 of 16 still cost 13.6 of 17.4 ms at 65 536 rows of [256, 256, 256]
 #pragma once
 #include "xarm_ppo_core.h"
 #include "xarm_sacw_core.h"
@@ -49,6 +55,8 @@ struct Dev {
     float *mean, *value, *adv, *ret, *oldlp;            // per rollout row (value: N + E)
     double *musig;                                      // [S][NMS]
     float *x, *ga, *gahat, *gret, *golp, *guse;         // the step's gathered rows
+    float *gv0;                                         // with clip_range_vf: the rows' call-start values (= dOvf, see above)
+    int *stop;                                          // the KL stop's flag (adam + 2)
     float *hid, *dH, *outM, *outV, *dOpi, *dOvf;        // activations and deltas [2][L][B, H], the towers' outputs and output deltas
     float *partial;                                     // [ranges][Ptow]
     double *scal, *normpart;                            // the step's NSCAL sums; a block's sum of squares
@@ -140,6 +148,8 @@ inline int64_t fill_work(Dev &d, void *base) {
     d.outM = take(B * g.A); d.outV = take(B); d.dOpi = take(B * g.A); d.dOvf = take(B);
     d.partial = take((int64_t)g.S * d.Ptow);
     d.grad = take(g.P);
+    d.gv0 = d.dOvf;
+    d.stop = b ? (int *)(d.adam + 2) : nullptr;
     return at;
 }
 
@@ -147,6 +157,7 @@ inline int64_t fill_work(Dev &d, void *base) {
 // call start, row n: old_logp of the stored action under the call's weights (unless given); rows n < E: their env's GAE recursion
 XARM_HD void gae_row(const Dev &d, int64_t n) {
     const xa2c::Shape &a = d.p.a;
+    if (n == 0 && d.h.kl_limit > 0.0) d.stop[0] = 0;
     if (d.old_logp == nullptr) {
         float nodls[MAX_ACT];
         d.oldlp[n] = xa2c::pi_row<false>(a.A, d.mean + n * a.A, 1, d.action + n * a.A, d.w[2 * d.g.tp], 0.0f, nullptr, 0, nodls);
@@ -193,8 +204,8 @@ XARM_HD double adv_squares(const Dev &d, int64_t st, int t, double mu) {
 }
 XARM_HD double mean_of(double n, double sa) { return n > 0.0 ? sa / n : 0.0; }
 
-// column j of gathered row i of step st: j < D obs, < D + A action, then A^, ret, old_logp, use
-XARM_HD int gather_width(const Dev &d) { return d.g.D + d.g.A + 4; }
+// column j of gathered row i of step st: j < D obs, < D + A action, then A^, ret, old_logp, use and, with clip_range_vf, v0
+XARM_HD int gather_width(const Dev &d) { return d.g.D + d.g.A + (d.h.vclip > 0.0f ? 5 : 4); }
 XARM_HD void gather_at(const Dev &d, int64_t st, int64_t i, int j) {
     const int D = d.g.D, A = d.g.A;
     int64_t first, count;
@@ -206,12 +217,13 @@ XARM_HD void gather_at(const Dev &d, int64_t st, int64_t i, int j) {
     else if (j == D + A) d.gahat[i] = in ? xppo::norm_adv(d.adv[r], d.musig + st * NMS) : 0.0f;
     else if (j == D + A + 1) d.gret[i] = in ? d.ret[r] : 0.0f;
     else if (j == D + A + 2) d.golp[i] = in ? (d.old_logp != nullptr ? d.old_logp[r] : d.oldlp[r]) : 0.0f;
-    else d.guse[i] = in ? (d.use != nullptr ? d.use[r] : 1.0f) : 0.0f;
+    else if (j == D + A + 3) d.guse[i] = in ? (d.use != nullptr ? d.use[r] : 1.0f) : 0.0f;
+    else d.gv0[i] = in ? d.value[r] : 0.0f;
 }
 
 // behind the step's forward, gathered row i: both towers' output deltas, the row's terms added to sums (xppo's record: 0 surrogate,
-// 1 value loss, 2 use, 3 + c log_std_c, 19 kl, 20 clipped)
-XARM_HD void head_row(const Dev &d, int64_t i, double *sums) {
+// 1 value loss, 2 use, 3 + c log_std_c, 19 kl, 20 clipped).  VCLIP: the call has clip_range_vf on (the launch picks the instantiation)
+template <bool VCLIP> XARM_HD void head_row(const Dev &d, int64_t i, double *sums) {
     const int A = d.g.A;
     const float u = d.guse[i], *mean = d.outM + i * A, *act = d.ga + i * A, *log_std = d.w[2 * d.g.tp];
     float dls[MAX_ACT];
@@ -221,8 +233,9 @@ XARM_HD void head_row(const Dev &d, int64_t i, double *sums) {
     const xppo::RowTerms t = xppo::surrogate(d.h, d.gahat[i], lp, d.golp[i], u);
     xa2c::pi_row<true>(A, mean, 1, act, log_std, t.q, d.dOpi + i * A, 1, dls);
     const float v = d.outV[i], rt = d.gret[i];
-    d.dOvf[i] = xa2c::value_delta(d.h.vf2, v, rt, u);
-    sums[0] += (double)t.surr; sums[1] += (double)((rt - v) * (rt - v) * u); sums[2] += (double)u;
+    const xppo::ValueTerms vt = xppo::value_terms<VCLIP>(d.h, v, VCLIP ? d.gv0[i] : v, rt, u);
+    d.dOvf[i] = vt.dvalue;
+    sums[0] += (double)t.surr; sums[1] += (double)vt.loss; sums[2] += (double)u;
     sums[19] += (double)t.kl; sums[20] += (double)t.clipped;
 #pragma unroll
     for (int c = 0; c < MAX_ACT; c++)
@@ -243,16 +256,28 @@ template <class D> XARM_HD float param_grad(const D &d, const double *scal, int6
 }
 template <class D> XARM_HD float param_grad(const D &d, int64_t p) { return param_grad(d, d.scal, p); }
 
-// one thread per step, in the reduce launch: step++, Adam's scalars, the stats row (slot 3, the norm, is the apply launch's)
+// one thread per step, in the reduce launch: the KL stop's decision; step++ and Adam's scalars unless it trips; the stats row (slot 3, the
+// norm, is the apply launch's, which a tripping step does not reach)
 XARM_HD void finish_step(const Dev &d, int64_t st) {
-    const int64_t t = d.step[0] + 1;
-    d.step[0] = t;
-    xopt::adam_scalars(d.h.adam, t, d.adam);
+    const double n_use = n_use_of(d);
+    const bool trips = xppo::kl_trips(d.h, (float)(d.scal[19] / n_use));
+    if (trips) {
+        d.stop[0] = (int)st + 1;
+    } else {
+        const int64_t t = d.step[0] + 1;
+        d.step[0] = t;
+        xopt::adam_scalars(d.h.adam, t, d.adam);
+    }
     if (d.out_stats == nullptr) return;
-    const double n_use = n_use_of(d), ent = xopt::gaussian_entropy(d.w[2 * d.g.tp], d.g.A);
+    const double ent = xopt::gaussian_entropy(d.w[2 * d.g.tp], d.g.A);
     float *o = d.out_stats + st * 8;
     o[0] = (float)(-d.scal[0] / n_use); o[1] = (float)(d.scal[1] / n_use); o[2] = (float)ent; o[4] = (float)n_use;
-    o[5] = (float)(d.scal[19] / n_use); o[6] = (float)(d.scal[20] / n_use); o[7] = 0.0f;
+    o[5] = (float)(d.scal[19] / n_use); o[6] = (float)(d.scal[20] / n_use); o[7] = trips ? 1.0f : 0.0f;
+    if (trips) o[3] = 0.0f;
+}
+// the reduce launch of a step behind the one that tripped: its stats row, by one thread
+XARM_HD void skip_step(const Dev &d, int64_t st) {
+    if (d.out_stats != nullptr) xppo::stopped_row(d.out_stats + st * 8);
 }
 
 // the norm from normpart's NB blocks in block order; returns the clip coefficient
@@ -303,11 +328,12 @@ template <class X> void run_update(const Dev &d, X &ex) {
         float *out[2] = {d.outM, d.outV};
         const int64_t base[2] = {0, d.Ppi};
         const int t0[2] = {0, tp};
+        const xsacw::Gate gate = {d.h.kl_limit > 0.0 ? d.stop : nullptr, st};
         ex.gather(d, st);
-        xsacw::fwd_pass(g, ex, 2, T, in, hid, out);
-        ex.head(d);
-        xsacw::bd_pass(g, ex, 2, T, dO, hid, dh);
-        xsacw::wg_pass(g, d.partial, ex, 2, T, in, dO, hid, dh, base, t0, d.Ptow);
+        xsacw::fwd_pass(g, ex, 2, T, in, hid, out, gate);
+        ex.head(d, st);
+        xsacw::bd_pass(g, ex, 2, T, dO, hid, dh, gate);
+        xsacw::wg_pass(g, d.partial, ex, 2, T, in, dO, hid, dh, base, t0, d.Ptow, gate);
         ex.reduce(d, st);
         ex.apply(d, st);
     }
@@ -354,24 +380,31 @@ struct HostExec : xsacw::HostExec {
         }
     }
     void gather(const Dev &d, int64_t st) {
+        if (xppo::stopped_before(d.h, d.stop, st)) return;
         const int W = gather_width(d);
         for (int64_t i = 0; i < d.g.B; i++)
             for (int j = 0; j < W; j++) gather_at(d, st, i, j);
     }
-    void head(const Dev &d) {
+    void head(const Dev &d, int64_t st) {
+        if (xppo::stopped_before(d.h, d.stop, st)) return;
         double tot[NSCAL] = {0.0};
         for (int t = 0; t < RED; t++) {
             double sums[NSCAL] = {0.0};
-            for (int64_t i = t; i < d.g.B; i += RED) head_row(d, i, sums);
+            for (int64_t i = t; i < d.g.B; i += RED) {
+                if (d.h.vclip > 0.0f) head_row<true>(d, i, sums);
+                else head_row<false>(d, i, sums);
+            }
             for (int k = 0; k < NSCAL; k++) tot[k] += sums[k];
         }
         for (int k = 0; k < NSCAL; k++) d.scal[k] = tot[k];
     }
     void reduce(const Dev &d, int64_t st) {
+        if (xppo::stopped_before(d.h, d.stop, st)) { skip_step(d, st); return; }
         host_reduce_blocks(d, d.p.a.NB, st == 0);
         finish_step(d, st);
     }
     void apply(const Dev &d, int64_t st) {
+        if (xppo::stopped_at(d.h, d.stop)) return;
         float norm;
         const float coef = clip_of(d, norm);
         if (d.out_stats != nullptr) d.out_stats[st * 8 + 3] = norm;

@@ -189,12 +189,22 @@ inline int64_t fill_work_act(Dev &d, void *base) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ the three GEMM jobs
+// a launch's gate: null, or a flag in the learner's workspace - 0, or 1 + the optimiser step at which the learner stopped.  A gated launch
+// of step `at` returns after one uniform read when the flag names an earlier step.  The wide PPO update's KL stop sets it
+// (xarm_ppow_core.h); every other caller leaves the job header's gate null, and the kernels then read nothing
+struct Gate { const int *stop; int64_t at; };
+XARM_HD bool gate_shut(const Gate &g) {
+    if (g.stop == nullptr) return false;
+    const int f = g.stop[0];
+    return f != 0 && (int64_t)f <= g.at;
+}
+
 struct FwdJob { const float *x, *W, *b; float *out; int K, N, act, vec; };                 // out [B, N] = act(x [B, K] W^T + b)
-struct Fwd { int64_t B; int nj, maxN; FwdJob j[4]; };
+struct Fwd { int64_t B; int nj, maxN; FwdJob j[4]; Gate gate; };
 struct BdJob { const float *d, *W, *h; float *out, *out2; int K, ldw, c0, N, mode, vec; }; // out [B, N] = (d [B, K] W[:, c0 : c0 + N]) dact(h); out2 nullable copy
-struct Bd { int64_t B; int nj, maxN; BdJob j[2]; };
+struct Bd { int64_t B; int nj, maxN; BdJob j[2]; Gate gate; };
 struct WgJob { const float *d, *x; int N, K; int64_t poff, boff; };                         // range s: partial[s][poff + j K + i], partial[s][boff + j]
-struct Wg { int nj, S, maxN, maxK; int64_t pstride; float *partial; int64_t rows[MAX_SPLIT + 1]; WgJob j[2 * (MAX_L + 1)]; };
+struct Wg { int nj, S, maxN, maxK; int64_t pstride; float *partial; int64_t rows[MAX_SPLIT + 1]; WgJob j[2 * (MAX_L + 1)]; Gate gate; };
 
 XARM_HD float act_f(int act, float x) { return act == ACT_RELU ? (x > 0.0f ? x : 0.0f) : (act == ACT_TANH ? xpol::tanh_f(x) : x); }
 XARM_HD float dact_f(int act, float h) { return act == ACT_RELU ? (h > 0.0f ? 1.0f : 0.0f) : fma32(-h, h, 1.0f); }
@@ -205,10 +215,11 @@ struct TowerRef { float *const *p; int Din, nout; };
 inline int vec_ok(const void *a, const void *b, int K) { return (K % 8 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0) ? 1 : 0; }
 
 // layer by layer: tower T[j] on in[j] [B, Din]; hidden layer l of job j goes to hid[j] + l B H, the outputs to out[j] [B, nout]
-template <class X> void fwd_pass(const Shape &s, X &ex, int nj, const TowerRef *T, const float *const *in, float *const *hid, float *const *out) {
+template <class X> void fwd_pass(const Shape &s, X &ex, int nj, const TowerRef *T, const float *const *in, float *const *hid, float *const *out,
+                                 Gate gate = Gate{nullptr, 0}) {
     for (int l = 0; l < s.NL; l++) {
         Fwd f = {};
-        f.B = s.B; f.nj = nj;
+        f.B = s.B; f.nj = nj; f.gate = gate;
         for (int j = 0; j < nj; j++) {
             FwdJob &a = f.j[j];
             a.x = l == 0 ? in[j] : hid[j] + (l - 1) * s.BH;
@@ -223,10 +234,11 @@ template <class X> void fwd_pass(const Shape &s, X &ex, int nj, const TowerRef *
 }
 
 // the hidden deltas of tower T[j] from its output deltas dO[j] [B, nout]: layer l's go to dH[j] + l B H
-template <class X> void bd_pass(const Shape &s, X &ex, int nj, const TowerRef *T, const float *const *dO, float *const *hid, float *const *dH) {
+template <class X> void bd_pass(const Shape &s, X &ex, int nj, const TowerRef *T, const float *const *dO, float *const *hid, float *const *dH,
+                                Gate gate = Gate{nullptr, 0}) {
     for (int l = s.L - 1; l >= 0; l--) {
         Bd f = {};
-        f.B = s.B; f.nj = nj; f.maxN = s.H;
+        f.B = s.B; f.nj = nj; f.maxN = s.H; f.gate = gate;
         for (int j = 0; j < nj; j++) {
             BdJob &a = f.j[j];
             a.d = l + 1 == s.NL - 1 ? dO[j] : dH[j] + (l + 1) * s.BH;
@@ -240,9 +252,9 @@ template <class X> void bd_pass(const Shape &s, X &ex, int nj, const TowerRef *T
 
 // every layer's weight and bias gradient of towers T[j] in one launch; tower j's slice starts at base[j] of a range's partial
 template <class X> void wg_pass(const Shape &s, float *partial, X &ex, int nj, const TowerRef *T, const float *const *in, const float *const *dO,
-                                float *const *hid, float *const *dH, const int64_t *base, const int *t0, int64_t pstride) {
+                                float *const *hid, float *const *dH, const int64_t *base, const int *t0, int64_t pstride, Gate gate = Gate{nullptr, 0}) {
     Wg f = {};
-    f.S = s.S; f.pstride = pstride; f.partial = partial;
+    f.S = s.S; f.pstride = pstride; f.partial = partial; f.gate = gate;
     for (int k = 0; k <= MAX_SPLIT; k++) f.rows[k] = s.rows[k];
     for (int j = 0; j < nj; j++)
         for (int l = 0; l < s.NL; l++) {
@@ -472,6 +484,7 @@ template <class X> void run_act(const Dev &d, X &ex) {
 struct HostExec {
     static float pad(int n, float acc) { return (n & 1) ? fma32(0.0f, 0.0f, acc) : acc; }
     void fwd(const Fwd &f) {
+        if (gate_shut(f.gate)) return;
         for (int jn = 0; jn < f.nj; jn++) {
             const FwdJob &a = f.j[jn];
             std::vector<float> Wt((size_t)a.K * a.N), acc((size_t)a.N);
@@ -489,6 +502,7 @@ struct HostExec {
         }
     }
     void bd(const Bd &f) {
+        if (gate_shut(f.gate)) return;
         for (int jn = 0; jn < f.nj; jn++) {
             const BdJob &a = f.j[jn];
             std::vector<float> acc((size_t)a.N);
@@ -508,6 +522,7 @@ struct HostExec {
         }
     }
     void wg(const Wg &f) {
+        if (gate_shut(f.gate)) return;
         for (int jn = 0; jn < f.nj; jn++) {
             const WgJob &a = f.j[jn];
             for (int sp = 0; sp < f.S; sp++) {

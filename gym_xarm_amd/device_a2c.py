@@ -145,6 +145,13 @@ class DeviceA2C:
             return acw_weights(tensors, self.device, "DeviceA2C")
         return policy_weights(tensors, self.device, "DeviceA2C")
 
+    def set_hyper(self, **kw):
+        """rewrite entries of `hyper` (lr, ...): the next update reads them"""
+        for k, v in kw.items():
+            if k not in self.hyper:
+                raise KeyError("DeviceA2C has no hyper-parameter %r (it has %s)" % (k, ", ".join(sorted(self.hyper))))
+            self.hyper[k] = v
+
     def store(self, k, obs, action, reward, done, resetting=None):
         """slot k of the rollout (train.store_rollout)"""
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)

@@ -67,7 +67,14 @@ class DevicePPO:
     model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors; they are read and written in place.
     `buffers` and `store(k, ...)` are DeviceA2C's.  `exp_avg`, `exp_avg_sq` (13 tensors each) and `step` (int64 [1]) are Adam's state,
     `perm` (int32 [n_epochs, N]) the minibatch order: all device tensors.  `stats` [S, 8]: one row per optimiser step of the last update,
-    policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, 0.  batch_size None: ceil(N / 4).
+    policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, stopped.  batch_size None: ceil(N / 4).
+
+    clip_range_vf (None: off): stable-baselines3's value clipping against the values at call start.  target_kl (None: off): SB3's early
+    stop, taken on the device - the first optimiser step whose approx_kl exceeds 1.5 target_kl, and every step after it, is not applied
+    (no parameter, no Adam state, no advance of `step`), with no host read, so the call stays capturable.  `stats[:, 7]` is 0 for an
+    applied step and 1 for one that was not; the tripping row keeps its sums with grad_norm 0, later rows are zero.  Both live in
+    `hyper`; `set_hyper(lr=..., clip_range=..., clip_range_vf=...)` rewrites entries of it between updates (train()'s schedules).  A
+    captured graph holds the hyper-parameters of its capture: schedules do not reach into it.
 
     `backend`: "tile64" - the fused 64-row tile of DESIGN.md 22, 4 + 3 S launches, for a 64-64 tanh model - or "wide" - the per-layer MFMA
     GEMM chain of DESIGN.md 25 (csrc/xarm_k_ppow.hip) for equal widths of 64, 128, 192 or 256 units in two or three layers, tanh or ReLU,
@@ -77,12 +84,13 @@ class DevicePPO:
     c = M + ceil(E / B) call-start forward chunks."""
 
     def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
-                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0, wide=None):
+                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0, wide=None,
+                 clip_range_vf=None, target_kl=None):
         self.model, self.num_envs, self.n_steps, self.n_epochs = model, int(num_envs), int(n_steps), int(n_epochs)
         N = self.num_envs * self.n_steps
         self.batch_size = int(batch_size) if batch_size is not None else max(1, -(-N // 4))
         self.hyper = dict(gamma=gamma, gae_lambda=gae_lambda, clip_range=clip_range, lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, vf_coef=vf_coef,
-                          ent_coef=ent_coef, max_grad_norm=max_grad_norm)
+                          ent_coef=ent_coef, max_grad_norm=max_grad_norm, clip_range_vf=clip_range_vf, target_kl=target_kl)
         self.normalize_advantage = bool(normalize_advantage)
         self.obs_width = int(model.pi[0].in_features)
         self.act_dim = int(model.pi[-1].out_features)
@@ -133,6 +141,13 @@ class DevicePPO:
     def _wide_weights(self, tensors):
         return acw_weights(tensors, self.device, "DevicePPO")
 
+    def set_hyper(self, **kw):
+        """rewrite entries of `hyper` (lr, clip_range, clip_range_vf, ...): the next update reads them"""
+        for k, v in kw.items():
+            if k not in self.hyper:
+                raise KeyError("DevicePPO has no hyper-parameter %r (it has %s)" % (k, ", ".join(sorted(self.hyper))))
+            self.hyper[k] = v
+
     def store(self, k, obs, action, reward, done, resetting=None):
         """slot k of the rollout (train.store_rollout)"""
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
@@ -153,17 +168,17 @@ class DevicePPO:
         b = self.buffers
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         params = _native.XarmPPOParams(*([float(hyper[k]) for k in _native.PPO_HYPER] + [int(self.normalize_advantage)]))
+        vclip, kl = hyper.get("clip_range_vf"), hyper.get("target_kl")
+        options = None if vclip is None and kl is None else C.byref(_native.XarmPPOOptions(float(vclip or 0.0), float(kl or 0.0)))
         args = (p(step), p(b["obs"]), p(b["action"]), p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(old_logp), p(self.perm), p(b["workspace"]),
-                p(out_adv), p(out_returns), p(out_grad), p(out_stats), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+                p(out_adv), p(out_returns), p(out_grad), p(out_stats), options, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         if self.backend == "wide":
             ws = [self._wide_weights(ts) for ts in (weights, exp_avg, exp_avg_sq)]        # held until the call has returned
-            rc = self._L.xarm_ppow_update(C.byref(self._layout), C.byref(params), *[C.byref(x) for x in ws], *args)
+            rc = self._L.xarm_ppow_update_opt(C.byref(self._layout), C.byref(params), *[C.byref(x) for x in ws], *args)
             _native.check(self._L, None, rc, "xarm_ppow_update")
             return
-        W = lambda ts: C.byref(policy_weights(ts, self.device, "DevicePPO"))
-        rc = self._L.xarm_ppo_update(C.byref(self._layout), C.byref(params), W(weights), W(exp_avg), W(exp_avg_sq), p(step), p(b["obs"]), p(b["action"]),
-                                     p(b["reward"]), p(b["done"]), p(b["use"]), p(last_obs), p(old_logp), p(self.perm), p(b["workspace"]), p(out_adv),
-                                     p(out_returns), p(out_grad), p(out_stats), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        ws = [policy_weights(ts, self.device, "DevicePPO") for ts in (weights, exp_avg, exp_avg_sq)]
+        rc = self._L.xarm_ppo_update_opt(C.byref(self._layout), C.byref(params), *[C.byref(x) for x in ws], *args)
         _native.check(self._L, None, rc, "xarm_ppo_update")
 
     def update(self, last_obs, shuffle=True, old_logp=None, out_adv=None, out_returns=None, out_grad=None):
@@ -186,6 +201,10 @@ class DevicePPO:
         g, a, r, st = torch.empty(self.num_params, device=dev), torch.empty(T, E, device=dev), torch.empty(T, E, device=dev), torch.zeros_like(self.stats)
         self._call(w, m, v, self.step.clone(), last_obs, dict(self.hyper, lr=0.0), old_logp, a, r, g, st)
         return g, a, r, st
+
+    def steps_applied(self):
+        """optimiser steps the last update applied, from `stats[:, 7]` (reads back: not for a capture)"""
+        return int((self.stats[:self.num_steps, 7] == 0).sum().item())
 
     def load_optimizer(self, opt):
         """continue from a torch.optim.Adam built on the same module"""

@@ -367,10 +367,20 @@ def ppo_prepare(model, rollout, last_obs, gamma=0.99, gae_lambda=0.95, old_logp=
     return adv.flatten(), (adv + values).flatten(), old_logp.flatten(), rollout["use"].flatten()
 
 
-def ppo_minibatch_loss(model, rollout, prep, idx, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True, diagnostics=False):
+def ppo_old_values(model, rollout):
+    """flat [N] values of the rollout's rows under the model as it is - what ppo_prepare's returns were built from, and what
+    ppo_minibatch_loss(clip_range_vf=...) clips against"""
+    with torch.no_grad():
+        return model.value(rollout["obs"]).flatten()
+
+
+def ppo_minibatch_loss(model, rollout, prep, idx, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, normalize_advantage=True, diagnostics=False,
+                       clip_range_vf=None, old_values=None):
     """(loss, terms) of the rows idx of ppo_prepare's `prep`: the advantage normalised over the minibatch's used rows (unless switched
     off, or fewer than two are used), the surrogate clipped at clip_range, value loss and entropy.  terms: the rows' rho, log_ratio,
-    a_hat, use, surr and policy_loss, value_loss, entropy, n_use; diagnostics: approx_kl and clip_fraction as well."""
+    a_hat, use, surr, value and policy_loss, value_loss, entropy, n_use; diagnostics: approx_kl and clip_fraction as well.
+    clip_range_vf (None: off): stable-baselines3's value clipping - the value loss is taken on old_values + clamp(value - old_values,
+    +- clip_range_vf), old_values [N] being ppo_old_values() at the start of the update."""
     adv, ret, old_logp, use = prep
     o, a = rollout["obs"].flatten(0, 1)[idx], rollout["action"].flatten(0, 1)[idx]
     u, a_hat = use[idx], adv[idx]
@@ -383,10 +393,17 @@ def ppo_minibatch_loss(model, rollout, prep, idx, clip_range=0.2, vf_coef=0.5, e
     log_ratio = model.dist(o).log_prob(a).sum(-1) - old_logp[idx]
     rho = log_ratio.exp()
     surr = torch.min(rho * a_hat, rho.clamp(1.0 - clip_range, 1.0 + clip_range) * a_hat)
-    policy_loss, value_sum = -(surr * u).sum() / n_use, (((ret[idx] - model.value(o)) ** 2) * u).sum()
+    value = model.value(o)
+    if clip_range_vf is None:
+        value_pred = value
+    else:
+        if old_values is None:
+            raise ValueError("clip_range_vf needs old_values (ppo_old_values at the start of the update)")
+        value_pred = old_values[idx] + (value - old_values[idx]).clamp(-clip_range_vf, clip_range_vf)
+    policy_loss, value_sum = -(surr * u).sum() / n_use, (((ret[idx] - value_pred) ** 2) * u).sum()
     loss, entropy = _entropy_term(model, policy_loss + vf_coef * value_sum / n_use, ent_coef)
     terms = {"policy_loss": policy_loss, "value_loss": value_sum / n_use, "entropy": entropy, "n_use": n_use, "rho": rho, "log_ratio": log_ratio,
-             "a_hat": a_hat, "use": u, "surr": surr}
+             "a_hat": a_hat, "use": u, "surr": surr, "value": value}
     if diagnostics:
         with torch.no_grad():
             terms["approx_kl"] = (((rho - 1.0) - log_ratio) * u).sum() / n_use
@@ -395,16 +412,31 @@ def ppo_minibatch_loss(model, rollout, prep, idx, clip_range=0.2, vf_coef=0.5, e
 
 
 def ppo_update(model, opt, rollout, last_obs, n_epochs, batch_size, gamma=0.99, gae_lambda=0.95, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
-               max_grad_norm=0.5, normalize_advantage=True):
+               max_grad_norm=0.5, normalize_advantage=True, clip_range_vf=None, target_kl=None):
     """stable-baselines3's PPO.train() on one rollout: n_epochs passes over minibatches of batch_size rows, a torch.randperm from the
-    global generator per pass"""
+    global generator per pass.  clip_range_vf: ppo_minibatch_loss's.  target_kl (None: off): the update ends before the optimiser step
+    of the first minibatch whose approx_kl exceeds 1.5 target_kl (one host read per minibatch, as in SB3).  Returns the number of
+    optimiser steps applied."""
     prep = ppo_prepare(model, rollout, last_obs, gamma, gae_lambda)
-    n_rows = prep[0].numel()
+    old_values = None if clip_range_vf is None else ppo_old_values(model, rollout)
+    n_rows, applied = prep[0].numel(), 0
     for _ in range(n_epochs):
         perm = torch.randperm(n_rows, device=last_obs.device)
         for m in range(0, n_rows, batch_size):
-            loss, _ = ppo_minibatch_loss(model, rollout, prep, perm[m:m + batch_size], clip_range, vf_coef, ent_coef, normalize_advantage)
+            loss, terms = ppo_minibatch_loss(model, rollout, prep, perm[m:m + batch_size], clip_range, vf_coef, ent_coef, normalize_advantage,
+                                             diagnostics=target_kl is not None, clip_range_vf=clip_range_vf, old_values=old_values)
+            if target_kl is not None and float(terms["approx_kl"]) > 1.5 * target_kl:
+                return applied
             optimizer_step(model, opt, loss, max_grad_norm)
+            applied += 1
+    return applied
+
+
+def linear_schedule(initial):
+    """progress_remaining (1 at the start of training, 0 at its end) -> progress_remaining * initial: stable-baselines3's usual schedule
+    for lr and clip_range"""
+    initial = float(initial)
+    return lambda progress_remaining: progress_remaining * initial
 
 
 class _TorchLearner:
@@ -416,6 +448,17 @@ class _TorchLearner:
 
     def store(self, k, obs, action, reward, done, resetting=None):
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
+
+    def set_hyper(self, **kw):
+        """rewrite hyper-parameters between updates: lr goes into the optimiser's param_groups, every other key into `hyper`"""
+        for k, v in kw.items():
+            if k == "lr":
+                for g in self.opt.param_groups:
+                    g["lr"] = v
+            elif k in self.hyper:
+                self.hyper[k] = v
+            else:
+                raise KeyError("%s has no hyper-parameter %r (it has lr, %s)" % (type(self).__name__, k, ", ".join(sorted(self.hyper))))
 
 
 class TorchA2C(_TorchLearner):
@@ -431,19 +474,26 @@ class TorchPPO(_TorchLearner):
     """batch_size None: ceil(N / 4)"""
 
     def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
-                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True):
+                 betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, clip_range_vf=None,
+                 target_kl=None):
         super().__init__(model, num_envs, n_steps, torch.optim.Adam(model.parameters(), lr=lr, betas=betas, eps=eps),
                          n_epochs=n_epochs, batch_size=max(1, -(-n_steps * num_envs // 4)) if batch_size is None else int(batch_size), gamma=gamma,
                          gae_lambda=gae_lambda, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm,
-                         normalize_advantage=normalize_advantage)
+                         normalize_advantage=normalize_advantage, clip_range_vf=clip_range_vf, target_kl=target_kl)
+        self._applied = 0
 
     def update(self, last_obs):
-        ppo_update(self.model, self.opt, self.buffers, last_obs, **self.hyper)
+        self._applied = ppo_update(self.model, self.opt, self.buffers, last_obs, **self.hyper)
+
+    def steps_applied(self):
+        """optimiser steps the last update applied (fewer than n_epochs x minibatches when target_kl stopped it)"""
+        return self._applied
 
 
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
-          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None, wide=None):
+          device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None, wide=None,
+          clip_range_vf=None, target_kl=None):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -463,7 +513,13 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     device_update run equal widths of 64, 128, 192 or 256 units in two or three layers on their "wide" backends; the A2C
     device_update runs them on its "wide" backend when wide=True, and without it is the 64-64 tanh shape's and raises
     ValueError for any other.
-    wide: handed to DeviceA2C / DevicePPO and to DevicePolicy as their `wide`; None leaves each class its default."""
+    wide: handed to DeviceA2C / DevicePPO and to DevicePolicy as their `wide`; None leaves each class its default.
+    clip_range_vf / target_kl (ppo; None: off): stable-baselines3's value clipping and early stop, in the torch block and in DevicePPO's
+    kernels alike.  With target_kl the log records carry `ppo_steps_applied`, the optimiser steps the last update applied.
+    lr, clip_range and clip_range_vf take a float or a callable of progress_remaining (linear_schedule): the learner is built with
+    f(1) and `set_hyper` gets f(1 - it / updates) just before update `it` - where SB3 calls _update_current_progress_remaining, so a
+    linear schedule runs its last update at 0.  A float is never passed through set_hyper.  Out of scope: schedules inside a captured
+    graph (it holds the hyper-parameters of its capture), SAC schedules, use_sde, an in-call device shuffle."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
     ppo = algo == "ppo"
@@ -489,6 +545,15 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     hyper = dict(n_steps=n_steps, gamma=gamma, lr=lr, eps=1e-5)
     if ppo:
         hyper.update(n_epochs=n_epochs, batch_size=batch_size, gae_lambda=gae_lambda, clip_range=clip_range)
+        if clip_range_vf is not None or target_kl is not None:
+            hyper.update(clip_range_vf=clip_range_vf, target_kl=target_kl)
+    elif clip_range_vf is not None or target_kl is not None:
+        raise ValueError("clip_range_vf and target_kl are PPO's (algo='ppo')")
+    schedules = {k: f for k, f in hyper.items() if callable(f)}
+    hyper.update({k: f(1.0) for k, f in schedules.items()})
+    if device_update and "clip_range" in schedules and not schedules["clip_range"](0.0) > 0.0:
+        raise ValueError("the device update needs clip_range > 0 at every update: this schedule gives %r at the last one (the torch block runs it)"
+                         % (schedules["clip_range"](0.0),))
     if device_update and ppo:
         from .device_ppo import DevicePPO
         learner = DevicePPO(model, num_envs, seed=seed, wide=wide, **hyper)
@@ -525,6 +590,8 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
             done_sum += done.float().sum()
             raw_sum += raw.mean()
             obs = nobs
+        if schedules:
+            learner.set_hyper(**{k: f(1.0 - it / updates) for k, f in schedules.items()})
         learner.update(obs)
         if it % log_every == 0 or it == updates:
             if dev.type == "cuda":
@@ -532,6 +599,8 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
             rec = {"update": it, "env_steps": it * n_steps * num_envs, "mean_raw_reward": (raw_sum / (log_every * n_steps)).item(),
                    "success_rate": (succ_sum / done_sum.clamp(min=1)).item(), "episodes": int(done_sum.item()),
                    "env_steps_per_sec": it * n_steps * num_envs / (time.perf_counter() - t0)}
+            if target_kl is not None:
+                rec["ppo_steps_applied"] = learner.steps_applied()
             hist.append(rec)
             if not quiet:
                 print(json.dumps(rec), flush=True)
@@ -570,7 +639,15 @@ def main(argv=None):
     ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="tanh (default) or relu (stable-baselines3's SAC default)")
     ap.add_argument("--wide", action="store_true", help="a2c / ppo: the per-layer GEMM chain for --device-update and --device-policy whatever the shape "
                                                         "(a2c: needed for any shape but 64 64 tanh)")
+    ap.add_argument("--target-kl", type=float, default=None, help="ppo: stop an update before the first step whose approx_kl exceeds 1.5 x this")
+    ap.add_argument("--clip-range-vf", type=float, default=None, help="ppo: clip the value's move from its call-start value to +- this")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant", help="a2c / ppo: linear runs lr down to 0 over --updates")
+    ap.add_argument("--clip-range-schedule", choices=("constant", "linear"), default="constant", help="ppo: linear runs clip_range (0.2) down to 0")
     args = ap.parse_args(argv)
+    if args.algo != "ppo" and (args.target_kl is not None or args.clip_range_vf is not None or args.clip_range_schedule != "constant"):
+        ap.error("--target-kl, --clip-range-vf and --clip-range-schedule are for --algo ppo")
+    if args.algo == "sac" and args.lr_schedule != "constant":
+        ap.error("--lr-schedule is for --algo a2c / ppo")
     if args.wide and args.algo == "sac":
         ap.error("--wide is for --algo a2c / ppo: the SAC device update selects its backend by shape")
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
@@ -589,7 +666,9 @@ def main(argv=None):
                               log_dir=args.log_dir, check_freq=args.check_freq, device_normalize=args.device_normalize,
                               device_policy=args.device_policy, device_update=args.device_update, algo=args.algo, n_steps=args.n_steps,
                               n_epochs=args.n_epochs, batch_size=args.batch_size, net_arch=None if args.net_arch is None else tuple(args.net_arch),
-                              activation=args.activation, wide=True if args.wide else None)
+                              activation=args.activation, wide=True if args.wide else None, clip_range_vf=args.clip_range_vf, target_kl=args.target_kl,
+                              lr=linear_schedule(3e-4 if args.algo == "ppo" else 7e-4) if args.lr_schedule == "linear" else None,
+                              clip_range=linear_schedule(0.2) if args.clip_range_schedule == "linear" else 0.2)
     if args.save:
         save_model(args.save, model, venv)
 
