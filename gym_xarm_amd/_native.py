@@ -26,7 +26,8 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
            "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update",
            "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update", "xarm_ppow_update_opt",
-           "xarm_a2cw_workspace_bytes", "xarm_a2cw_update"]
+           "xarm_a2cw_workspace_bytes", "xarm_a2cw_update",
+           "xarm_perm_fill"]
 HO_MAX_STAGES = 5           # XARM_HO_MAX_STAGES
 RENDER_SHADOWS = 1          # include/xarm_hip.h XARM_RENDER_SHADOWS
 RENDER_MAX_DIM = 2048       # XARM_RENDER_MAX_DIM
@@ -260,6 +261,7 @@ def load(path=None):
     wa = C.POINTER(XarmA2CWLayout)
     L.xarm_a2cw_workspace_bytes.argtypes = [wa, C.POINTER(C.c_int64)]
     L.xarm_a2cw_update.argtypes = [wa, C.POINTER(XarmA2CParams), cw, cw] + [vp] * 11
+    L.xarm_perm_fill.argtypes = [vp, C.c_int32, C.c_int64, C.c_uint64, vp, vp]
     L.xarm_last_error.argtypes = [vp]
     L.xarm_last_error.restype = C.c_char_p
     L.xarm_version.argtypes = []

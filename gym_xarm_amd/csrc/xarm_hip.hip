@@ -41,6 +41,7 @@
 #include "xarm_acw_core.h"
 #include "xarm_ppow_core.h"
 #include "xarm_a2cw_core.h"
+#include "xarm_rollout_core.h"
 
 using namespace xd;
 
@@ -1317,6 +1318,17 @@ int xarm_a2cw_update(const xarm_a2cw_layout *layout, const xarm_a2c_params *para
     d.out_returns = out_returns; d.out_grad = out_grad; d.out_stats = out_stats;
     const int le = xa2cw::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_a2cw_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+
+// ------------------------------------------------------------------------------------- device shuffle (xarm_k_rollout.hip)
+int xarm_perm_fill(int32_t *perm_i32, int32_t n_epochs, int64_t N, uint64_t seed, int64_t *calls_i64, void *stream) {
+    if (const char *why = xroll::perm_error(n_epochs, N)) return fail(nullptr, XARM_E_INVALID, "xarm_perm_fill: %s", why);
+    if (N == 0) return XARM_OK;
+    if (!perm_i32 || !calls_i64) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_perm_fill: NULL pointer");
+    const int le = xroll::launch_perm_fill(perm_i32, n_epochs, N, seed, calls_i64, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_perm_fill: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

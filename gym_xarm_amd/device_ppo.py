@@ -66,7 +66,9 @@ class DevicePPO:
 
     model: a train.ActorCritic whose parameters are contiguous float32 CUDA tensors; they are read and written in place.
     `buffers` and `store(k, ...)` are DeviceA2C's.  `exp_avg`, `exp_avg_sq` (13 tensors each) and `step` (int64 [1]) are Adam's state,
-    `perm` (int32 [n_epochs, N]) the minibatch order: all device tensors.  `stats` [S, 8]: one row per optimiser step of the last update,
+    `perm` (int32 [n_epochs, N]) the minibatch order: all device tensors.  shuffle: what refills `perm` in front of an update - "torch"
+    (torch.randperm per epoch) or "device" (xarm_perm_fill, csrc/xarm_k_rollout.hip, DESIGN.md 27: capturable; `perm_calls` int64 [1] counts
+    its draws).  `stats` [S, 8]: one row per optimiser step of the last update,
     policy_loss, value_loss, entropy, grad_norm, n_use, approx_kl, clip_fraction, stopped.  batch_size None: ceil(N / 4).
 
     clip_range_vf (None: off): stable-baselines3's value clipping against the values at call start.  target_kl (None: off): SB3's early
@@ -85,7 +87,10 @@ class DevicePPO:
 
     def __init__(self, model, num_envs, n_steps=16, n_epochs=4, batch_size=None, gamma=0.99, gae_lambda=0.95, clip_range=0.2, lr=3e-4,
                  betas=(0.9, 0.999), eps=1e-5, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, normalize_advantage=True, seed=0, wide=None,
-                 clip_range_vf=None, target_kl=None):
+                 clip_range_vf=None, target_kl=None, shuffle="torch"):
+        if shuffle not in ("torch", "device"):
+            raise ValueError("DevicePPO: shuffle must be 'torch' or 'device', not %r" % (shuffle,))
+        self.shuffle_mode, self.seed = shuffle, int(seed)
         self.model, self.num_envs, self.n_steps, self.n_epochs = model, int(num_envs), int(n_steps), int(n_epochs)
         N = self.num_envs * self.n_steps
         self.batch_size = int(batch_size) if batch_size is not None else max(1, -(-N // 4))
@@ -130,6 +135,7 @@ class DevicePPO:
         self.num_params = sum(p.numel() for p in self.params())
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(int(seed))
+        self.perm_calls = torch.zeros(1, dtype=torch.int64, device=dev) if shuffle == "device" else None    # shuffles drawn so far
 
     def params(self):
         """the trained tensors in the flat order of out_grad: pi's W1, b1, ..., vf's, log_std (the 13 of xarm_policy_weights on "tile64")"""
@@ -153,8 +159,15 @@ class DevicePPO:
         store_rollout(self.buffers, k, obs, action, reward, done, resetting)
 
     def shuffle(self):
-        """a fresh permutation per epoch from the object's own seeded device generator, in place (allocates: not for a capture)"""
+        """a fresh permutation per epoch, in place.  shuffle="torch": torch.randperm from the object's own seeded device generator
+        (allocates: not for a capture).  shuffle="device": xarm_perm_fill keyed by (seed, `perm_calls`) on the current stream - two launches,
+        no allocation, no host read; the fill advances `perm_calls` on the device, so a captured call draws a fresh shuffle per replay."""
         N = self.num_envs * self.n_steps
+        if self.shuffle_mode == "device":
+            rc = self._L.xarm_perm_fill(C.c_void_p(self.perm.data_ptr()), self.n_epochs, N, self.seed, C.c_void_p(self.perm_calls.data_ptr()),
+                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            _native.check(self._L, None, rc, "xarm_perm_fill")
+            return
         for ep in range(self.n_epochs):
             self.perm[ep].copy_(torch.randperm(N, generator=self._gen, device=self.device))
 
@@ -183,8 +196,9 @@ class DevicePPO:
 
     def update(self, last_obs, shuffle=True, old_logp=None, out_adv=None, out_returns=None, out_grad=None):
         """one update from the stored rollout and the observation after its last step; the module's parameters, Adam's state and `step`
-        change in place, `stats` is rewritten.  shuffle: refill `perm` first.  With shuffle=False nothing is allocated and nothing is
-        read back, so the call can be captured in a torch.cuda.graph; a captured user calls shuffle() between replays.  old_logp [T, E]:
+        change in place, `stats` is rewritten.  shuffle: refill `perm` first.  With shuffle=False, or on a DevicePPO(shuffle="device"),
+        nothing is allocated and nothing is read back, so the call can be captured in a torch.cuda.graph - with the device shuffle inside
+        it; a captured user of the torch shuffle calls shuffle() between replays.  old_logp [T, E]:
         used in place of the log-probabilities at call start.  out_adv / out_returns [T, E], out_grad [num_params] (debug): the
         advantages before normalisation, the returns and step 0's gradient before the clip."""
         if shuffle:

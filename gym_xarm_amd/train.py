@@ -493,7 +493,7 @@ class TorchPPO(_TorchLearner):
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
           device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None, wide=None,
-          clip_range_vf=None, target_kl=None):
+          clip_range_vf=None, target_kl=None, shuffle=None):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -518,8 +518,10 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     kernels alike.  With target_kl the log records carry `ppo_steps_applied`, the optimiser steps the last update applied.
     lr, clip_range and clip_range_vf take a float or a callable of progress_remaining (linear_schedule): the learner is built with
     f(1) and `set_hyper` gets f(1 - it / updates) just before update `it` - where SB3 calls _update_current_progress_remaining, so a
-    linear schedule runs its last update at 0.  A float is never passed through set_hyper.  Out of scope: schedules inside a captured
-    graph (it holds the hyper-parameters of its capture), SAC schedules, use_sde, an in-call device shuffle."""
+    linear schedule runs its last update at 0.  A float is never passed through set_hyper.
+    shuffle (ppo with device_update; None: "torch"): "torch" - torch.randperm per epoch - or "device" - DevicePPO's xarm_perm_fill, HIP launches
+    inside the update call that allocate nothing and read nothing back.
+    Out of scope: schedules inside a captured graph (it holds the hyper-parameters of its capture), SAC schedules, use_sde."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
     ppo = algo == "ppo"
@@ -554,9 +556,13 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     if device_update and "clip_range" in schedules and not schedules["clip_range"](0.0) > 0.0:
         raise ValueError("the device update needs clip_range > 0 at every update: this schedule gives %r at the last one (the torch block runs it)"
                          % (schedules["clip_range"](0.0),))
+    if shuffle not in (None, "torch", "device"):
+        raise ValueError("shuffle must be None, 'torch' or 'device', not %r" % (shuffle,))
+    if shuffle == "device" and ppo and not device_update:
+        raise ValueError("shuffle='device' is DevicePPO's (device_update=True); the torch update shuffles with torch.randperm")
     if device_update and ppo:
         from .device_ppo import DevicePPO
-        learner = DevicePPO(model, num_envs, seed=seed, wide=wide, **hyper)
+        learner = DevicePPO(model, num_envs, seed=seed, wide=wide, shuffle=shuffle or "torch", **hyper)
     elif device_update:
         from .device_a2c import DeviceA2C
         learner = DeviceA2C(model, num_envs, wide=wide, **hyper)
@@ -643,11 +649,14 @@ def main(argv=None):
     ap.add_argument("--clip-range-vf", type=float, default=None, help="ppo: clip the value's move from its call-start value to +- this")
     ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant", help="a2c / ppo: linear runs lr down to 0 over --updates")
     ap.add_argument("--clip-range-schedule", choices=("constant", "linear"), default="constant", help="ppo: linear runs clip_range (0.2) down to 0")
+    ap.add_argument("--shuffle", choices=("torch", "device"), default=None, help="ppo with --device-update: the minibatch shuffle (default torch; device: a HIP launch inside the update call)")
     args = ap.parse_args(argv)
     if args.algo != "ppo" and (args.target_kl is not None or args.clip_range_vf is not None or args.clip_range_schedule != "constant"):
         ap.error("--target-kl, --clip-range-vf and --clip-range-schedule are for --algo ppo")
     if args.algo == "sac" and args.lr_schedule != "constant":
         ap.error("--lr-schedule is for --algo a2c / ppo")
+    if args.algo != "ppo" and args.shuffle is not None:
+        ap.error("--shuffle is for --algo ppo")
     if args.wide and args.algo == "sac":
         ap.error("--wide is for --algo a2c / ppo: the SAC device update selects its backend by shape")
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
@@ -668,7 +677,7 @@ def main(argv=None):
                               n_epochs=args.n_epochs, batch_size=args.batch_size, net_arch=None if args.net_arch is None else tuple(args.net_arch),
                               activation=args.activation, wide=True if args.wide else None, clip_range_vf=args.clip_range_vf, target_kl=args.target_kl,
                               lr=linear_schedule(3e-4 if args.algo == "ppo" else 7e-4) if args.lr_schedule == "linear" else None,
-                              clip_range=linear_schedule(0.2) if args.clip_range_schedule == "linear" else 0.2)
+                              clip_range=linear_schedule(0.2) if args.clip_range_schedule == "linear" else 0.2, shuffle=args.shuffle)
     if args.save:
         save_model(args.save, model, venv)
 

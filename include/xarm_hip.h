@@ -823,6 +823,20 @@ int xarm_a2cw_update(const xarm_a2cw_layout *layout, const xarm_a2c_params *para
                      const float *use /* may be NULL */, const float *last_obs, void *workspace, float *out_returns /* may be NULL */,
                      float *out_grad /* may be NULL */, float *out_stats /* may be NULL */, void *stream);
 
+/* ---- a device shuffle for the PPO update's `perm` (gym_xarm_amd/csrc/xarm_rollout_core.h, xarm_k_rollout.hip).  Like
+ * the calls above it needs no env handle: everything is caller-owned DEVICE memory, the launches go to `stream` on the caller's current
+ * device, the messages of XARM_E_INVALID go to xarm_last_error(NULL).  The call does not allocate, synchronise, read device memory from
+ * the host or use an atomic: the same inputs give the same bits, and it can be captured in a graph. */
+/* perm_i32 [n_epochs, N] <- n_epochs independent pseudo-random permutations of [0, N), one thread per entry, no sort, no workspace:
+ * entry i of epoch ep is i enciphered by a keyed bijection of [0, 2^b), b = max(8, ceil(log2 N)), again and again until the value is
+ * below N (cycle walking).  The bijection is an alternating unbalanced Feistel network of 8 rounds over the low floor(b / 2) and the
+ * high ceil(b / 2) bits whose round function is the first word of Philox(seed; the other half, round | ep << 8, low word of calls,
+ * 0x5045524D + high word of calls), masked to the width of the half it is x-ored into.  N == 1 writes 0, N == 0 launches nothing.
+ * *calls_i64 (int64 [1], zero at the start) is read by every thread and advanced by one behind the fill, on the device, so the replays
+ * of a captured graph draw a fresh shuffle each.  Two launches.  XARM_E_INVALID: N outside [0, 2^31), n_epochs outside [1, 255], a NULL
+ * pointer with N > 0. */
+int xarm_perm_fill(int32_t *perm_i32, int32_t n_epochs, int64_t N, uint64_t seed, int64_t *calls_i64, void *stream);
+
 const char *xarm_last_error(const xarm_handle *h);
 const char *xarm_version(void);
 
