@@ -25,6 +25,7 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update", "xarm_ppo_update_opt",
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
            "xarm_sacw_workspace_bytes", "xarm_sacw_act", "xarm_sacw_update",
+           "xarm_td3_workspace_bytes", "xarm_td3_act", "xarm_td3_update",
            "xarm_acw_workspace_bytes", "xarm_acw_act", "xarm_ppow_workspace_bytes", "xarm_ppow_update", "xarm_ppow_update_opt",
            "xarm_a2cw_workspace_bytes", "xarm_a2cw_update",
            "xarm_perm_fill"]
@@ -162,6 +163,21 @@ class XarmSACWWeights(C.Structure):
     _fields_ = [(k, C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))) for k in SAC_TOWERS] + [("log_alpha", C.c_void_p)]
 
 
+TD3_HYPER = ("gamma", "lr", "tau", "beta1", "beta2", "eps", "target_policy_noise", "target_noise_clip", "action_noise")
+TD3_TOWERS = ("actor", "q1", "q2", "actor_target", "q1_target", "q2_target")
+TD3_MODES = {"deterministic": 0, "gaussian": 1, "uniform": 2}
+
+
+class XarmTD3Params(C.Structure):
+    """include/xarm_hip.h xarm_td3_params (88 bytes)"""
+    _fields_ = [("seed", C.c_uint64)] + [(k, C.c_double) for k in TD3_HYPER] + [("policy_delay", C.c_int32), ("mode", C.c_int32)]
+
+
+class XarmTD3Weights(C.Structure):
+    """include/xarm_hip.h xarm_td3_weights (48 device pointers): six towers of W1, b1, ..., W_out, b_out (eight slots)"""
+    _fields_ = [(k, C.c_void_p * (2 * (SACW_MAX_LAYERS + 1))) for k in TD3_TOWERS]
+
+
 class XarmACWLayout(C.Structure):
     """include/xarm_hip.h xarm_acw_layout (40 bytes)"""
     _fields_ = [(k, C.c_int32) for k in ("num_rows", "obs_dim", "goal_dim", "act_dim", "hidden", "n_hidden", "activation")] + [("row_offset", C.c_int64)]
@@ -251,6 +267,10 @@ def load(path=None):
     L.xarm_sacw_workspace_bytes.argtypes = [wl, C.POINTER(C.c_int64)]
     L.xarm_sacw_act.argtypes = [wl, sp, ww] + [vp] * 6
     L.xarm_sacw_update.argtypes = [wl, sp, ww, ww, ww] + [vp] * 16
+    tp_, tw = C.POINTER(XarmTD3Params), C.POINTER(XarmTD3Weights)
+    L.xarm_td3_workspace_bytes.argtypes = [wl, C.POINTER(C.c_int64)]
+    L.xarm_td3_act.argtypes = [wl, tp_, tw] + [vp] * 5
+    L.xarm_td3_update.argtypes = [wl, tp_, tw, tw, tw] + [vp] * 15
     cl = C.POINTER(XarmACWLayout)
     L.xarm_acw_workspace_bytes.argtypes = [cl, C.POINTER(C.c_int64)]
     L.xarm_acw_act.argtypes = [cl, C.POINTER(XarmPolicyParams), C.POINTER(XarmACWWeights)] + [vp] * 11

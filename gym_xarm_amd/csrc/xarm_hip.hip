@@ -38,6 +38,7 @@
 #include "xarm_ppo_core.h"
 #include "xarm_sac_core.h"
 #include "xarm_sacw_core.h"
+#include "xarm_td3_core.h"
 #include "xarm_acw_core.h"
 #include "xarm_ppow_core.h"
 #include "xarm_a2cw_core.h"
@@ -1213,6 +1214,61 @@ int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *para
     d.out_grad = out_grad; d.out_dqda = out_dqda; d.out_target = out_target; d.out_stats = out_stats; d.out_q = out_q;
     const int le = xsacw::launch_update(d, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_sacw_update: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ TD3 update (xarm_k_td3.hip)
+int xarm_td3_workspace_bytes(const xarm_sacw_layout *layout, int64_t *bytes) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_td3_workspace_bytes: %s", why);
+    if (!bytes) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_td3_workspace_bytes: NULL pointer");
+    xtd3::Dev d = {};
+    xtd3::shape_of(d.s, layout);
+    *bytes = xtd3::fill_work(d, nullptr);
+    return XARM_OK;
+}
+
+int xarm_td3_act(const xarm_sacw_layout *layout, const xarm_td3_params *params, const xarm_td3_weights *weights, int64_t *calls_i64,
+                 const float *obs, void *workspace, float *out_action, void *stream) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_td3_act: %s", why);
+    if (const char *why = xtd3::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_td3_act: %s", why);
+    if (!weights) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_td3_act: weights is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xtd3::act_pointer_error(layout, params, weights, calls_i64, obs, workspace, out_action))
+        return fail(nullptr, XARM_E_INVALID, "xarm_td3_act: %s", why);
+    xtd3::Dev d = {};
+    xtd3::shape_of(d.s, layout);
+    xtd3::fill_hyper(d.h, params);
+    for (int i = 0; i < d.s.tp; i++) d.w[i] = const_cast<float *>(weights->actor[i]);
+    xtd3::fill_work_act(d, workspace);
+    d.calls = calls_i64; d.obs = obs; d.out_action = out_action;
+    const int le = xtd3::launch_act(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_td3_act: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_td3_update(const xarm_sacw_layout *layout, const xarm_td3_params *params, const xarm_td3_weights *weights,
+                    const xarm_td3_weights *exp_avg, const xarm_td3_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *next_obs, const float *action, const float *reward, const float *done, const float *use,
+                    const float *noise_next, void *workspace, float *out_grad, float *out_target, float *out_q, float *out_dqda,
+                    float *out_stats, void *stream) {
+    if (const char *why = xsacw::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_td3_update: %s", why);
+    if (const char *why = xtd3::params_error(params)) return fail(nullptr, XARM_E_INVALID, "xarm_td3_update: %s", why);
+    if (!weights || !exp_avg || !exp_avg_sq) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_td3_update: weights / exp_avg / exp_avg_sq is NULL");
+    if (layout->batch_size == 0) return XARM_OK;
+    if (const char *why = xtd3::pointer_error(layout, weights, exp_avg, exp_avg_sq, step_i64, obs, next_obs, action, reward, done, workspace))
+        return fail(nullptr, XARM_E_INVALID, "xarm_td3_update: %s", why);
+    xtd3::Dev d = {};
+    xtd3::shape_of(d.s, layout);
+    xtd3::fill_hyper(d.h, params);
+    xtd3::tensors_of(d.s, weights, d.w, d.tg);
+    xtd3::tensors_of(d.s, exp_avg, d.m, nullptr);
+    xtd3::tensors_of(d.s, exp_avg_sq, d.v, nullptr);
+    xtd3::fill_work(d, workspace);
+    d.step = step_i64;
+    d.obs = obs; d.next_obs = next_obs; d.action = action; d.reward = reward; d.done = done; d.use = use; d.noise_next = noise_next;
+    d.out_grad = out_grad; d.out_target = out_target; d.out_q = out_q; d.out_dqda = out_dqda; d.out_stats = out_stats;
+    const int le = xtd3::launch_update(d, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_td3_update: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -152,26 +152,20 @@ def normalized_batch(venv, s):
     return b
 
 
-def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
-              lr=1e-3, tau=0.005, ent_coef="auto", target_entropy=None, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None,
-              log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None,
-              net_arch=None, activation=None):
-    """SAC + HER on a batched goal env.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
-    2 x max_episode_steps, so that closed episodes exist) every `train_freq`-th step runs `gradient_steps` SAC steps on `batch_size`
-    relabelled rows.  Observations are normalised at sample time with the running statistics; rewards stay raw.
-    device_update: the rollout action and the SAC step in HIP kernels (DeviceSAC).  device_normalize: DeviceVecNormalize (statistics,
-    Monitor and - with device_update - the sample's normalisation in HIP kernels); with both on a GPU env an iteration reads nothing
-    back outside logging.  log_dir, check_freq: Monitor CSV, best-model checkpoints and the final statistics as in train().
-    net_arch, activation: SacPolicy's (None: 64-64 tanh); a best-model checkpoint of another shape carries both beside the state_dict
-    (`load_checkpoint` rebuilds the module).
-    Returns (model, venv, hist)."""
+def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None,
+                     gamma=0.95, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None, log_dir=None, device_normalize=False, config=None,
+                     log_every=50, quiet=False, check_freq=1000, horizon=None):
+    """The driver loop that `train_sac` and `td3.train_td3` share: an off-policy learner + HER on a batched goal env.  It builds the env, the
+    normaliser, the Monitor, the callback and the HER buffer, then calls `build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)`
+    -> (model, act, learn): `act(nobs, it)` is the rollout action [E, A] of step `it`, `learn()` samples the buffer and runs one gradient step,
+    returning its stats (a tensor in the order of `stats`, or a dict of 0-d tensors keyed by it).  Returns (model, venv, hist)."""
     from .her import DeviceHerReplayBuffer, HerReplayBuffer
     from .train import EpisodeMonitor, SaveOnBestTrainingRewardCallback, VecNormalize
     torch.manual_seed(seed)
     if env is None:
         import gym_xarm_amd
         env = gym_xarm_amd.make(env_id, num_envs=num_envs, seed=seed, config=config, auto_reset=True)
-    assert not getattr(env, "_lazy", False), "train_sac stores terminal observations: it needs the in-call auto-reset (auto_reset=True)"
+    assert not getattr(env, "_lazy", False), "the off-policy driver stores terminal observations: it needs the in-call auto-reset (auto_reset=True)"
     num_envs, dev = env.num_envs, torch.device(env.device)
     act_dim = int(getattr(env, "action_dim", getattr(env, "act_dim", 0)))
     max_len = int(getattr(env, "max_episode_steps", 50))
@@ -187,26 +181,14 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
     Buffer = DeviceHerReplayBuffer if dev.type == "cuda" else HerReplayBuffer
     buffer = Buffer(env, horizon=horizon, n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=seed)
-    model = SacPolicy(venv.dim, act_dim, (64, 64) if net_arch is None else net_arch, "tanh" if activation is None else activation).to(dev)
-    if device_update:
-        from .device_sac import DeviceSAC
-        dsac = DeviceSAC(model, batch_size, gamma=gamma, lr=lr, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, seed=seed,
-                         row_offset=int(getattr(env, "_env_id_offset", 0)), act_rows=num_envs)
-        act_out = {"action": torch.empty(num_envs, act_dim, device=dev)}
-        sample = buffer.alloc_out(batch_size)
-    else:
-        opts = make_optimizers(model, lr, ent_coef)
+    model, act, learn = build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)
     obs = env.reset()
     nobs = venv.reset_from(obs) if device_normalize else venv._norm(venv._flat(obs))
     hist, t0, last, updates, window = [], time.perf_counter(), None, 0, 0
     succ_sum, done_sum, raw_sum = torch.zeros((), device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)
     for it in range(1, steps + 1):
         prev = {k: v.clone() for k, v in obs.items()}
-        if device_update:
-            a = dsac.act_into(act_out, nobs)["action"]
-        else:
-            with torch.no_grad():
-                a, _ = model.action_log_prob(nobs)
+        a = act(nobs, it)
         obs, rew, done, info = env.step(a)
         term = info.get("terminal_observation")
         if term is not None:
@@ -224,12 +206,7 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
             callback.on_step(model, venv, it * num_envs)
         if it > learning_starts and it % train_freq == 0:
             for _ in range(gradient_steps):
-                if device_update and device_normalize:
-                    last = dsac.update_from(buffer, venv, sample)
-                elif device_update:
-                    last = dsac.update(normalized_batch(venv, buffer.sample_into(sample)))
-                else:
-                    last = sac_step(model, opts, normalized_batch(venv, buffer.sample(batch_size)), gamma, tau, ent_coef, target_entropy)
+                last = learn()
                 updates += 1
         succ_sum += (info["is_success"].float() * done.float()).sum()
         done_sum += done.float().sum()
@@ -242,8 +219,8 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
                    "success_rate": (succ_sum / done_sum.clamp(min=1)).item(), "episodes": int(done_sum.item()),
                    "env_steps_per_sec": it * num_envs / (time.perf_counter() - t0)}
             if last is not None:
-                vals = last.tolist() if torch.is_tensor(last) else [float(last[k]) for k in STATS]
-                rec.update({k: float(v) for k, v in zip(STATS, vals)})
+                vals = last.tolist() if torch.is_tensor(last) else [float(last[k]) for k in stats]
+                rec.update({k: float(v) for k, v in zip(stats, vals)})
             hist.append(rec)
             if not quiet:
                 print(json.dumps(rec), flush=True)
@@ -257,6 +234,46 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
         torch.cuda.synchronize()
     env.close()
     return model, venv, hist
+
+
+def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
+              lr=1e-3, tau=0.005, ent_coef="auto", target_entropy=None, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None,
+              log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None,
+              net_arch=None, activation=None):
+    """SAC + HER on a batched goal env.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
+    2 x max_episode_steps, so that closed episodes exist) every `train_freq`-th step runs `gradient_steps` SAC steps on `batch_size`
+    relabelled rows.  Observations are normalised at sample time with the running statistics; rewards stay raw.
+    device_update: the rollout action and the SAC step in HIP kernels (DeviceSAC).  device_normalize: DeviceVecNormalize (statistics,
+    Monitor and - with device_update - the sample's normalisation in HIP kernels); with both on a GPU env an iteration reads nothing
+    back outside logging.  log_dir, check_freq: Monitor CSV, best-model checkpoints and the final statistics as in train().
+    net_arch, activation: SacPolicy's (None: 64-64 tanh); a best-model checkpoint of another shape carries both beside the state_dict
+    (`load_checkpoint` rebuilds the module).  The loop itself is `train_off_policy`, shared with td3.train_td3.
+    Returns (model, venv, hist)."""
+    def build(venv, env, buffer, dev, num_envs, act_dim, learning_starts):
+        model = SacPolicy(venv.dim, act_dim, (64, 64) if net_arch is None else net_arch, "tanh" if activation is None else activation).to(dev)
+        if device_update:
+            from .device_sac import DeviceSAC
+            dsac = DeviceSAC(model, batch_size, gamma=gamma, lr=lr, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, seed=seed,
+                             row_offset=int(getattr(env, "_env_id_offset", 0)), act_rows=num_envs)
+            act_out = {"action": torch.empty(num_envs, act_dim, device=dev)}
+            sample = buffer.alloc_out(batch_size)
+            act = lambda nobs, it: dsac.act_into(act_out, nobs)["action"]
+            if device_normalize:
+                learn = lambda: dsac.update_from(buffer, venv, sample)
+            else:
+                learn = lambda: dsac.update(normalized_batch(venv, buffer.sample_into(sample)))
+        else:
+            opts = make_optimizers(model, lr, ent_coef)
+
+            def act(nobs, it):
+                with torch.no_grad():
+                    return model.action_log_prob(nobs)[0]
+            learn = lambda: sac_step(model, opts, normalized_batch(venv, buffer.sample(batch_size)), gamma, tau, ent_coef, target_entropy)
+        return model, act, learn
+    return train_off_policy(build, STATS, env_id=env_id, num_envs=num_envs, steps=steps, batch_size=batch_size, gradient_steps=gradient_steps,
+                            train_freq=train_freq, learning_starts=learning_starts, gamma=gamma, n_sampled_goal=n_sampled_goal,
+                            goal_selection_strategy=goal_selection_strategy, seed=seed, env=env, log_dir=log_dir, device_normalize=device_normalize,
+                            config=config, log_every=log_every, quiet=quiet, check_freq=check_freq, horizon=horizon)
 
 
 def load_checkpoint(path):

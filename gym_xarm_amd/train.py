@@ -224,6 +224,8 @@ def save_model(path, model, venv):
     meta = None
     if hasattr(model, "net_arch") and hasattr(model, "activation"):
         meta = {"net_arch": ",".join(str(int(n)) for n in model.net_arch), "activation": str(model.activation)}
+        if getattr(model, "algo", None) is not None:        # td3.Td3Policy: td3.load_checkpoint checks it
+            meta["algo"] = str(model.algo)
     save_file(sd, path, metadata=meta)
 
 
@@ -633,14 +635,18 @@ def main(argv=None):
     ap.add_argument("--check-freq", type=int, default=1000)
     ap.add_argument("--device-normalize", action="store_true", help="VecNormalize + Monitor in fused HIP kernels (gym_xarm_amd/normalize.py)")
     ap.add_argument("--device-policy", action="store_true", help="the rollout's sample + clamp in one HIP launch (gym_xarm_amd/device_policy.py)")
-    ap.add_argument("--device-update", action="store_true", help="the update in HIP kernels (gym_xarm_amd/device_a2c.py, device_ppo.py, device_sac.py)")
-    ap.add_argument("--algo", choices=("a2c", "ppo", "sac"), default="a2c",
+    ap.add_argument("--device-update", action="store_true", help="the update in HIP kernels (gym_xarm_amd/device_a2c.py, device_ppo.py, device_sac.py, device_td3.py)")
+    ap.add_argument("--algo", choices=("a2c", "ppo", "sac", "td3"), default="a2c",
                     help="a2c: n-step returns, RMSprop; ppo: GAE, clipped surrogate, Adam; sac: SAC + HER (gym_xarm_amd/sac.py train_sac: --updates "
-                         "counts env steps)")
+                         "counts env steps); td3: TD3 + HER (gym_xarm_amd/td3.py train_td3, likewise)")
     ap.add_argument("--n-steps", type=int, default=None, help="rollout length (a2c 5, ppo 16)")
     ap.add_argument("--n-epochs", type=int, default=4, help="ppo: passes over a rollout")
     ap.add_argument("--batch-size", type=int, default=None, help="ppo: rows per minibatch (default: a quarter of the rollout); sac: rows per step (256)")
-    ap.add_argument("--gradient-steps", type=int, default=1, help="sac: SAC steps per training env step")
+    ap.add_argument("--gradient-steps", type=int, default=1, help="sac / td3: gradient steps per training env step")
+    ap.add_argument("--policy-delay", type=int, default=None, help="td3: the actor and the targets step on every policy_delay-th gradient step (2)")
+    ap.add_argument("--target-policy-noise", type=float, default=None, help="td3: standard deviation of the target policy smoothing noise (0.2)")
+    ap.add_argument("--target-noise-clip", type=float, default=None, help="td3: clip of the smoothing noise (0.5)")
+    ap.add_argument("--action-noise", type=float, default=None, help="td3: standard deviation of the Gaussian exploration noise (0.1)")
     ap.add_argument("--net-arch", type=int, nargs="+", default=None, help="hidden widths of every tower (default 64 64; the reference's sparse branch: 256 256 256)")
     ap.add_argument("--activation", choices=("tanh", "relu"), default=None, help="tanh (default) or relu (stable-baselines3's SAC default)")
     ap.add_argument("--wide", action="store_true", help="a2c / ppo: the per-layer GEMM chain for --device-update and --device-policy whatever the shape "
@@ -653,12 +659,16 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.algo != "ppo" and (args.target_kl is not None or args.clip_range_vf is not None or args.clip_range_schedule != "constant"):
         ap.error("--target-kl, --clip-range-vf and --clip-range-schedule are for --algo ppo")
-    if args.algo == "sac" and args.lr_schedule != "constant":
+    if args.algo in ("sac", "td3") and args.lr_schedule != "constant":
         ap.error("--lr-schedule is for --algo a2c / ppo")
+    if args.algo != "td3" and any(v is not None for v in (args.policy_delay, args.target_policy_noise, args.target_noise_clip, args.action_noise)):
+        ap.error("--policy-delay, --target-policy-noise, --target-noise-clip and --action-noise are for --algo td3")
     if args.algo != "ppo" and args.shuffle is not None:
         ap.error("--shuffle is for --algo ppo")
     if args.wide and args.algo == "sac":
         ap.error("--wide is for --algo a2c / ppo: the SAC device update selects its backend by shape")
+    if args.wide and args.algo == "td3":
+        ap.error("--wide is for --algo a2c / ppo: the TD3 device update has the per-layer GEMM chain only")
     cfg = {"reward_type": args.reward_type, "GUI": False} if ("Reach" in args.env or "PickAndPlace" in args.env) else None
     if "Handover" in args.env and "NoGoal" not in args.env:
         cfg = {"reward_type": args.reward_type}
@@ -668,6 +678,17 @@ def main(argv=None):
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
                                           device_update=args.device_update, device_normalize=args.device_normalize,
                                           net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation)
+        if args.save:
+            save_model(args.save, model, venv)
+        return
+    if args.algo == "td3":
+        from . import td3
+        extra = {k: v for k, v in (("policy_delay", args.policy_delay), ("target_policy_noise", args.target_policy_noise),
+                                   ("target_noise_clip", args.target_noise_clip), ("action_noise", args.action_noise)) if v is not None}
+        model, venv, hist = td3.train_td3(args.env, num_envs=args.num_envs, steps=args.updates, batch_size=args.batch_size or 256,
+                                          gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
+                                          device_update=args.device_update, device_normalize=args.device_normalize,
+                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation, **extra)
         if args.save:
             save_model(args.save, model, venv)
         return

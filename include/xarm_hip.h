@@ -709,6 +709,77 @@ int xarm_sacw_update(const xarm_sacw_layout *layout, const xarm_sac_params *para
                      float *out_dqda /* may be NULL */, float *out_target /* may be NULL */, float *out_stats /* may be NULL */,
                      float *out_q /* may be NULL */, void *stream);
 
+/* ---- device-resident TD3 (gym_xarm_amd/csrc/xarm_td3_core.h, xarm_k_td3.hip): ONE gradient step of stable-baselines3's
+ * TD3.train() on a batch drawn from a replay buffer, on xarm_sacw's per-layer f32 MFMA GEMM chain, for the shapes of xarm_sacw_layout
+ * (equal widths of 64, 128, 192 or 256 units, two or three hidden layers, tanh or ReLU).  Everything is caller-owned float32 DEVICE
+ * memory, row-major; B = batch_size, D = obs_dim, A = act_dim.
+ *   model    actor and actor_target D -> H x L -> A with tanh on the output; q1 / q2 / q1_target / q2_target D + A -> H x L -> 1 on the
+ *            row obs | action; a tower is 2 (n_hidden + 1) pointers W1, b1, ..., W_out, b_out as in xarm_sacw_weights
+ *   step     t = *step_i64 at call start; use NULL = all ones; n_use = max(sum use, 1); every mean is sum(. use) / n_use
+ *            a' = clamp(tanh(actor_target(next_obs)) + clamp(target_policy_noise z, -target_noise_clip, target_noise_clip), -1, 1)
+ *            y = reward + gamma (1 - done) min(q1_target, q2_target)(next_obs | a')                          (no gradient)
+ *            critic_loss = mean((q1(obs | action) - y)^2) + mean((q2(obs | action) - y)^2), Adam on q1 and q2 at count t + 1
+ *            when (t + 1) % policy_delay == 0, decided on the device:
+ *              actor_loss = -mean(q1(obs | tanh(actor(obs)))) under the stepped q1, Adam on the actor at count (t + 1) / policy_delay
+ *              target = (1 - tau) target + tau net for actor_target, q1_target and q2_target (the stepped critics)
+ *   weights  the six towers, READ AND WRITTEN in place (b1 .. W_out of each tower 16-byte aligned)
+ *   exp_avg, exp_avg_sq  Adam's state of actor, q1 and q2 in the same struct; the target fields are not read
+ *   step_i64 device int64 [1]: the calls so far (the critics' Adam count), advanced by one on the device per call
+ *   noise_next [B, A]: the step's z.  NULL: Philox keyed by (seed, row_offset + row, t), the noise stream 1 of xarm_sacw_update
+ *   workspace   xarm_td3_workspace_bytes() bytes, 16-byte aligned; holds nothing between calls
+ *   out_grad [P] (actor's tensors, q1's, q2's: the gradients after the 1 / n_use factor; the actor's part is left as it is on a call
+ *   without an actor step), out_target [B] (y), out_q [2, B] (q1, q2 at obs | action), out_dqda [B, A] (d q1 / d action at obs | a_pi
+ *   under the stepped q1; written on a call with an actor step), out_stats [8] = critic_loss, actor_loss, mean q1(obs | a_pi), mean y,
+ *   n_use, actor_stepped, 0, 0 - actor_loss and the mean q1 are left as they are on a call without an actor step, so a row that starts
+ *   at zero repeats the last actor step's values: each may be NULL
+ * A call is 7 n_hidden + 14 launches on `stream`, on delayed and undelayed calls alike (the actor phase's launches return after one
+ * uniform read of a flag in the workspace), with no allocation, no host read, no atomics and no side stream: it can be captured and
+ * replayed.  Sums run in xarm_sacw_update's fixed order: the same inputs give the same bits.
+ * xarm_td3_act is the rollout / deployment call, by params->mode: 0 out_action [B, A] = tanh(actor(obs)); 1 clamp(tanh(actor(obs)) +
+ * action_noise z, -1, 1) with z as xarm_sacw_act draws it - Philox keyed by (seed, row_offset + row, *calls, column block); 2 uniform
+ * on [-1, 1) from Philox under the same key, obs and the weights not read.  Modes 1 and 2 are followed by a one-thread launch that
+ * advances `calls`.  A row's result does not depend on the batch it is in.  n_hidden + 2 launches (1 in mode 2; + the tick).
+ * Out of scope: DDPG and n_critics != 2, unequal widths, a fourth hidden layer, widths above 256, use_sde.  batch_size == 0 launches
+ * nothing. */
+typedef struct xarm_td3_params {
+    uint64_t seed;
+    double gamma;               /* [0, 1] */
+    double lr;                  /* >= 0 */
+    double tau;                 /* [0, 1] */
+    double beta1;               /* [0, 1) */
+    double beta2;               /* [0, 1) */
+    double eps;                 /* > 0 */
+    double target_policy_noise; /* finite, >= 0 */
+    double target_noise_clip;   /* finite, >= 0 */
+    double action_noise;        /* xarm_td3_act, mode 1: finite, >= 0 */
+    int32_t policy_delay;       /* >= 1 */
+    int32_t mode;               /* xarm_td3_act: 0 deterministic, 1 Gaussian, 2 uniform */
+} xarm_td3_params;              /* 88 bytes */
+typedef struct xarm_td3_weights {
+    const float *actor[2 * (XARM_SACW_MAX_LAYERS + 1)];     /* W1 [H, D], b1 [H], W2 [H, H], b2 [H], (W3 [H, H], b3 [H],) W_out [A, H], b_out [A] */
+    const float *q1[2 * (XARM_SACW_MAX_LAYERS + 1)];        /* W1 [H, D + A], b1, ..., W_out [1, H], b_out [1] */
+    const float *q2[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *actor_target[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *q1_target[2 * (XARM_SACW_MAX_LAYERS + 1)];
+    const float *q2_target[2 * (XARM_SACW_MAX_LAYERS + 1)];
+} xarm_td3_weights;             /* 48 device pointers */
+/* *bytes = size of `workspace` for this layout (of either call).  XARM_E_INVALID: NULL argument or unusable layout (xarm_sacw's). */
+int xarm_td3_workspace_bytes(const xarm_sacw_layout *layout, int64_t *bytes);
+/* XARM_E_INVALID: what xarm_sacw_act's layout check refuses, NULL params / weights, a mode outside {0, 1, 2}, a policy_delay < 1, a
+ * negative noise or clip, tau or gamma outside [0, 1]; with batch_size > 0 a NULL or misaligned actor tensor or a NULL obs (modes 0 and
+ * 1), a NULL out_action, a NULL calls with mode != 0, a NULL or not 16-byte aligned workspace. */
+int xarm_td3_act(const xarm_sacw_layout *layout, const xarm_td3_params *params, const xarm_td3_weights *weights, int64_t *calls_i64,
+                 const float *obs, void *workspace, float *out_action, void *stream);
+/* XARM_E_INVALID: every case xarm_sacw_update refuses (with the six towers of xarm_td3_weights in place of its five and log_alpha),
+ * policy_delay < 1, a negative or non-finite target_policy_noise, target_noise_clip or action_noise, tau outside [0, 1].  All checks
+ * come before any launch. */
+int xarm_td3_update(const xarm_sacw_layout *layout, const xarm_td3_params *params, const xarm_td3_weights *weights,
+                    const xarm_td3_weights *exp_avg, const xarm_td3_weights *exp_avg_sq, int64_t *step_i64, const float *obs,
+                    const float *next_obs, const float *action, const float *reward, const float *done,
+                    const float *use /* may be NULL */, const float *noise_next /* may be NULL */, void *workspace,
+                    float *out_grad /* may be NULL */, float *out_target /* may be NULL */, float *out_q /* may be NULL */,
+                    float *out_dqda /* may be NULL */, float *out_stats /* may be NULL */, void *stream);
+
 /* ---- wide device-resident MlpPolicy (gym_xarm_amd/csrc/xarm_acw_core.h, xarm_k_acw.hip): xarm_policy_act's contract for
  * gym_xarm_amd/train.py's ActorCritic(net_arch, activation) with equal-width towers of n_hidden = 2 or 3 hidden layers of hidden = 64,
  * 128, 192 or 256 units, tanh or ReLU (XARM_SACW_TANH / XARM_SACW_RELU).  Rows, stats, calls, the noise and the four outputs mean what
