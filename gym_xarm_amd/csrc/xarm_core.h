@@ -744,16 +744,35 @@ XARM_HD bool substep(EnvState<T> &st, const T (&qt)[9], const T dt, Lds lds, con
     }
 
     // ---------------- (M) motors, (L) limits, (G) gear: row constants
-    T m_vt[9], m_invd[9], m_lam[9];
+    // TWO sets of every impulse the sweep carries (the table lam[3] of each slot, m_lam, la_lam, lf_lam, g_lam): a sweep reads the impulses of the sweep
+    // before it from one set and writes its own into the other, and the loop is unrolled by two so that which set is which is
+    // fixed in the code.  With one set (XK_SWEEP_V1, the form the host build keeps for comparison) `lam = nl` after
+    // `dl = nl - lam` cannot reuse lam's register while dl is still to be formed: the clamp writes a fresh register and a
+    // v_mov_b32 per row carries it round the loop - 27 of the 368 instructions of the fast sweep.  Same values,
+    // same arithmetic, same order (xc::sweep_all, xarm_coop_core.h, has the same two forms).
+    // The product form is what the pad-free FAST substep runs.  The full substep keeps the first form: its sweep carries the pad
+    // phase, four copies of it (two loops, each unrolled by two) take k_step from 13.4 k to 17.2 k instructions and put scratch
+    // accesses into its sweep loop.  -DXK_SWEEP_FULL builds the full substep with the product form as well (the
+    // host comparison, tests/test_lane_sweep_forms.py, and timing variants).
+#if defined(XK_SWEEP_V1)
+    constexpr bool SWEEP_TWO = false;
+#elif defined(XK_SWEEP_FULL)
+    constexpr bool SWEEP_TWO = true;
+#else
+    constexpr bool SWEEP_TWO = FAST;
+#endif
+    constexpr int LSETS = SWEEP_TWO ? 2 : 1;
+    T m_vt[9], m_invd[9], m_lam[LSETS][9];
 #pragma unroll
     for (int i = 0; i < 9; i++) {
         m_vt[i] = (T)xm::MOTOR_KP * (qt[i] - st.q[i]) * idt + (T)(1.0 - xm::MOTOR_KD) * dq[i];
         m_invd[i] = (T)1 / Minv[tri(i, i)];
-        m_lam[i] = (T)0;
+#pragma unroll
+        for (int l = 0; l < LSETS; l++) m_lam[l][i] = (T)0;
     }
     const T m_hi_arm = (T)(xm::ARM_MOTOR_FORCE * Scene::TIME_STEP), m_hi_fin = (T)(Scene::FINGER_MOTOR_FORCE * Scene::TIME_STEP);
     // arm joints: range > 2 * window, so at most one side is inside the window
-    T la_vt[7], la_sg[7], la_lam[7];
+    T la_vt[7], la_sg[7], la_lam[LSETS][7];
 #pragma unroll
     for (int i = 0; i < 7; i++) {
         const T g0 = st.q[i] - (T)xm::LOWER[i], g1 = (T)xm::UPPER[i] - st.q[i];
@@ -761,21 +780,25 @@ XARM_HD bool substep(EnvState<T> &st, const T (&qt)[9], const T dt, Lds lds, con
         const T g = lo ? g0 : g1;
         la_sg[i] = lo ? (T)1 : (hi ? (T)-1 : (T)0);
         la_vt[i] = g < (T)0 ? -(T)xm::GLOBAL_ERP * g * idt : -g * idt;
-        la_lam[i] = (T)0;
+#pragma unroll
+        for (int l = 0; l < LSETS; l++) la_lam[l][i] = (T)0;
     }
     // finger joints: range (0.04) < window, both sides always present
-    T lf_vt[2][2], lf_lam[2][2];
+    T lf_vt[2][2], lf_lam[LSETS][2][2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const T g0 = st.q[7 + k] - (T)xm::LOWER[7 + k], g1 = (T)xm::UPPER[7 + k] - st.q[7 + k];
         lf_vt[k][0] = g0 < (T)0 ? -(T)xm::GLOBAL_ERP * g0 * idt : -g0 * idt;
         lf_vt[k][1] = g1 < (T)0 ? -(T)xm::GLOBAL_ERP * g1 * idt : -g1 * idt;
-        lf_lam[k][0] = lf_lam[k][1] = (T)0;
+#pragma unroll
+        for (int l = 0; l < LSETS; l++) lf_lam[l][k][0] = lf_lam[l][k][1] = (T)0;
     }
     const T g_vt = -(T)(xm::GEAR_ERP * xm::GLOBAL_ERP) * (st.q[7] - st.q[8]) * idt;
     const T g_hi = (T)(xm::GEAR_MAX_FORCE * Scene::TIME_STEP);
     const T g_invd = (T)1 / (Minv[tri(7, 7)] - (T)2 * Minv[tri(8, 7)] + Minv[tri(8, 8)]);
-    T g_lam = (T)0;
+    T g_lam[LSETS];
+#pragma unroll
+    for (int l = 0; l < LSETS; l++) g_lam[l] = (T)0;
 
     // ---------------- (F) finger pad spheres against the object
     static_assert(xm::NPAD == 2, "the finger block below fuses exactly two pad points per finger");
@@ -967,194 +990,224 @@ XARM_HD bool substep(EnvState<T> &st, const T (&qt)[9], const T dt, Lds lds, con
 #define XARM_DQ_AXPY(col, dl_) do { _Pragma("unroll") for (int k_ = 0; k_ < 4; k_++) dqp[k_] = pkfma(MC[col][k_], (dl_), dqp[k_]); dq8 += ML[col] * (dl_); } while (0)
     // ---------------- projected Gauss-Seidel, rows in the order T, M, L, G, F
     const T mu_p = (T)xm::MU_OBJECT * (st.mug > (T)0.5 ? (T)xm::MU_FINGER_GRASP : (T)xm::MU_FINGER);
-#pragma unroll 1
-    for (int it = 0; it < XK_SWEEP_ITERS; it++) {
-        XARM_LDS_FENCE(); // keep the S / T reads of this sweep as LDS reads inside the loop
-        // (T) object / table points: n = +z, t1 = -y, t2 = +x
+    // the table impulses: set 0 is tp[s].lam itself, set 1 (two-set form only) is t_lam1[s]
+    T t_lam1[SWEEP_TWO ? NTS : 1][3];
 #pragma unroll
-        for (int s = 0; s < NTS; s++) {
-            TablePoint<T> &P = tp[s];
-            // no wave-level skip: the slot math is a no-op for inactive lanes (1/diag = 0) and, being independent of the
-            // motor rows that follow, fills their dependency stalls when both sit in one basic block
-            const T Kxy = lds[LDS_TBL + s * 8 + 0], Kxz = lds[LDS_TBL + s * 8 + 1], Kyy = lds[LDS_TBL + s * 8 + 2],
-                    Kyz = lds[LDS_TBL + s * 8 + 3], Kzz = lds[LDS_TBL + s * 8 + 4];
-            V3<T> u = vb + cross(wb, P.r);
-            T dl = (P.vt - u.z) * lds[LDS_TBL + s * 8 + 5];
-            T nl = P.lam[0] + dl;
-            nl = smax0(nl);
-            dl = nl - P.lam[0];
-            P.lam[0] = nl;
-            V3<T> fi = mk<T>((T)0, (T)0, dl);
-            u = u + mk<T>(Kxz, Kyz, Kzz) * dl;
-            const T lim = mu_t * P.lam[0];
-            dl = u.y * lds[LDS_TBL + s * 8 + 6]; // t1 = -y: jv = -u.y, target 0
-            nl = sclamp(P.lam[1] + dl, -lim, lim);
-            dl = nl - P.lam[1];
-            P.lam[1] = nl;
-            fi.y = -dl;
-            u = u - mk<T>(Kxy, Kyy, Kyz) * dl;
-            dl = -u.x * lds[LDS_TBL + s * 8 + 7]; // t2 = +x
-            nl = sclamp(P.lam[2] + dl, -lim, lim);
-            dl = nl - P.lam[2];
-            P.lam[2] = nl;
-            fi.x = dl;
-            vb = vb + fi * imb;
-            wb = wb + symmul(Iinv, cross(P.r, fi));
-        }
-        // (M) velocity-level PD motors
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            const T hi = i < 7 ? m_hi_arm : m_hi_fin;
-            T dl = (m_vt[i] - XARM_DQ(i)) * m_invd[i];
-            const T nl = sclamp(m_lam[i] + dl, -hi, hi);
-            dl = nl - m_lam[i];
-            m_lam[i] = nl;
-            XARM_DQ_AXPY(i, dl);
-        }
-        // (L) joint limits: arm (one side at most), then fingers (lower, upper)
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            if (!la_row[i]) continue;   // wave-uniform, decided once per substep
-            const T sg = la_sg[i];
-            T dl = (la_vt[i] - sg * XARM_DQ(i)) * (sg != (T)0 ? m_invd[i] : (T)0);
-            T nl = la_lam[i] + dl;
-            nl = smax0(nl);
-            dl = (nl - la_lam[i]) * sg;
-            la_lam[i] = nl;
-            XARM_DQ_AXPY(i, dl);
-        }
-#pragma unroll
-        for (int k = 0; k < 2; k++)
-#pragma unroll
-            for (int side = 0; side < 2; side++) {
-                const T sg = side == 0 ? (T)1 : (T)-1;
-                T dl = (lf_vt[k][side] - sg * XARM_DQ(7 + k)) * m_invd[7 + k];
-                T nl = lf_lam[k][side] + dl;
-                nl = smax0(nl);
-                dl = (nl - lf_lam[k][side]) * sg;
-                lf_lam[k][side] = nl;
-                XARM_DQ_AXPY(7 + k, dl);
-            }
-        // (G) gear row, q7' - q8' = 0
-        {
-            T dl = (g_vt - (XARM_DQ(7) - dq8)) * g_invd;
-            const T nl = sclamp(g_lam + dl, -g_hi, g_hi);
-            dl = nl - g_lam;
-            g_lam = nl;
-            XARM_DQ_AXPY(7, dl);
-            XARM_DQ_AXPY(8, -dl);
-        }
-        // (F) pad points, each solved as a 3x3 block in operational space; with two arms the pads of arm 0 are
-        // swept first, the object velocity is handed to the other lane, then the pads of arm 1
-#pragma unroll
-        for (int ph = 0; ph < Scene::NARMS; ph++) {
-        // two arms: sequential (phase = arm) when both touch the object; otherwise the touching arm sweeps in phase 0
-        const bool mine = Scene::NARMS == 1 || (seq ? arm == ph : ph == 0);
-        if (!FAST && XARM_ANY(pad_any && mine)) {   // NOT a rare path at wave level: ~2 % of the envs hold a finger contact, i.e. 1 - 0.98^64 = 73 % of the wavefronts (a __builtin_expect(.., 0) here took k_step from 2.02 to 3.15 ms)
-            T y[6], yf[2], wtot[8];
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-                T s = (T)0;
-#pragma unroll
-                for (int i = 0; i < 7; i++) s += lds[LDS_S + i * 6 + k] * XARM_DQ(i);
-                y[k] = s;
-            }
-            yf[0] = XARM_DQ(7); yf[1] = dq8;
-#pragma unroll
-            for (int k = 0; k < 8; k++) wtot[k] = (T)0;
-#pragma unroll
-            for (int fk = 0; fk < 2; fk++) {
-                PadPoint<T> &P1 = pp[2 * fk], &P2 = pp[2 * fk + 1];
-                if (!XARM_ANY((P1.invd[0] != (T)0 || P2.invd[0] != (T)0) && mine)) continue;
-                const V3<T> af = hc1 * (fk == 0 ? (T)1 : (T)-1);
-                const V3<T> yw = mk<T>(y[0], y[1], y[2]);
-                const V3<T> base = mk<T>(y[3], y[4], y[5]) + af * yf[fk] - vb;
-                V3<T> fsum = mk<T>(0, 0, 0), msum = mk<T>(0, 0, 0), bsum = mk<T>(0, 0, 0); // sum f, sum p x f, sum r x f
-                V3<T> f1 = mk<T>(0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    PadPoint<T> &P = j == 0 ? P1 : P2;
-                    const T e0 = mine ? P.invd[0] : (T)0, e1 = mine ? P.invd[1] : (T)0, e2 = mine ? P.invd[2] : (T)0;
-                    const V3<T> r = P.p - cb;
-                    const V3<T> t2 = cross(P.n, P.t1);
-                    V3<T> u = base + cross(yw, P.p) - cross(wb, r);
-                    if (j == 1) // effect of the impulse just applied at this finger's first point
-                        u = u + mk<T>(K21[fk][0] * f1.x + K21[fk][1] * f1.y + K21[fk][2] * f1.z,
-                                      K21[fk][3] * f1.x + K21[fk][4] * f1.y + K21[fk][5] * f1.z,
-                                      K21[fk][6] * f1.x + K21[fk][7] * f1.y + K21[fk][8] * f1.z);
-                    T dl = (P.vt - pad_cfm * P.lam[0] - dot(P.n, u)) * e0;
-                    T nl = P.lam[0] + dl;
-                    nl = smax0(nl);
-                    dl = nl - P.lam[0];
-                    P.lam[0] = nl;
-                    V3<T> fi = P.n * dl;
-                    u = u + P.Kn * dl;
-                    const T lim = mu_p * P.lam[0];
-                    dl = -dot(P.t1, u) * e1;
-                    nl = sclamp(P.lam[1] + dl, -lim, lim);
-                    dl = nl - P.lam[1];
-                    P.lam[1] = nl;
-                    fi = fi + P.t1 * dl;
-                    u = u + P.Kt1 * dl;
-                    dl = -dot(t2, u) * e2;
-                    nl = sclamp(P.lam[2] + dl, -lim, lim);
-                    dl = nl - P.lam[2];
-                    P.lam[2] = nl;
-                    fi = fi + t2 * dl;
-                    if (j == 0) f1 = fi;
-                    fsum = fsum + fi;
-                    msum = msum + cross(P.p, fi);
-                    bsum = bsum + cross(r, fi);
-                }
-                // ONE operational-space update for the finger: +fsum on finger fk (moment msum about the world
-                // origin), -fsum on the object (moment bsum about its centre)
-                const T W[6] = {msum.x, msum.y, msum.z, fsum.x, fsum.y, fsum.z};
-                const T wf = dot(af, fsum);
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-                    T s = lds[LDS_T + (7 + fk) * 6 + a] * wf;
-#pragma unroll
-                    for (int b = 0; b < 6; b++) s += lds[LDS_AHH + symi(a, b)] * W[b];
-                    y[a] += s;
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 2; k2++) {
-                    T s = Minv[symi(7 + k2, 7 + fk)] * wf;
-#pragma unroll
-                    for (int b = 0; b < 6; b++) s += lds[LDS_T + (7 + k2) * 6 + b] * W[b];
-                    yf[k2] += s;
-                }
-#pragma unroll
-                for (int b = 0; b < 6; b++) wtot[b] += W[b];
-                wtot[6 + fk] += wf;
-                vb = vb - fsum * imb;
-                wb = wb - symmul(Iinv, bsum);
-            }
-            XARM_DQ_AXPY(7, wtot[6]);
-            XARM_DQ_AXPY(8, wtot[7]);
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-#pragma unroll
-                for (int r2 = 0; r2 < 4; r2++)
-                    dqp[r2] = pkfma(mkpk<T>(lds[LDS_T + (2 * r2) * 6 + k], lds[LDS_T + (2 * r2 + 1) * 6 + k]), wtot[k], dqp[r2]);
-                dq8 += lds[LDS_T + 8 * 6 + k] * wtot[k];
-            }
-        }
-        if (Scene::NARMS == 2 && !FAST) {
-            if (ph == 0) {
-                const V3<T> f0 = mk<T>(xchg.from0(vb.x), xchg.from0(vb.y), xchg.from0(vb.z)), g0 = mk<T>(xchg.from0(wb.x), xchg.from0(wb.y), xchg.from0(wb.z));
-                const V3<T> pv = mk<T>(xchg.partner(vb.x), xchg.partner(vb.y), xchg.partner(vb.z)), pw = mk<T>(xchg.partner(wb.x), xchg.partner(wb.y), xchg.partner(wb.z));
-                // concurrent form: the object is taken from the lane whose pads touched it
-                vb = selv(seq, f0, selv(other_any, pv, vb));
-                wb = selv(seq, g0, selv(other_any, pw, wb));
-            } else {
-                const V3<T> f1 = mk<T>(xchg.from1(vb.x), xchg.from1(vb.y), xchg.from1(vb.z)), g1 = mk<T>(xchg.from1(wb.x), xchg.from1(wb.y), xchg.from1(wb.z));
-                vb = selv(seq, f1, vb);
-                wb = selv(seq, g1, wb);
-            }
-        }
-        }
+    for (int s = 0; s < (SWEEP_TWO ? NTS : 1); s++) { t_lam1[s][0] = tp[s].lam[0]; t_lam1[s][1] = tp[s].lam[1]; t_lam1[s][2] = tp[s].lam[2]; }
+    // (the table slots stay scalar: a packed form of them - x and y of u, of vb += imb f and of wb += Iinv (r x f) as register
+    // pairs - took the limit-free sweep from 327 to 303 instructions and did not keep the bits on the device)
+    // One sweep: reads the impulses of set RD, writes those of set WR (RD == WR: the one-set form).  LA: the sweep has arm-limit
+    // rows - `la_wave` is fixed for the substep, so the loop is chosen once, and the loop of a wavefront with no arm joint
+    // inside a limit window (all but a handful: 0 of 604 185 substeps under random actions, tools/row_census.py) carries no
+    // test of la_row[] at all (7 s_andn2_b64 + s_cbranch pairs per sweep before).
+#define XK_SWEEP(RD, WR, LA) {                                                                                                  \
+        XARM_LDS_FENCE(); /* keep the S / T reads of this sweep as LDS reads inside the loop */                                  \
+        /* (T) object / table points: n = +z, t1 = -y, t2 = +x */                                                               \
+        _Pragma("unroll")                                                                                                       \
+        for (int s = 0; s < NTS; s++) {                                                                                         \
+            TablePoint<T> &P = tp[s];                                                                                           \
+            const T (&lr)[3] = (RD) == 0 ? P.lam : t_lam1[SWEEP_TWO ? s : 0];                                                   \
+            T (&lw)[3] = (WR) == 0 ? P.lam : t_lam1[SWEEP_TWO ? s : 0];                                                         \
+            /* no wave-level skip: the slot math is a no-op for inactive lanes (1/diag = 0) and, being independent of the */    \
+            /* motor rows that follow, fills their dependency stalls when both sit in one basic block */                        \
+            const T Kxy = lds[LDS_TBL + s * 8 + 0], Kxz = lds[LDS_TBL + s * 8 + 1], Kyy = lds[LDS_TBL + s * 8 + 2],             \
+                    Kyz = lds[LDS_TBL + s * 8 + 3], Kzz = lds[LDS_TBL + s * 8 + 4];                                             \
+            V3<T> u = vb + cross(wb, P.r);                                                                                      \
+            T dl = (P.vt - u.z) * lds[LDS_TBL + s * 8 + 5];                                                                     \
+            T nl = lr[0] + dl;                                                                                                  \
+            nl = smax0(nl);                                                                                                     \
+            dl = nl - lr[0];                                                                                                    \
+            lw[0] = nl;                                                                                                         \
+            V3<T> fi = mk<T>((T)0, (T)0, dl);                                                                                   \
+            u = u + mk<T>(Kxz, Kyz, Kzz) * dl;                                                                                  \
+            const T lim = mu_t * nl;   /* the friction limit comes from the fresh normal impulse */                             \
+            dl = u.y * lds[LDS_TBL + s * 8 + 6]; /* t1 = -y: jv = -u.y, target 0 */                                             \
+            nl = sclamp(lr[1] + dl, -lim, lim);                                                                                 \
+            dl = nl - lr[1];                                                                                                    \
+            lw[1] = nl;                                                                                                         \
+            fi.y = -dl;                                                                                                         \
+            u = u - mk<T>(Kxy, Kyy, Kyz) * dl;                                                                                  \
+            dl = -u.x * lds[LDS_TBL + s * 8 + 7]; /* t2 = +x */                                                                 \
+            nl = sclamp(lr[2] + dl, -lim, lim);                                                                                 \
+            dl = nl - lr[2];                                                                                                    \
+            lw[2] = nl;                                                                                                         \
+            fi.x = dl;                                                                                                          \
+            vb = vb + fi * imb;                                                                                                 \
+            wb = wb + symmul(Iinv, cross(P.r, fi));                                                                             \
+        }                                                                                                                       \
+        /* (M) velocity-level PD motors */                                                                                      \
+        _Pragma("unroll")                                                                                                       \
+        for (int i = 0; i < 9; i++) {                                                                                           \
+            const T hi = i < 7 ? m_hi_arm : m_hi_fin;                                                                           \
+            T dl = (m_vt[i] - XARM_DQ(i)) * m_invd[i];                                                                          \
+            const T nl = sclamp(m_lam[RD][i] + dl, -hi, hi);                                                                    \
+            dl = nl - m_lam[RD][i];                                                                                             \
+            m_lam[WR][i] = nl;                                                                                                  \
+            XARM_DQ_AXPY(i, dl);                                                                                                \
+        }                                                                                                                       \
+        /* (L) joint limits: arm (one side at most), then fingers (lower, upper) */                                             \
+        if (LA) {                                                                                                               \
+            _Pragma("unroll")                                                                                                   \
+            for (int i = 0; i < 7; i++) {                                                                                       \
+                if (!la_row[i]) continue;   /* wave-uniform, decided once per substep */                                        \
+                const T sg = la_sg[i];                                                                                          \
+                T dl = (la_vt[i] - sg * XARM_DQ(i)) * (sg != (T)0 ? m_invd[i] : (T)0);                                          \
+                T nl = la_lam[RD][i] + dl;                                                                                      \
+                nl = smax0(nl);                                                                                                 \
+                dl = (nl - la_lam[RD][i]) * sg;                                                                                 \
+                la_lam[WR][i] = nl;                                                                                             \
+                XARM_DQ_AXPY(i, dl);                                                                                            \
+            }                                                                                                                   \
+        }                                                                                                                       \
+        _Pragma("unroll")                                                                                                       \
+        for (int k = 0; k < 2; k++)                                                                                             \
+            _Pragma("unroll")                                                                                                   \
+            for (int side = 0; side < 2; side++) {                                                                              \
+                const T sg = side == 0 ? (T)1 : (T)-1;                                                                          \
+                T dl = (lf_vt[k][side] - sg * XARM_DQ(7 + k)) * m_invd[7 + k];                                                  \
+                T nl = lf_lam[RD][k][side] + dl;                                                                                \
+                nl = smax0(nl);                                                                                                 \
+                dl = (nl - lf_lam[RD][k][side]) * sg;                                                                           \
+                lf_lam[WR][k][side] = nl;                                                                                       \
+                XARM_DQ_AXPY(7 + k, dl);                                                                                        \
+            }                                                                                                                   \
+        /* (G) gear row, q7' - q8' = 0 */                                                                                       \
+        {                                                                                                                       \
+            T dl = (g_vt - (XARM_DQ(7) - dq8)) * g_invd;                                                                        \
+            const T nl = sclamp(g_lam[RD] + dl, -g_hi, g_hi);                                                                   \
+            dl = nl - g_lam[RD];                                                                                                \
+            g_lam[WR] = nl;                                                                                                     \
+            XARM_DQ_AXPY(7, dl);                                                                                                \
+            XARM_DQ_AXPY(8, -dl);                                                                                               \
+        }                                                                                                                       \
+        /* (F) pad points, each solved as a 3x3 block in operational space; with two arms the pads of arm 0 are */ \
+        /* swept first, the object velocity is handed to the other lane, then the pads of arm 1 */ \
+        _Pragma("unroll") \
+        for (int ph = 0; ph < Scene::NARMS; ph++) { \
+        /* two arms: sequential (phase = arm) when both touch the object; otherwise the touching arm sweeps in phase 0 */ \
+        const bool mine = Scene::NARMS == 1 || (seq ? arm == ph : ph == 0); \
+        if (!FAST && XARM_ANY(pad_any && mine)) {   /* NOT a rare path at wave level: ~2 % of the envs hold a finger contact, i.e. 1 - 0.98^64 = 73 % of the wavefronts (a __builtin_expect(.., 0) here took k_step from 2.02 to 3.15 ms) */ \
+            T y[6], yf[2], wtot[8]; \
+        _Pragma("unroll") \
+            for (int k = 0; k < 6; k++) { \
+                T s = (T)0; \
+        _Pragma("unroll") \
+                for (int i = 0; i < 7; i++) s += lds[LDS_S + i * 6 + k] * XARM_DQ(i); \
+                y[k] = s; \
+            } \
+            yf[0] = XARM_DQ(7); yf[1] = dq8; \
+        _Pragma("unroll") \
+            for (int k = 0; k < 8; k++) wtot[k] = (T)0; \
+        _Pragma("unroll") \
+            for (int fk = 0; fk < 2; fk++) { \
+                PadPoint<T> &P1 = pp[2 * fk], &P2 = pp[2 * fk + 1]; \
+                if (!XARM_ANY((P1.invd[0] != (T)0 || P2.invd[0] != (T)0) && mine)) continue; \
+                const V3<T> af = hc1 * (fk == 0 ? (T)1 : (T)-1); \
+                const V3<T> yw = mk<T>(y[0], y[1], y[2]); \
+                const V3<T> base = mk<T>(y[3], y[4], y[5]) + af * yf[fk] - vb; \
+                V3<T> fsum = mk<T>(0, 0, 0), msum = mk<T>(0, 0, 0), bsum = mk<T>(0, 0, 0); /* sum f, sum p x f, sum r x f */ \
+                V3<T> f1 = mk<T>(0, 0, 0); \
+        _Pragma("unroll") \
+                for (int j = 0; j < 2; j++) { \
+                    PadPoint<T> &P = j == 0 ? P1 : P2; \
+                    const T e0 = mine ? P.invd[0] : (T)0, e1 = mine ? P.invd[1] : (T)0, e2 = mine ? P.invd[2] : (T)0; \
+                    const V3<T> r = P.p - cb; \
+                    const V3<T> t2 = cross(P.n, P.t1); \
+                    V3<T> u = base + cross(yw, P.p) - cross(wb, r); \
+                    if (j == 1) /* effect of the impulse just applied at this finger's first point */ \
+                        u = u + mk<T>(K21[fk][0] * f1.x + K21[fk][1] * f1.y + K21[fk][2] * f1.z, \
+                                      K21[fk][3] * f1.x + K21[fk][4] * f1.y + K21[fk][5] * f1.z, \
+                                      K21[fk][6] * f1.x + K21[fk][7] * f1.y + K21[fk][8] * f1.z); \
+                    T dl = (P.vt - pad_cfm * P.lam[0] - dot(P.n, u)) * e0; \
+                    T nl = P.lam[0] + dl; \
+                    nl = smax0(nl); \
+                    dl = nl - P.lam[0]; \
+                    P.lam[0] = nl; \
+                    V3<T> fi = P.n * dl; \
+                    u = u + P.Kn * dl; \
+                    const T lim = mu_p * P.lam[0]; \
+                    dl = -dot(P.t1, u) * e1; \
+                    nl = sclamp(P.lam[1] + dl, -lim, lim); \
+                    dl = nl - P.lam[1]; \
+                    P.lam[1] = nl; \
+                    fi = fi + P.t1 * dl; \
+                    u = u + P.Kt1 * dl; \
+                    dl = -dot(t2, u) * e2; \
+                    nl = sclamp(P.lam[2] + dl, -lim, lim); \
+                    dl = nl - P.lam[2]; \
+                    P.lam[2] = nl; \
+                    fi = fi + t2 * dl; \
+                    if (j == 0) f1 = fi; \
+                    fsum = fsum + fi; \
+                    msum = msum + cross(P.p, fi); \
+                    bsum = bsum + cross(r, fi); \
+                } \
+                /* ONE operational-space update for the finger: +fsum on finger fk (moment msum about the world */ \
+                /* origin), -fsum on the object (moment bsum about its centre) */ \
+                const T W[6] = {msum.x, msum.y, msum.z, fsum.x, fsum.y, fsum.z}; \
+                const T wf = dot(af, fsum); \
+        _Pragma("unroll") \
+                for (int a = 0; a < 6; a++) { \
+                    T s = lds[LDS_T + (7 + fk) * 6 + a] * wf; \
+        _Pragma("unroll") \
+                    for (int b = 0; b < 6; b++) s += lds[LDS_AHH + symi(a, b)] * W[b]; \
+                    y[a] += s; \
+                } \
+        _Pragma("unroll") \
+                for (int k2 = 0; k2 < 2; k2++) { \
+                    T s = Minv[symi(7 + k2, 7 + fk)] * wf; \
+        _Pragma("unroll") \
+                    for (int b = 0; b < 6; b++) s += lds[LDS_T + (7 + k2) * 6 + b] * W[b]; \
+                    yf[k2] += s; \
+                } \
+        _Pragma("unroll") \
+                for (int b = 0; b < 6; b++) wtot[b] += W[b]; \
+                wtot[6 + fk] += wf; \
+                vb = vb - fsum * imb; \
+                wb = wb - symmul(Iinv, bsum); \
+            } \
+            XARM_DQ_AXPY(7, wtot[6]); \
+            XARM_DQ_AXPY(8, wtot[7]); \
+        _Pragma("unroll") \
+            for (int k = 0; k < 6; k++) { \
+        _Pragma("unroll") \
+                for (int r2 = 0; r2 < 4; r2++) \
+                    dqp[r2] = pkfma(mkpk<T>(lds[LDS_T + (2 * r2) * 6 + k], lds[LDS_T + (2 * r2 + 1) * 6 + k]), wtot[k], dqp[r2]); \
+                dq8 += lds[LDS_T + 8 * 6 + k] * wtot[k]; \
+            } \
+        } \
+        if (Scene::NARMS == 2 && !FAST) { \
+            if (ph == 0) { \
+                const V3<T> f0 = mk<T>(xchg.from0(vb.x), xchg.from0(vb.y), xchg.from0(vb.z)), g0 = mk<T>(xchg.from0(wb.x), xchg.from0(wb.y), xchg.from0(wb.z)); \
+                const V3<T> pv = mk<T>(xchg.partner(vb.x), xchg.partner(vb.y), xchg.partner(vb.z)), pw = mk<T>(xchg.partner(wb.x), xchg.partner(wb.y), xchg.partner(wb.z)); \
+                /* concurrent form: the object is taken from the lane whose pads touched it */ \
+                vb = selv(seq, f0, selv(other_any, pv, vb)); \
+                wb = selv(seq, g0, selv(other_any, pw, wb)); \
+            } else { \
+                const V3<T> f1 = mk<T>(xchg.from1(vb.x), xchg.from1(vb.y), xchg.from1(vb.z)), g1 = mk<T>(xchg.from1(wb.x), xchg.from1(wb.y), xchg.from1(wb.z)); \
+                vb = selv(seq, f1, vb); \
+                wb = selv(seq, g1, wb); \
+            } \
+        } \
+        } \
     }
+    constexpr int NSW = XK_SWEEP_ITERS;
+    constexpr int LAST = SWEEP_TWO ? (NSW & 1) : 0;   // the set the last sweep wrote
+    if constexpr (!SWEEP_TWO) {
+#pragma unroll 1
+        for (int it = 0; it < NSW; it++) XK_SWEEP(0, 0, true)
+    } else {
+#define XK_LOOP(LA)                                                                                          \
+        _Pragma("unroll 1") for (int it = 0; it + 1 < NSW; it += 2) {                                        \
+            XK_SWEEP(0, LSETS - 1, LA)                                                                       \
+            XK_SWEEP(LSETS - 1, 0, LA)                                                                       \
+        }                                                                                                    \
+        if (NSW & 1) XK_SWEEP(0, LSETS - 1, LA)     /* an odd sweep count (the timing variants) */
+        if (la_wave) { XK_LOOP(true) }
+        else { XK_LOOP(false) }
+#undef XK_LOOP
+    }
+#undef XK_SWEEP
 
 #pragma unroll
     for (int k = 0; k < 4; k++) { dq[2 * k] = pklo(dqp[k]); dq[2 * k + 1] = pkhi(dqp[k]); }
@@ -1167,7 +1220,7 @@ XARM_HD bool substep(EnvState<T> &st, const T (&qt)[9], const T dt, Lds lds, con
     for (int i = 0; i < 8; i++) {
         T l = (T)0;
 #pragma unroll
-        for (int s = 0; s < NTS; s++) l = tp[s].id == i ? tp[s].lam[0] : l;
+        for (int s = 0; s < NTS; s++) l = tp[s].id == i ? (LAST == 0 ? tp[s].lam[0] : t_lam1[SWEEP_TWO ? s : 0][0]) : l;
         st.lam_t[i] = l;
         st.lam_p[i] = (!FAST && i < NP) ? pp[i < NP ? i : 0].lam[0] : (T)0;
     }
