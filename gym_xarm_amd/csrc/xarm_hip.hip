@@ -43,6 +43,7 @@
 #include "xarm_ppow_core.h"
 #include "xarm_a2cw_core.h"
 #include "xarm_rollout_core.h"
+#include "xarm_replay_core.h"
 
 using namespace xd;
 
@@ -919,6 +920,50 @@ int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int6
     a.fail_count = fail_count_i64;
     const int le = xher::launch_her_sample(a, clock, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_her_sample: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------- uniform replay (xarm_k_replay.hip)
+int xarm_replay_record_floats(const xarm_replay_layout *layout) {
+    if (const char *why = xrep::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_replay_record_floats: %s", why);
+    return xrep::make_layout(*layout).R;
+}
+
+int xarm_replay_add(const xarm_replay_layout *layout, float *ring, int64_t *clock, const float *obs, const float *ag, const float *dg,
+                    const float *next_obs, const float *next_ag, const float *act, const float *rew, const uint8_t *done_u8,
+                    const uint8_t *timeout_u8, void *stream) {
+    if (const char *why = xrep::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_replay_add: %s", why);
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!ring || !clock || !obs || !next_obs || !act || !rew || !done_u8 || (layout->goal_dim > 0 && (!ag || !dg || !next_ag)))
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_replay_add: NULL pointer");
+    xrep::AddArgs a;
+    a.L = xrep::make_layout(*layout);
+    a.ring = ring; a.clock = clock; a.obs = obs; a.ag = ag; a.dg = dg; a.next_obs = next_obs; a.next_ag = next_ag; a.act = act; a.rew = rew;
+    a.done = done_u8; a.timeout = timeout_u8;
+    const int le = xrep::launch_replay_add(a, clock, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_replay_add: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_replay_sample(const xarm_replay_layout *layout, const float *ring, int64_t *clock, uint64_t seed, int32_t batch,
+                       int32_t handle_timeout, const double *stats, double clip_obs, double eps, float *out_obs, float *out_next_obs,
+                       float *out_act, float *out_rew, float *out_done, float *out_use, int64_t *out_env_i64, int64_t *out_time_i64,
+                       void *stream) {
+    if (const char *why = xrep::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_replay_sample: %s", why);
+    if (batch < 0) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_replay_sample: batch must be >= 0");
+    if (stats && !(clip_obs > 0.0)) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_replay_sample: clip_obs must be > 0");
+    if (stats && (!(eps > 0.0) || !isfinite(eps))) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_replay_sample: eps must be finite and > 0");
+    if (batch == 0 || layout->num_envs == 0) return XARM_OK;
+    if (!ring || !clock || !out_obs || !out_next_obs || !out_act || !out_rew || !out_done || !out_use)
+        return fail(nullptr, XARM_E_INVALID, "%s", "xarm_replay_sample: NULL pointer");
+    xrep::SampleArgs a;
+    a.L = xrep::make_layout(*layout);
+    a.ring = ring; a.clock = clock; a.seed = seed; a.batch = batch; a.handle_timeout = handle_timeout != 0;
+    a.stats = stats; a.clip_obs = clip_obs; a.eps = eps;
+    a.obs = out_obs; a.next_obs = out_next_obs; a.act = out_act; a.rew = out_rew; a.done = out_done; a.use = out_use;
+    a.env = out_env_i64; a.time = out_time_i64;
+    const int le = xrep::launch_replay_sample(a, clock, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_replay_sample: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -16,6 +16,7 @@ import torch
 
 from . import _native
 from .device_ppo import export_adam, load_adam
+from .replay import DeviceReplayBuffer
 
 
 def tower_params(seq):
@@ -210,7 +211,10 @@ class DeviceSAC:
         """sample `buffer` (a DeviceHerReplayBuffer) and step: `buffer.sample_into` with its relabelled rewards, the two observation
         triples concatenated and normalised by `normalize` (a DeviceVecNormalize: one xarm_norm_obs launch each with update = 0; None:
         concatenated as they are), `ok` as use, then `update`.  sample: `buffer.alloc_out(batch_size)` tensors to reuse (allocated at
-        the first call otherwise).  After the first call no allocation and no host read; capturable."""
+        the first call otherwise).  After the first call no allocation and no host read; capturable.
+        A DeviceReplayBuffer (gym_xarm_amd/replay.py) takes the short way: `_update_from_uniform`."""
+        if isinstance(buffer, DeviceReplayBuffer):
+            return self._update_from_uniform(buffer, normalize, sample)
         if sample is None:
             if getattr(self, "_sample", None) is None:
                 self._sample = buffer.alloc_out(self.batch_size)
@@ -228,6 +232,23 @@ class DeviceSAC:
         b["done"].copy_(s["done"])
         b["use"].copy_(s["ok"])
         return self.update({"obs": b["obs"], "next_obs": b["next_obs"], "action": s["action"], "reward": s["reward"], "done": b["done"], "use": b["use"]})
+
+    def _update_from_uniform(self, buffer, normalize=None, sample=None):
+        """update_from on a DeviceReplayBuffer: its sample kernel writes the batch where `update` reads it - `buffers`' obs, next_obs (normalised
+        in the kernel by `normalize`'s statistics), done and use, and the action / reward tensors of `sample` (buffer.alloc_out's; two tensors
+        of this updater's, allocated at the first call, otherwise) - and `update` runs behind it: no torch op in between."""
+        if buffer.dim != self.obs_width or buffer.act_dim != self.act_dim:
+            raise ValueError("%s: the buffer's rows (observation %d, action %d) do not belong to this model (%d, %d)"
+                             % (type(self).__name__, buffer.dim, buffer.act_dim, self.obs_width, self.act_dim))
+        if sample is None:
+            if getattr(self, "_uniform_sample", None) is None:
+                self._uniform_sample = {"action": torch.empty(self.batch_size, self.act_dim, device=self.device),
+                                        "reward": torch.empty(self.batch_size, device=self.device)}
+            sample = self._uniform_sample
+        b = self.buffers
+        batch = {"obs": b["obs"], "next_obs": b["next_obs"], "action": sample["action"], "reward": sample["reward"], "done": b["done"], "use": b["use"]}
+        buffer.sample_into(batch, normalize)
+        return self.update(batch)
 
     def act_into(self, out, obs, deterministic=False):
         """One launch (n_hidden + 2 on the wide backend; plus the counter tick of a stochastic call): out["action"] [E, A] = tanh(mean + exp(log_std) z) (tanh(mean) when

@@ -22,6 +22,8 @@ import time
 import torch
 import torch.nn as nn
 
+from .replay import UNIFORM_BUFFERS
+
 LOG_STD_MIN, LOG_STD_MAX, SQUASH_EPS = -20.0, 2.0, 1e-6
 
 
@@ -152,14 +154,26 @@ def normalized_batch(venv, s):
     return b
 
 
+def flat_batch(venv, s):
+    """the learner's batch of a uniform-replay sample `s` (replay.ReplayBuffer.sample): both observation rows normalised with the running
+    statistics as they are now, raw rewards, done with the time-limit truncations already taken out - normalized_batch's counterpart"""
+    return {"obs": _frozen_norm(venv, s["obs"]), "next_obs": _frozen_norm(venv, s["next_obs"]), "action": s["action"], "reward": s["reward"],
+            "done": s["done"].float(), "use": s["use"].float()}
+
+
 def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None,
                      gamma=0.95, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None, log_dir=None, device_normalize=False, config=None,
-                     log_every=50, quiet=False, check_freq=1000, horizon=None):
-    """The driver loop that `train_sac` and `td3.train_td3` share: an off-policy learner + HER on a batched goal env.  It builds the env, the
-    normaliser, the Monitor, the callback and the HER buffer, then calls `build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)`
+                     log_every=50, quiet=False, check_freq=1000, horizon=None, replay=None, buffer_size=None):
+    """The driver loop that `train_sac` and `td3.train_td3` share: an off-policy learner on a batched env, with HER on a goal env
+    (replay="her") or SB3's plain uniform buffer (replay="uniform": gym_xarm_amd/replay.py; the flat-observation env, or a goal env
+    without relabelling; buffer_size: its transitions, default 1 000 000).  replay=None: "uniform" on a flat-observation env, else "her".
+    The uniform buffer is told which finished envs ran into the time limit (info["TimeLimit.truncated"]) and samples those transitions
+    with done = 0; the HER buffer stores them as terminations.  The driver builds the env, the normaliser, the Monitor, the callback
+    and the buffer, then calls `build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)`
     -> (model, act, learn): `act(nobs, it)` is the rollout action [E, A] of step `it`, `learn()` samples the buffer and runs one gradient step,
     returning its stats (a tensor in the order of `stats`, or a dict of 0-d tensors keyed by it).  Returns (model, venv, hist)."""
     from .her import DeviceHerReplayBuffer, HerReplayBuffer
+    from .replay import DeviceReplayBuffer, ReplayBuffer
     from .train import EpisodeMonitor, SaveOnBestTrainingRewardCallback, VecNormalize
     torch.manual_seed(seed)
     if env is None:
@@ -167,6 +181,13 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
         env = gym_xarm_amd.make(env_id, num_envs=num_envs, seed=seed, config=config, auto_reset=True)
     assert not getattr(env, "_lazy", False), "the off-policy driver stores terminal observations: it needs the in-call auto-reset (auto_reset=True)"
     num_envs, dev = env.num_envs, torch.device(env.device)
+    flat = bool(getattr(env, "flat_observation", False))
+    replay = ("uniform" if flat else "her") if replay is None else replay
+    if replay not in ("her", "uniform"):
+        raise ValueError("replay must be 'her' or 'uniform', not %r" % (replay,))
+    if replay == "her" and flat:
+        raise ValueError("replay='her' needs a goal env: a flat-observation env has no achieved or desired goal to relabel (use replay='uniform')")
+    uniform = replay == "uniform"
     act_dim = int(getattr(env, "action_dim", getattr(env, "act_dim", 0)))
     max_len = int(getattr(env, "max_episode_steps", 50))
     learning_starts = 2 * max_len if learning_starts is None else int(learning_starts)
@@ -179,24 +200,33 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
         venv = VecNormalize(env, gamma=gamma)
         monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
-    Buffer = DeviceHerReplayBuffer if dev.type == "cuda" else HerReplayBuffer
-    buffer = Buffer(env, horizon=horizon, n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=seed)
+    if uniform:
+        Buffer = DeviceReplayBuffer if dev.type == "cuda" else ReplayBuffer
+        buffer = Buffer(env, buffer_size=1_000_000 if buffer_size is None else int(buffer_size), seed=seed)
+    else:
+        Buffer = DeviceHerReplayBuffer if dev.type == "cuda" else HerReplayBuffer
+        buffer = Buffer(env, horizon=horizon, n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=seed)
     model, act, learn = build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)
     obs = env.reset()
     nobs = venv.reset_from(obs) if device_normalize else venv._norm(venv._flat(obs))
     hist, t0, last, updates, window = [], time.perf_counter(), None, 0, 0
     succ_sum, done_sum, raw_sum = torch.zeros((), device=dev), torch.zeros((), device=dev), torch.zeros((), device=dev)
     for it in range(1, steps + 1):
-        prev = {k: v.clone() for k, v in obs.items()}
+        prev = obs.clone() if flat else {k: v.clone() for k, v in obs.items()}
         a = act(nobs, it)
         obs, rew, done, info = env.step(a)
         term = info.get("terminal_observation")
-        if term is not None:
+        if term is None:
+            nxt = obs
+        elif flat:          # the terminal observation is the row itself
+            nxt = torch.where((done != 0)[:, None], term, obs)
+        else:
             d = (done != 0)[:, None]
             nxt = {"observation": torch.where(d, term, obs["observation"]), "achieved_goal": torch.where(d, env.achieved_goal_of(term), obs["achieved_goal"])}
+        if uniform:
+            buffer.add(prev, nxt, a, rew, done, info.get("TimeLimit.truncated"))
         else:
-            nxt = obs
-        buffer.add(prev, nxt, a, rew, done)
+            buffer.add(prev, nxt, a, rew, done)
         if device_normalize:
             nobs = venv.step_into(norm_out, obs, rew, done)["nobs"]
         else:
@@ -239,8 +269,10 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
 def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
               lr=1e-3, tau=0.005, ent_coef="auto", target_entropy=None, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None,
               log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None,
-              net_arch=None, activation=None):
-    """SAC + HER on a batched goal env.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
+              net_arch=None, activation=None, replay=None, buffer_size=None):
+    """SAC + HER on a batched goal env, or - replay="uniform", the default on a flat-observation env such as XarmPDHandoverNoGoal-v1 - SAC on
+    SB3's plain ReplayBuffer of `buffer_size` transitions (default 1 000 000), which bootstraps through time-limit truncations; "uniform" on
+    a goal env is the dense-reward / no-relabel setting.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
     2 x max_episode_steps, so that closed episodes exist) every `train_freq`-th step runs `gradient_steps` SAC steps on `batch_size`
     relabelled rows.  Observations are normalised at sample time with the running statistics; rewards stay raw.
     device_update: the rollout action and the SAC step in HIP kernels (DeviceSAC).  device_normalize: DeviceVecNormalize (statistics,
@@ -258,22 +290,25 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
             act_out = {"action": torch.empty(num_envs, act_dim, device=dev)}
             sample = buffer.alloc_out(batch_size)
             act = lambda nobs, it: dsac.act_into(act_out, nobs)["action"]
+            to_batch = flat_batch if isinstance(buffer, UNIFORM_BUFFERS) else normalized_batch
             if device_normalize:
                 learn = lambda: dsac.update_from(buffer, venv, sample)
             else:
-                learn = lambda: dsac.update(normalized_batch(venv, buffer.sample_into(sample)))
+                learn = lambda: dsac.update(to_batch(venv, buffer.sample_into(sample)))
         else:
             opts = make_optimizers(model, lr, ent_coef)
 
             def act(nobs, it):
                 with torch.no_grad():
                     return model.action_log_prob(nobs)[0]
-            learn = lambda: sac_step(model, opts, normalized_batch(venv, buffer.sample(batch_size)), gamma, tau, ent_coef, target_entropy)
+            to_batch = flat_batch if isinstance(buffer, UNIFORM_BUFFERS) else normalized_batch
+            learn = lambda: sac_step(model, opts, to_batch(venv, buffer.sample(batch_size)), gamma, tau, ent_coef, target_entropy)
         return model, act, learn
     return train_off_policy(build, STATS, env_id=env_id, num_envs=num_envs, steps=steps, batch_size=batch_size, gradient_steps=gradient_steps,
                             train_freq=train_freq, learning_starts=learning_starts, gamma=gamma, n_sampled_goal=n_sampled_goal,
                             goal_selection_strategy=goal_selection_strategy, seed=seed, env=env, log_dir=log_dir, device_normalize=device_normalize,
-                            config=config, log_every=log_every, quiet=quiet, check_freq=check_freq, horizon=horizon)
+                            config=config, log_every=log_every, quiet=quiet, check_freq=check_freq, horizon=horizon, replay=replay,
+                            buffer_size=buffer_size)
 
 
 def load_checkpoint(path):

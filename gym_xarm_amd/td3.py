@@ -111,8 +111,9 @@ def td3_step(model, opts, batch, n_updates, gamma=0.95, tau=0.005, policy_delay=
 def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
               lr=1e-3, tau=0.005, policy_delay=2, target_policy_noise=0.2, target_noise_clip=0.5, action_noise=0.1, n_sampled_goal=4,
               goal_selection_strategy="future", seed=0, env=None, log_dir=None, device_update=False, device_normalize=False, config=None,
-              log_every=50, quiet=False, check_freq=1000, horizon=None, net_arch=None, activation=None):
-    """TD3 + HER on a batched goal env: sac.train_sac's arguments without the entropy coefficient's, plus TD3's.  Exploration is SB3's
+              log_every=50, quiet=False, check_freq=1000, horizon=None, net_arch=None, activation=None, replay=None, buffer_size=None):
+    """TD3 + HER on a batched goal env, or TD3 on the uniform buffer (replay, buffer_size: as in sac.train_sac): sac.train_sac's arguments
+    without the entropy coefficient's, plus TD3's.  Exploration is SB3's
     `_sample_action`: uniform actions in [-1, 1] while the step count is <= learning_starts, after that
     clamp(actor(nobs) + action_noise z, -1, 1); the stored action is the clamped one.  device_update: the rollout action and the TD3 step in
     HIP kernels (DeviceTD3); device_normalize: DeviceVecNormalize, as in train_sac.  Returns (model, venv, hist)."""
@@ -126,13 +127,15 @@ def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
             act_out = torch.empty(num_envs, act_dim, device=dev)
             sample = buffer.alloc_out(batch_size)
             act = lambda nobs, it: dtd3.act_into(act_out, nobs, "uniform" if it <= learning_starts else "gaussian")
+            to_batch = sac.flat_batch if isinstance(buffer, sac.UNIFORM_BUFFERS) else normalized_batch
             if device_normalize:
                 learn = lambda: dtd3.update_from(buffer, venv, sample)
             else:
-                learn = lambda: dtd3.update(normalized_batch(venv, buffer.sample_into(sample)))
+                learn = lambda: dtd3.update(to_batch(venv, buffer.sample_into(sample)))
         else:
             opts = make_optimizers(model, lr)
             state = {"n": 0, "last": None}
+            to_batch = sac.flat_batch if isinstance(buffer, sac.UNIFORM_BUFFERS) else normalized_batch
 
             def act(nobs, it):
                 with torch.no_grad():
@@ -143,7 +146,7 @@ def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
 
             def learn():
                 state["n"] += 1
-                state["last"] = td3_step(model, opts, normalized_batch(venv, buffer.sample(batch_size)), state["n"], gamma, tau, policy_delay,
+                state["last"] = td3_step(model, opts, to_batch(venv, buffer.sample(batch_size)), state["n"], gamma, tau, policy_delay,
                                          target_policy_noise, target_noise_clip, last=state["last"])
                 return state["last"]
         return model, act, learn
@@ -151,7 +154,7 @@ def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
                                 train_freq=train_freq, learning_starts=learning_starts, gamma=gamma, n_sampled_goal=n_sampled_goal,
                                 goal_selection_strategy=goal_selection_strategy, seed=seed, env=env, log_dir=log_dir,
                                 device_normalize=device_normalize, config=config, log_every=log_every, quiet=quiet, check_freq=check_freq,
-                                horizon=horizon)
+                                horizon=horizon, replay=replay, buffer_size=buffer_size)
 
 
 def load_checkpoint(path):

@@ -656,7 +656,12 @@ def main(argv=None):
     ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant", help="a2c / ppo: linear runs lr down to 0 over --updates")
     ap.add_argument("--clip-range-schedule", choices=("constant", "linear"), default="constant", help="ppo: linear runs clip_range (0.2) down to 0")
     ap.add_argument("--shuffle", choices=("torch", "device"), default=None, help="ppo with --device-update: the minibatch shuffle (default torch; device: a HIP launch inside the update call)")
+    ap.add_argument("--replay", choices=("her", "uniform"), default=None, help="sac / td3: the HER buffer, or stable-baselines3's plain ReplayBuffer "
+                    "(gym_xarm_amd/replay.py; default: uniform on a flat-observation env, her otherwise)")
+    ap.add_argument("--buffer-size", type=int, default=None, help="sac / td3 with the uniform buffer: transitions kept (1000000)")
     args = ap.parse_args(argv)
+    if args.algo not in ("sac", "td3") and (args.replay is not None or args.buffer_size is not None):
+        ap.error("--replay and --buffer-size are for --algo sac / td3")
     if args.algo != "ppo" and (args.target_kl is not None or args.clip_range_vf is not None or args.clip_range_schedule != "constant"):
         ap.error("--target-kl, --clip-range-vf and --clip-range-schedule are for --algo ppo")
     if args.algo in ("sac", "td3") and args.lr_schedule != "constant":
@@ -677,7 +682,8 @@ def main(argv=None):
         model, venv, hist = sac.train_sac(args.env, num_envs=args.num_envs, steps=args.updates, batch_size=args.batch_size or 256,
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
                                           device_update=args.device_update, device_normalize=args.device_normalize,
-                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation)
+                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation,
+                                          replay=args.replay, buffer_size=args.buffer_size)
         if args.save:
             save_model(args.save, model, venv)
         return
@@ -688,7 +694,8 @@ def main(argv=None):
         model, venv, hist = td3.train_td3(args.env, num_envs=args.num_envs, steps=args.updates, batch_size=args.batch_size or 256,
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
                                           device_update=args.device_update, device_normalize=args.device_normalize,
-                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation, **extra)
+                                          net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation,
+                                          replay=args.replay, buffer_size=args.buffer_size, **extra)
         if args.save:
             save_model(args.save, model, venv)
         return

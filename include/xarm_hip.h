@@ -343,6 +343,48 @@ int xarm_her_sample(const xarm_her_layout *layout, const float *ring, const int6
                     float *out_next_ag, float *out_goal, float *out_act, float *out_rew, uint8_t *out_done_u8, int64_t *out_env_i64,
                     int64_t *out_time_i64, int64_t *out_goal_time_i64, uint8_t *out_ok_u8, int64_t *fail_count_i64, void *stream);
 
+/* ---- device-resident uniform replay (gym_xarm_amd/csrc/xarm_replay_core.h, xarm_k_replay.hip): SB3's plain
+ * `ReplayBuffer` - every stored transition is sampled with the same probability, nothing is relabelled, running episodes
+ * included - for the off-policy learners on a flat-observation env or on a goal env with a dense reward.  Like the HER calls
+ * these need no env handle: the buffer is caller-owned DEVICE memory described by an xarm_replay_layout, the launches go to
+ * `stream` on the caller's current device, and the messages of XARM_E_INVALID go to xarm_last_error(NULL).
+ *   ring      float32 [horizon, num_envs, R], one record per (slot, env): obs | next_obs | action | reward | done | timeout,
+ *             R = 2 D + act_dim + 3 floats.  D = obs_dim + 2 goal_dim is the learner's flat observation: the row
+ *             observation | achieved_goal | desired_goal (goal_dim 0: the observation alone), and next_obs is
+ *             next_observation | next_achieved_goal | desired_goal
+ *   clock     int64 [2] = {t, sample_calls}, zero before the first add, advanced on the device as the HER clock is
+ * Neither call allocates, synchronises, uses atomics or reads device memory from the host; each is two kernel launches. */
+typedef struct xarm_replay_layout {
+    int32_t num_envs;
+    int32_t horizon;        /* ring slots per env, >= 1 */
+    int32_t obs_dim;
+    int32_t goal_dim;       /* 0: a flat-observation env, achieved / desired goal are not read */
+    int32_t act_dim;
+} xarm_replay_layout;       /* 20 bytes */
+/* R, the floats of one record; XARM_E_INVALID for a NULL or unusable layout (obs_dim or act_dim < 1, goal_dim < 0, horizon < 1,
+ * num_envs < 0) */
+int xarm_replay_record_floats(const xarm_replay_layout *layout);
+/* store one transition per env at slot t mod horizon ([num_envs, dim] float32 rows, rew float32 [num_envs], done uint8
+ * [num_envs]; for a finished env next_obs / next_ag are the TERMINAL ones).  timeout_u8 (may be NULL = none) marks the envs whose
+ * done is a time-limit truncation.  O(num_envs); num_envs == 0 launches nothing.  XARM_E_INVALID: unusable layout, or with
+ * num_envs > 0 a NULL pointer other than timeout_u8 (ag / dg / next_ag may be NULL when goal_dim == 0). */
+int xarm_replay_add(const xarm_replay_layout *layout, float *ring, int64_t *clock, const float *obs, const float *ag, const float *dg,
+                    const float *next_obs, const float *next_ag, const float *act, const float *rew, const uint8_t *done_u8,
+                    const uint8_t *timeout_u8 /* may be NULL */, void *stream);
+/* draw `batch` rows uniformly from the min(t, horizon) num_envs stored transitions: row b takes entry
+ * mulhi64(Philox(seed; b, sample_calls, 0, tag + sample_calls >> 32), min(t, horizon) num_envs) - one draw, no rejection.
+ * The row is written as the learners take it: out_obs / out_next_obs [batch, D] - with stats (the normaliser's double
+ * [2 D + 4], xarm_norm_obs's layout) column j is clamp((x - mean_j) / sqrt(var_j + eps), +-clip_obs) in float64, rounded to
+ * float32 once, what xarm_norm_obs writes; with stats NULL the columns are copied - out_act [batch, act_dim], out_rew [batch] the
+ * stored reward, out_done [batch] float32 = done && !(handle_timeout && timeout), out_use [batch] float32 = 1, or 0 with an
+ * all-zero row while the buffer is empty.  out_env_i64 / out_time_i64 (int64 [batch], may be NULL) name the entry.
+ * batch == 0 or num_envs == 0 launches nothing.  XARM_E_INVALID: unusable layout, batch < 0, with stats a clip_obs <= 0 or an
+ * eps that is not finite and > 0, or with batch > 0 a NULL pointer other than stats / out_env_i64 / out_time_i64. */
+int xarm_replay_sample(const xarm_replay_layout *layout, const float *ring, int64_t *clock, uint64_t seed, int32_t batch,
+                       int32_t handle_timeout, const double *stats /* may be NULL */, double clip_obs, double eps, float *out_obs,
+                       float *out_next_obs, float *out_act, float *out_rew, float *out_done, float *out_use,
+                       int64_t *out_env_i64 /* may be NULL */, int64_t *out_time_i64 /* may be NULL */, void *stream);
+
 /* ---- device-resident VecNormalize + episode monitor (gym_xarm_amd/csrc/xarm_norm_core.h, xarm_k_norm.hip):
  * the running observation / return statistics, the normalised observation and reward and the Monitor's per-env return and length
  * of gym_xarm_amd/train.py (VecNormalize.step + EpisodeMonitor.update) in one stream-ordered call.  Like the HER calls these
