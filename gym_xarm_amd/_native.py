@@ -22,6 +22,7 @@ EXPORTS = ["xarm_create", "xarm_destroy", "xarm_dims", "xarm_reset", "xarm_step"
            "xarm_version", "xarm_default_camera", "xarm_render", "xarm_view_from_camera", "xarm_default_view", "xarm_render_views",
            "xarm_her_record_floats", "xarm_her_add", "xarm_her_sample",
            "xarm_replay_record_floats", "xarm_replay_add", "xarm_replay_sample",
+           "xarm_eval_begin", "xarm_eval_step", "xarm_eval_summary",
            "xarm_norm_work_bytes", "xarm_norm_obs", "xarm_norm_step",
            "xarm_policy_act", "xarm_a2c_workspace_bytes", "xarm_a2c_update", "xarm_ppo_workspace_bytes", "xarm_ppo_update", "xarm_ppo_update_opt",
            "xarm_sac_workspace_bytes", "xarm_sac_act", "xarm_sac_update",
@@ -74,6 +75,11 @@ class XarmReplayLayout(C.Structure):
     """include/xarm_hip.h xarm_replay_layout (20 bytes)"""
     _fields_ = [("num_envs", C.c_int32), ("horizon", C.c_int32), ("obs_dim", C.c_int32), ("goal_dim", C.c_int32),
                 ("act_dim", C.c_int32)]
+
+
+class XarmEvalLayout(C.Structure):
+    """include/xarm_hip.h xarm_eval_layout (8 bytes)"""
+    _fields_ = [("num_envs", C.c_int32), ("n_eval_episodes", C.c_int32)]
 
 
 class XarmNormLayout(C.Structure):
@@ -258,6 +264,10 @@ def load(path=None):
     L.xarm_replay_record_floats.argtypes = [rl]
     L.xarm_replay_add.argtypes = [rl] + [vp] * 12
     L.xarm_replay_sample.argtypes = [rl, vp, vp, C.c_uint64, C.c_int32, C.c_int32, vp, C.c_double, C.c_double] + [vp] * 9
+    el = C.POINTER(XarmEvalLayout)
+    L.xarm_eval_begin.argtypes = [el] + [vp] * 6
+    L.xarm_eval_step.argtypes = [el] + [vp] * 10
+    L.xarm_eval_summary.argtypes = [el] + [vp] * 4
     nl, npar = C.POINTER(XarmNormLayout), C.POINTER(XarmNormParams)
     L.xarm_norm_work_bytes.argtypes = [nl, C.POINTER(C.c_int64)]
     L.xarm_norm_obs.argtypes = [nl, npar] + [vp] * 6 + [C.c_int32, vp, vp]

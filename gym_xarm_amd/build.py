@@ -9,10 +9,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libxarm_hip.so")
 # one translation unit per kernel family (the fused kernels take ~30 s each to compile; the units are compiled in parallel)
 UNITS = ["xarm_hip.hip", "xarm_k_pnp.hip", "xarm_k_pnp_coop.hip", "xarm_k_reach.hip", "xarm_k_handover.hip", "xarm_k_handover_coop.hip",
-         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip", "xarm_k_policy.hip", "xarm_k_a2c.hip", "xarm_k_ppo.hip", "xarm_k_sac.hip", "xarm_k_sacw.hip", "xarm_k_td3.hip", "xarm_k_acw.hip", "xarm_k_ppow.hip", "xarm_k_a2cw.hip", "xarm_k_rollout.hip", "xarm_k_replay.hip"]
+         "xarm_k_handover2.hip", "xarm_k_stack.hip", "xarm_k_rearrange.hip", "xarm_k_render.hip", "xarm_k_her.hip", "xarm_k_norm.hip", "xarm_k_policy.hip", "xarm_k_a2c.hip", "xarm_k_ppo.hip", "xarm_k_sac.hip", "xarm_k_sacw.hip", "xarm_k_td3.hip", "xarm_k_acw.hip", "xarm_k_ppow.hip", "xarm_k_a2cw.hip", "xarm_k_rollout.hip", "xarm_k_replay.hip", "xarm_k_eval.hip"]
 HEADERS = ["xarm_dev.h", "xarm_core.h", "xarm7_pd_model.h", "xarm_reach_core.h", "xarm7_reach_model.h", "xarm_handover_core.h", "xarm_handover2_core.h",
            "xarm_stack_core.h", "xarm_rearrange_core.h", "xarm_cubes_dev.h", "xarm_coop_core.h", "xarm_reach_coop_core.h", "xarm_handover_coop_core.h", "xarm_render_core.h",
-           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h", "xarm_policy_core.h", "xarm_opt_core.h", "xarm_a2c_core.h", "xarm_grad_tile.h", "xarm_ppo_core.h", "xarm_sac_core.h", "xarm_sacw_core.h", "xarm_td3_core.h", "xarm_gemm_tile.h", "xarm_acw_core.h", "xarm_ppow_core.h", "xarm_a2cw_core.h", "xarm_rollout_core.h", "xarm_replay_core.h"]
+           "xarm_render_model.h", "xarm_her_core.h", "xarm_norm_core.h", "xarm_policy_core.h", "xarm_opt_core.h", "xarm_a2c_core.h", "xarm_grad_tile.h", "xarm_ppo_core.h", "xarm_sac_core.h", "xarm_sacw_core.h", "xarm_td3_core.h", "xarm_gemm_tile.h", "xarm_acw_core.h", "xarm_ppow_core.h", "xarm_a2cw_core.h", "xarm_rollout_core.h", "xarm_replay_core.h", "xarm_eval_core.h"]
 SOURCES = UNITS + HEADERS
 # per-unit extra flags.  Tried and not shipped: "-ffp-contract=on" for xarm_k_pnp.hip / xarm_k_handover.hip (fused multiply-adds
 # only where the source writes them, so that k_step_fast / k_ho_step_fast compute the BITS of k_step / k_ho_step on every env
@@ -39,6 +39,8 @@ SOURCES = UNITS + HEADERS
 # The device-shuffle unit (csrc/xarm_rollout_core.h) gets the flag like the learner units; the g++ build of the header is its checker.
 # The uniform-replay unit (csrc/xarm_replay_core.h) evaluates the float64 expression of xnorm::norm_value on its sampled rows, as the
 # VecNormalize unit does, and gets that unit's flag: the g++ build of the header, compiled with the same flag, gives the same bits.
+# The evaluation unit (csrc/xarm_eval_core.h) accumulates returns and the summary's moments in float64 in one fixed order and gets the flag
+# too: the g++ build of the header, compiled with the same flag, gives the same bits.
 # "-DXC_SWEEP_COPY" for the cooperative Handover unit: xc::sweep_all keeps its one-set form there (csrc/xarm_coop_core.h).  The two-set
 # form is bit for bit the same arithmetic and what the PickAndPlace unit runs, but built into this unit it made an env's result
 # depend on the env that shares its wavefront (tests/test_edge_cases.py::test_an_env_does_not_depend_on_its_batch, Handover, batch
@@ -56,7 +58,7 @@ UNIT_FLAGS = {"xarm_k_handover_coop.hip": ["-ffp-contract=on", "-DXC_SWEEP_COPY"
               "xarm_k_sacw.hip": ["-ffp-contract=off"], "xarm_k_acw.hip": ["-ffp-contract=off"],
               "xarm_k_ppow.hip": ["-ffp-contract=off"], "xarm_k_a2cw.hip": ["-ffp-contract=off"],
               "xarm_k_rollout.hip": ["-ffp-contract=off"], "xarm_k_td3.hip": ["-ffp-contract=off"],
-              "xarm_k_replay.hip": ["-ffp-contract=off"]}
+              "xarm_k_replay.hip": ["-ffp-contract=off"], "xarm_k_eval.hip": ["-ffp-contract=off"]}
 # -fno-slp-vectorize: LLVM's SLP pass pairs the scalar fp32 ops of the unrolled solver into v_pk_* instructions,
 # which need even-aligned register pairs; in this 400-live-value kernel that costs ~30 % extra v_mov and pushes
 # 1.3 KB/lane into scratch.  Without it the step kernel needs 28 B/lane of scratch and 18 % fewer instructions.

@@ -44,6 +44,7 @@
 #include "xarm_a2cw_core.h"
 #include "xarm_rollout_core.h"
 #include "xarm_replay_core.h"
+#include "xarm_eval_core.h"
 
 using namespace xd;
 
@@ -964,6 +965,53 @@ int xarm_replay_sample(const xarm_replay_layout *layout, const float *ring, int6
     a.env = out_env_i64; a.time = out_time_i64;
     const int le = xrep::launch_replay_sample(a, clock, stream);
     if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_replay_sample: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+// ------------------------------------------------------------------------------------- policy evaluation (xarm_k_eval.hip)
+static int eval_state(xeval::StepArgs &a, const char *fmt, const xarm_eval_layout *layout, double *cur_ret, int32_t *cur_len,
+                      int32_t *count, int32_t *remaining, double *records) {
+    if (const char *why = xeval::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, fmt, why);
+    if (layout->num_envs > 0 && (!cur_ret || !cur_len || !count || !remaining || !records))
+        return fail(nullptr, XARM_E_INVALID, fmt, "NULL pointer");
+    a.L = xeval::make_layout(*layout);
+    a.cur_ret = cur_ret; a.cur_len = cur_len; a.count = count; a.remaining = remaining; a.records = records;
+    a.rew = nullptr; a.done = a.success = a.keep = nullptr;
+    return XARM_OK;
+}
+
+int xarm_eval_begin(const xarm_eval_layout *layout, double *cur_ret, int32_t *cur_len_i32, int32_t *count_i32, int32_t *remaining_i32,
+                    double *records, void *stream) {
+    xeval::StepArgs a;
+    if (const int rc = eval_state(a, "xarm_eval_begin: %s", layout, cur_ret, cur_len_i32, count_i32, remaining_i32, records)) return rc;
+    if (layout->num_envs == 0) return XARM_OK;
+    const int le = xeval::launch_eval_begin(a, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_eval_begin: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_eval_step(const xarm_eval_layout *layout, double *cur_ret, int32_t *cur_len_i32, int32_t *count_i32, int32_t *remaining_i32,
+                   double *records, const float *rew, const uint8_t *done_u8, const uint8_t *success_u8, const uint8_t *keep_u8,
+                   void *stream) {
+    xeval::StepArgs a;
+    if (const int rc = eval_state(a, "xarm_eval_step: %s", layout, cur_ret, cur_len_i32, count_i32, remaining_i32, records)) return rc;
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!rew || !done_u8 || !success_u8) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_eval_step: NULL pointer");
+    a.rew = rew; a.done = done_u8; a.success = success_u8; a.keep = keep_u8;
+    const int le = xeval::launch_eval_step(a, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_eval_step: %s", hipGetErrorString((hipError_t)le));
+    return XARM_OK;
+}
+
+int xarm_eval_summary(const xarm_eval_layout *layout, const int32_t *count_i32, const double *records, double *out_f64, void *stream) {
+    if (const char *why = xeval::layout_error(layout)) return fail(nullptr, XARM_E_INVALID, "xarm_eval_summary: %s", why);
+    if (layout->num_envs == 0) return XARM_OK;
+    if (!count_i32 || !records || !out_f64) return fail(nullptr, XARM_E_INVALID, "%s", "xarm_eval_summary: NULL pointer");
+    xeval::SummaryArgs a;
+    a.L = xeval::make_layout(*layout);
+    a.count = count_i32; a.records = records; a.out = out_f64;
+    const int le = xeval::launch_eval_summary(a, stream);
+    if (le != 0) return fail(nullptr, XARM_E_HIP, "xarm_eval_summary: %s", hipGetErrorString((hipError_t)le));
     return XARM_OK;
 }
 

@@ -163,7 +163,8 @@ def flat_batch(venv, s):
 
 def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None,
                      gamma=0.95, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None, log_dir=None, device_normalize=False, config=None,
-                     log_every=50, quiet=False, check_freq=1000, horizon=None, replay=None, buffer_size=None):
+                     log_every=50, quiet=False, check_freq=1000, horizon=None, replay=None, buffer_size=None, eval_freq=None, n_eval_episodes=None,
+                     eval_envs=None, eval_env=None, eval_graph=False):
     """The driver loop that `train_sac` and `td3.train_td3` share: an off-policy learner on a batched env, with HER on a goal env
     (replay="her") or SB3's plain uniform buffer (replay="uniform": gym_xarm_amd/replay.py; the flat-observation env, or a goal env
     without relabelling; buffer_size: its transitions, default 1 000 000).  replay=None: "uniform" on a flat-observation env, else "her".
@@ -171,7 +172,9 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
     with done = 0; the HER buffer stores them as terminations.  The driver builds the env, the normaliser, the Monitor, the callback
     and the buffer, then calls `build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)`
     -> (model, act, learn): `act(nobs, it)` is the rollout action [E, A] of step `it`, `learn()` samples the buffer and runs one gradient step,
-    returning its stats (a tensor in the order of `stats`, or a dict of 0-d tensors keyed by it).  Returns (model, venv, hist)."""
+    returning its stats (a tensor in the order of `stats`, or a dict of 0-d tensors keyed by it).  eval_freq, n_eval_episodes, eval_envs,
+    eval_env, eval_graph: train.train's - the deterministic action on a second env (evaluation.EvalCallback, left on venv.eval_callback),
+    `eval_mean_reward` and `eval_success_rate` in the log records; None builds nothing.  Returns (model, venv, hist)."""
     from .her import DeviceHerReplayBuffer, HerReplayBuffer
     from .replay import DeviceReplayBuffer, ReplayBuffer
     from .train import EpisodeMonitor, SaveOnBestTrainingRewardCallback, VecNormalize
@@ -207,6 +210,10 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
         Buffer = DeviceHerReplayBuffer if dev.type == "cuda" else HerReplayBuffer
         buffer = Buffer(env, horizon=horizon, n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=seed)
     model, act, learn = build(venv, env, buffer, dev, num_envs, act_dim, learning_starts)
+    eval_callback = None
+    if eval_freq is not None:
+        from .evaluation import make_eval_callback
+        eval_callback = make_eval_callback(eval_freq, n_eval_episodes, eval_envs, eval_env, eval_graph, env_id, num_envs, seed, config, log_dir, quiet)
     obs = env.reset()
     nobs = venv.reset_from(obs) if device_normalize else venv._norm(venv._flat(obs))
     hist, t0, last, updates, window = [], time.perf_counter(), None, 0, 0
@@ -234,6 +241,8 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
             monitor.update(rew, done)
         if callback is not None:
             callback.on_step(model, venv, it * num_envs)
+        if eval_callback is not None:
+            eval_callback.on_step(model, venv, it * num_envs)
         if it > learning_starts and it % train_freq == 0:
             for _ in range(gradient_steps):
                 last = learn()
@@ -251,6 +260,8 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
             if last is not None:
                 vals = last.tolist() if torch.is_tensor(last) else [float(last[k]) for k in stats]
                 rec.update({k: float(v) for k, v in zip(stats, vals)})
+            if eval_callback is not None and eval_callback.evaluations_timesteps:
+                rec["eval_mean_reward"], rec["eval_success_rate"] = eval_callback.last_mean_reward, eval_callback.last_success_rate
             hist.append(rec)
             if not quiet:
                 print(json.dumps(rec), flush=True)
@@ -262,6 +273,9 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
     venv.monitor, venv.callback, venv.buffer = monitor, callback, buffer
     if dev.type == "cuda":
         torch.cuda.synchronize()
+    if eval_callback is not None:
+        venv.eval_callback = eval_callback
+        eval_callback.eval_env.close()
     env.close()
     return model, venv, hist
 
@@ -269,7 +283,8 @@ def train_off_policy(build, stats, env_id="XarmReach-v0", num_envs=256, steps=20
 def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
               lr=1e-3, tau=0.005, ent_coef="auto", target_entropy=None, n_sampled_goal=4, goal_selection_strategy="future", seed=0, env=None,
               log_dir=None, device_update=False, device_normalize=False, config=None, log_every=50, quiet=False, check_freq=1000, horizon=None,
-              net_arch=None, activation=None, replay=None, buffer_size=None):
+              net_arch=None, activation=None, replay=None, buffer_size=None, eval_freq=None, n_eval_episodes=None, eval_envs=None, eval_env=None,
+              eval_graph=False):
     """SAC + HER on a batched goal env, or - replay="uniform", the default on a flat-observation env such as XarmPDHandoverNoGoal-v1 - SAC on
     SB3's plain ReplayBuffer of `buffer_size` transitions (default 1 000 000), which bootstraps through time-limit truncations; "uniform" on
     a goal env is the dense-reward / no-relabel setting.  steps: calls of env.step (num_envs transitions each).  After `learning_starts` steps (default
@@ -279,7 +294,7 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
     Monitor and - with device_update - the sample's normalisation in HIP kernels); with both on a GPU env an iteration reads nothing
     back outside logging.  log_dir, check_freq: Monitor CSV, best-model checkpoints and the final statistics as in train().
     net_arch, activation: SacPolicy's (None: 64-64 tanh); a best-model checkpoint of another shape carries both beside the state_dict
-    (`load_checkpoint` rebuilds the module).  The loop itself is `train_off_policy`, shared with td3.train_td3.
+    (`load_checkpoint` rebuilds the module).  eval_freq, n_eval_episodes, eval_envs, eval_env, eval_graph: train_off_policy's.  The loop itself is `train_off_policy`, shared with td3.train_td3.
     Returns (model, venv, hist)."""
     def build(venv, env, buffer, dev, num_envs, act_dim, learning_starts):
         model = SacPolicy(venv.dim, act_dim, (64, 64) if net_arch is None else net_arch, "tanh" if activation is None else activation).to(dev)
@@ -308,7 +323,8 @@ def train_sac(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
                             train_freq=train_freq, learning_starts=learning_starts, gamma=gamma, n_sampled_goal=n_sampled_goal,
                             goal_selection_strategy=goal_selection_strategy, seed=seed, env=env, log_dir=log_dir, device_normalize=device_normalize,
                             config=config, log_every=log_every, quiet=quiet, check_freq=check_freq, horizon=horizon, replay=replay,
-                            buffer_size=buffer_size)
+                            buffer_size=buffer_size, eval_freq=eval_freq, n_eval_episodes=n_eval_episodes, eval_envs=eval_envs, eval_env=eval_env,
+                            eval_graph=eval_graph)
 
 
 def load_checkpoint(path):

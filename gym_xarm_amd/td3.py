@@ -111,12 +111,14 @@ def td3_step(model, opts, batch, n_updates, gamma=0.95, tau=0.005, policy_delay=
 def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, gradient_steps=1, train_freq=1, learning_starts=None, gamma=0.95,
               lr=1e-3, tau=0.005, policy_delay=2, target_policy_noise=0.2, target_noise_clip=0.5, action_noise=0.1, n_sampled_goal=4,
               goal_selection_strategy="future", seed=0, env=None, log_dir=None, device_update=False, device_normalize=False, config=None,
-              log_every=50, quiet=False, check_freq=1000, horizon=None, net_arch=None, activation=None, replay=None, buffer_size=None):
+              log_every=50, quiet=False, check_freq=1000, horizon=None, net_arch=None, activation=None, replay=None, buffer_size=None,
+              eval_freq=None, n_eval_episodes=None, eval_envs=None, eval_env=None, eval_graph=False):
     """TD3 + HER on a batched goal env, or TD3 on the uniform buffer (replay, buffer_size: as in sac.train_sac): sac.train_sac's arguments
     without the entropy coefficient's, plus TD3's.  Exploration is SB3's
     `_sample_action`: uniform actions in [-1, 1] while the step count is <= learning_starts, after that
     clamp(actor(nobs) + action_noise z, -1, 1); the stored action is the clamped one.  device_update: the rollout action and the TD3 step in
-    HIP kernels (DeviceTD3); device_normalize: DeviceVecNormalize, as in train_sac.  Returns (model, venv, hist)."""
+    HIP kernels (DeviceTD3); device_normalize: DeviceVecNormalize, as in train_sac.  eval_freq, n_eval_episodes, eval_envs, eval_env,
+    eval_graph: sac.train_off_policy's.  Returns (model, venv, hist)."""
     def build(venv, env, buffer, dev, num_envs, act_dim, learning_starts):
         model = Td3Policy(venv.dim, act_dim, (64, 64) if net_arch is None else net_arch, "tanh" if activation is None else activation).to(dev)
         if device_update:
@@ -154,7 +156,8 @@ def train_td3(env_id="XarmReach-v0", num_envs=256, steps=2000, batch_size=256, g
                                 train_freq=train_freq, learning_starts=learning_starts, gamma=gamma, n_sampled_goal=n_sampled_goal,
                                 goal_selection_strategy=goal_selection_strategy, seed=seed, env=env, log_dir=log_dir,
                                 device_normalize=device_normalize, config=config, log_every=log_every, quiet=quiet, check_freq=check_freq,
-                                horizon=horizon, replay=replay, buffer_size=buffer_size)
+                                horizon=horizon, replay=replay, buffer_size=buffer_size, eval_freq=eval_freq, n_eval_episodes=n_eval_episodes,
+                                eval_envs=eval_envs, eval_env=eval_env, eval_graph=eval_graph)
 
 
 def load_checkpoint(path):

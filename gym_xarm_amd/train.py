@@ -495,7 +495,7 @@ class TorchPPO(_TorchLearner):
 def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma=0.99, lr=None, seed=0, config=None, log_every=50,
           quiet=False, auto_reset=True, log_dir=None, check_freq=1000, env=None, device_normalize=False, device_policy=False,
           device_update=False, algo="a2c", n_epochs=4, batch_size=None, gae_lambda=0.95, clip_range=0.2, net_arch=None, activation=None, wide=None,
-          clip_range_vf=None, target_kl=None, shuffle=None):
+          clip_range_vf=None, target_kl=None, shuffle=None, eval_freq=None, n_eval_episodes=None, eval_envs=None, eval_env=None, eval_graph=False):
     """auto_reset="lazy" (PickAndPlace): transitions flagged info["resetting"] carry no reward and no gradient and cut the
     return like an episode end - the env spends them on its reset ticks (include/xarm_hip.h XARM_AUTO_RESET_LAZY).
     log_dir: Monitor CSV + best-model checkpoints every `check_freq` env.step calls + the final VecNormalize statistics
@@ -523,6 +523,11 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     linear schedule runs its last update at 0.  A float is never passed through set_hyper.
     shuffle (ppo with device_update; None: "torch"): "torch" - torch.randperm per epoch - or "device" - DevicePPO's xarm_perm_fill, HIP launches
     inside the update call that allocate nothing and read nothing back.
+    eval_freq (None: off, nothing is built): every eval_freq calls of env.step an evaluation.EvalCallback evaluates the deterministic policy
+    with the normaliser's statistics frozen, for n_eval_episodes episodes (default: one per eval env) on `eval_env`, or on a second env of
+    eval_envs (default min(num_envs, 1024)) envs made with seed + 1; it writes <log_dir>/evaluations.npz and best_eval_model.safetensors, the
+    log records carry `eval_mean_reward` and `eval_success_rate` of the latest evaluation, and the callback is left on venv.eval_callback.
+    eval_graph: the evaluator replays a captured iteration.
     Out of scope: schedules inside a captured graph (it holds the hyper-parameters of its capture), SAC schedules, use_sde."""
     if algo not in ("a2c", "ppo"):
         raise ValueError("algo must be 'a2c' or 'ppo'")
@@ -543,6 +548,10 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
         venv = VecNormalize(env, gamma=gamma)
         monitor = EpisodeMonitor(num_envs, dev, log_dir, env_id)
     callback = SaveOnBestTrainingRewardCallback(check_freq, log_dir, monitor, verbose=0 if quiet else 1) if log_dir else None
+    eval_callback = None
+    if eval_freq is not None:
+        from .evaluation import make_eval_callback
+        eval_callback = make_eval_callback(eval_freq, n_eval_episodes, eval_envs, eval_env, eval_graph, env_id, num_envs, seed, config, log_dir, quiet)
     model = ActorCritic(venv.dim, env.act_dim, (64, 64) if net_arch is None else tuple(net_arch), activation or "tanh").to(dev)
     n_rows = n_steps * num_envs
     batch_size = max(1, -(-n_rows // 4)) if batch_size is None else min(int(batch_size), n_rows)
@@ -593,6 +602,8 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
                 monitor.update(raw, done, None if resetting is None else ~resetting)
             if callback is not None:
                 callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (k + 1) * num_envs)
+            if eval_callback is not None:
+                eval_callback.on_step(model, venv, (it - 1) * n_steps * num_envs + (k + 1) * num_envs)
             learner.store(k, obs, a, nrew, done, resetting)
             succ_sum += (info["is_success"].float() * done.float()).sum()
             done_sum += done.float().sum()
@@ -609,6 +620,8 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
                    "env_steps_per_sec": it * n_steps * num_envs / (time.perf_counter() - t0)}
             if target_kl is not None:
                 rec["ppo_steps_applied"] = learner.steps_applied()
+            if eval_callback is not None and eval_callback.evaluations_timesteps:
+                rec["eval_mean_reward"], rec["eval_success_rate"] = eval_callback.last_mean_reward, eval_callback.last_success_rate
             hist.append(rec)
             if not quiet:
                 print(json.dumps(rec), flush=True)
@@ -619,6 +632,9 @@ def train(env_id="XarmReach-v0", num_envs=4096, updates=300, n_steps=None, gamma
     venv.monitor, venv.callback = monitor, callback
     if hasattr(torch.cuda, "synchronize") and dev.type == "cuda":
         torch.cuda.synchronize()
+    if eval_callback is not None:
+        venv.eval_callback = eval_callback
+        eval_callback.eval_env.close()
     env.close()
     return model, venv, hist
 
@@ -659,7 +675,15 @@ def main(argv=None):
     ap.add_argument("--replay", choices=("her", "uniform"), default=None, help="sac / td3: the HER buffer, or stable-baselines3's plain ReplayBuffer "
                     "(gym_xarm_amd/replay.py; default: uniform on a flat-observation env, her otherwise)")
     ap.add_argument("--buffer-size", type=int, default=None, help="sac / td3 with the uniform buffer: transitions kept (1000000)")
+    ap.add_argument("--eval-freq", type=int, default=None, help="evaluate the deterministic policy every this many env.step calls (gym_xarm_amd/evaluation.py "
+                    "EvalCallback: evaluations.npz and best_eval_model.safetensors in --log-dir; default: off)")
+    ap.add_argument("--eval-episodes", type=int, default=None, help="episodes per evaluation (default: one per eval env)")
+    ap.add_argument("--eval-envs", type=int, default=None, help="envs of the evaluation env (default: min(--num-envs, 1024))")
+    ap.add_argument("--eval-graph", action="store_true", help="the evaluator replays one captured iteration")
     args = ap.parse_args(argv)
+    if args.eval_freq is None and (args.eval_episodes is not None or args.eval_envs is not None or args.eval_graph):
+        ap.error("--eval-episodes, --eval-envs and --eval-graph need --eval-freq")
+    evalkw = dict(eval_freq=args.eval_freq, n_eval_episodes=args.eval_episodes, eval_envs=args.eval_envs, eval_graph=args.eval_graph)
     if args.algo not in ("sac", "td3") and (args.replay is not None or args.buffer_size is not None):
         ap.error("--replay and --buffer-size are for --algo sac / td3")
     if args.algo != "ppo" and (args.target_kl is not None or args.clip_range_vf is not None or args.clip_range_schedule != "constant"):
@@ -683,7 +707,7 @@ def main(argv=None):
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
                                           device_update=args.device_update, device_normalize=args.device_normalize,
                                           net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation,
-                                          replay=args.replay, buffer_size=args.buffer_size)
+                                          replay=args.replay, buffer_size=args.buffer_size, **evalkw)
         if args.save:
             save_model(args.save, model, venv)
         return
@@ -695,7 +719,7 @@ def main(argv=None):
                                           gradient_steps=args.gradient_steps, config=cfg, log_dir=args.log_dir, check_freq=args.check_freq,
                                           device_update=args.device_update, device_normalize=args.device_normalize,
                                           net_arch=None if args.net_arch is None else tuple(args.net_arch), activation=args.activation,
-                                          replay=args.replay, buffer_size=args.buffer_size, **extra)
+                                          replay=args.replay, buffer_size=args.buffer_size, **extra, **evalkw)
         if args.save:
             save_model(args.save, model, venv)
         return
@@ -705,7 +729,7 @@ def main(argv=None):
                               n_epochs=args.n_epochs, batch_size=args.batch_size, net_arch=None if args.net_arch is None else tuple(args.net_arch),
                               activation=args.activation, wide=True if args.wide else None, clip_range_vf=args.clip_range_vf, target_kl=args.target_kl,
                               lr=linear_schedule(3e-4 if args.algo == "ppo" else 7e-4) if args.lr_schedule == "linear" else None,
-                              clip_range=linear_schedule(0.2) if args.clip_range_schedule == "linear" else 0.2, shuffle=args.shuffle)
+                              clip_range=linear_schedule(0.2) if args.clip_range_schedule == "linear" else 0.2, shuffle=args.shuffle, **evalkw)
     if args.save:
         save_model(args.save, model, venv)
 

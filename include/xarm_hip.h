@@ -385,6 +385,38 @@ int xarm_replay_sample(const xarm_replay_layout *layout, const float *ring, int6
                        float *out_next_obs, float *out_act, float *out_rew, float *out_done, float *out_use,
                        int64_t *out_env_i64 /* may be NULL */, int64_t *out_time_i64 /* may be NULL */, void *stream);
 
+/* ---- device-resident policy evaluation (gym_xarm_amd/csrc/xarm_eval_core.h, xarm_k_eval.hip): the episode
+ * accounting of SB3's `evaluate_policy` for a batch of envs and the summary of its records.  Like the replay calls these need no
+ * env handle: the state is caller-owned DEVICE memory described by an xarm_eval_layout, the launches go to `stream` on the
+ * caller's current device, and the messages of XARM_E_INVALID go to xarm_last_error(NULL).
+ * With E = num_envs, N = n_eval_episodes, q, r = divmod(N, E): env i contributes its first target[i] = (N + i) / E =
+ * q + (i >= E - r) episodes after xarm_eval_begin (SB3's split), and episode k of env i is recorded at the fixed slot
+ * base[i] + k, base[i] = q i + max(0, i - (E - r)) - env-major, whatever the order in which the envs finish.
+ *   cur_ret   double [num_envs], cur_len int32 [num_envs]: return and length of the running episode
+ *   count     int32 [num_envs]: records written per env
+ *   remaining int32 [1]: N - records written; the only word a driver has to read back, and not on every step
+ *   records   double [N, 3]: return (float64 sum of the float32 rewards), length, success
+ * No call allocates, synchronises, uses floating-point atomics or reads device memory from the host; each is one launch and
+ * can be captured in a graph.  XARM_E_INVALID: a NULL layout, num_envs < 0, n_eval_episodes < 1, or with num_envs > 0 a NULL
+ * pointer other than keep_u8.  num_envs == 0 launches nothing. */
+typedef struct xarm_eval_layout {
+    int32_t num_envs;
+    int32_t n_eval_episodes;    /* >= 1 */
+} xarm_eval_layout;         /* 8 bytes */
+/* zero cur_ret, cur_len, count and records; remaining = N */
+int xarm_eval_begin(const xarm_eval_layout *layout, double *cur_ret, int32_t *cur_len_i32, int32_t *count_i32, int32_t *remaining_i32,
+                    double *records, void *stream);
+/* one env step: cur_ret += c rew, cur_len += c with c = keep_u8[i] != 0 (NULL: 1; lazy auto-reset hands ~resetting).  Where
+ * done_u8[i] != 0: if count[i] < target[i] the record (cur_ret, cur_len, success_u8[i] != 0) is written and count[i] += 1; cur_ret
+ * and cur_len are zeroed either way.  remaining falls by the records written in the call. */
+int xarm_eval_step(const xarm_eval_layout *layout, double *cur_ret, int32_t *cur_len_i32, int32_t *count_i32, int32_t *remaining_i32,
+                   double *records, const float *rew, const uint8_t *done_u8, const uint8_t *success_u8,
+                   const uint8_t *keep_u8 /* may be NULL */, void *stream);
+/* out (double [8]) = mean_reward, std_reward, mean_length, std_length, success_rate, min_reward, max_reward, n over the n records
+ * written so far (a slot counts when its index inside its env is below count, not by its value); two-pass, population std as
+ * np.std, in one fixed order: the same records give the same bits.  n == 0 gives NaN in every slot but the last. */
+int xarm_eval_summary(const xarm_eval_layout *layout, const int32_t *count_i32, const double *records, double *out_f64, void *stream);
+
 /* ---- device-resident VecNormalize + episode monitor (gym_xarm_amd/csrc/xarm_norm_core.h, xarm_k_norm.hip):
  * the running observation / return statistics, the normalised observation and reward and the Monitor's per-env return and length
  * of gym_xarm_amd/train.py (VecNormalize.step + EpisodeMonitor.update) in one stream-ordered call.  Like the HER calls these
